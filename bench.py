@@ -2,6 +2,7 @@
 """Benchmark of the ARFlow hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload NAME] [--size H W] [--batch B]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one full pass of the hot path over one batch of synthetic image pairs: model forward for
 both flow directions (cost-volume correlation + bilinear warp at every pyramid level, HIP kernels),
@@ -9,6 +10,24 @@ the unsupervised loss (census / occlusion splat / smoothness, HIP kernels), back
 gradient all-reduce (N > 1) and the Adam update.  Default workload = BASELINE.json configs[1]:
 384x640 pairs, batch 8 per GPU (weak scaling), fp32.  Inputs are resident in HBM before the timed
 region.  Rank 0 prints ONE JSON line.
+
+Every step, warm-up and timed, starts from the same state: the seeded weights and a fresh Adam state are
+restored on the device first (Checkpoint, ~0.06 ms of the ~56 ms step, inside the timed region).  A step
+is thus one training step from a fixed checkpoint, repeated, and runs with the same arguments compute the
+same thing.  Chained steps of the untrained model do not: reductions that end in float atomics differ
+between runs in the last bits, and Adam's sign-like update with the model's dynamics grows that into
+different weights within a few steps.  The level-dropout draws still follow one seeded sequence.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`).
+--full adds what takes work of its own: HIP events around every launch of every 4th timed step
+(`hot_path`, `roofline`, `host_glue`; --no-kernel-timing drops them) and, at world size 1, the CPU
+oracle baseline (`cpu_baseline`, ~25 s; --no-cpu-baseline drops it).
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed on rank 0 as
+DIR/<name>.npy (see dump_outputs()); with the same arguments its inputs are the same every run, so
+runs are comparable array by array.  Measured on the default workload, two runs of one build give the
+same loss bit for bit, flows within 1e-6 of their range, and gradients within ~3e-3 of the largest
+one in the bias gradients of the feature-extractor convolutions: sums over ~10^6 pixels whose result
+cancels far below their terms, reduced in an order that varies.
 
 N > 1: either launched by  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
 127.0.0.1 --master-port P bench.py --gpus N ...  (one rank per GPU, RCCL), or plainly as  python bench.py
@@ -389,6 +408,61 @@ def cpu_baseline(workload, height, width, batch, budget_s=25.0):
                       '%d timed step(s) after 1 warm-up, torch threads=%d' % (workload, B, height, width, len(times), cores)}
 
 
+class Checkpoint:
+    """The state every step starts from: the seeded weights and a fresh Adam state (zero moments, step 0 --
+    what torch.optim.Adam creates at its first step)."""
+
+    def __init__(self, step):
+        self.params = list(step.model.parameters())
+        self.weights = [p.detach().clone() for p in self.params]
+        self.opt = step.opt
+
+    @torch.no_grad()
+    def restore(self):
+        torch._foreach_copy_(self.params, self.weights)
+        state = [self.opt.state[p] for p in self.params if p in self.opt.state]  # empty before the first step
+        if state:
+            torch._foreach_zero_([s[k] for s in state for k in ('exp_avg', 'exp_avg_sq', 'step')])
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # under the 64 MB cap of --dump-outputs
+
+
+def dump_outputs(out_dir, step, res):
+    """What the last timed step computed, as float32 .npy files: `loss`, the flows of both directions at every
+    pyramid level (`flows_fw_<k>`, `flows_bw_<k>`, the model's output `res`) and the gradients the Adam update
+    consumed (`grads`: the flat buffer of ddp.FlatGradAllReduce, all-reduced).  The updated weights are not
+    written: from the fixed Checkpoint they are a function of `grads` alone (Adam's first update,
+    lr * g / (|g| + eps)), which turns the rounding noise of gradients that are analytically ~0 into +-lr.
+    When the arrays exceed DUMP_BUDGET_BYTES the largest ones are cut to a fixed sample of their flattened
+    elements (sorted indices drawn by numpy's default_rng(0), the same for the same sizes)."""
+    import numpy as np
+    arrays = {'loss': step.last.reshape(1)}
+
+    def add(name, v):  # a pyramid level is a tensor; the 5-frame model nests one list per frame window
+        if torch.is_tensor(v):
+            arrays[name] = v
+        else:
+            for k, f in enumerate(v):
+                add('%s_%d' % (name, k), f)
+    for key in ('flows_fw', 'flows_bw'):
+        if key in res:
+            add(key, res[key])
+    arrays['grads'] = step.reducer.flat
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    # water-filling: the small arrays are kept whole, the budget left is shared evenly among the large ones
+    left, todo = DUMP_BUDGET_BYTES // 4, sorted(arrays, key=lambda k: arrays[k].size)
+    for i, k in enumerate(todo):
+        keep = min(arrays[k].size, left // (len(todo) - i))
+        if keep < arrays[k].size:
+            idx = np.sort(np.random.default_rng(0).choice(arrays[k].size, keep, replace=False))
+            arrays[k] = arrays[k].reshape(-1)[idx]
+        left -= keep
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def _self_launch(n):
     """`python bench.py --gpus N` from a plain shell: start N ranks as CHILD processes through
     torch.distributed.run (never an exec of this process), relay rank 0's JSON line and the exit code."""
@@ -425,11 +499,18 @@ def main():
     ap.add_argument('--batch', type=int, default=8, help='image pairs per GPU')
     ap.add_argument('--feature-storage', choices=['fp32', 'bf16'], default='fp32',
                     help="opt-in: keep the correlation / warp inputs as bf16 in HBM (fp32 arithmetic); default fp32 = the headline")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-timing', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also the per-launch HIP-event timings (hot_path, roofline, host_glue) and the CPU oracle baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle baseline')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='with --full: skip the per-launch HIP-event timings')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB in all)")
     ap.add_argument('--miopen-find', '--miopen-benchmark', dest='miopen_benchmark', action='store_true',
                     help='let MIOpen time every solver per convolution (slow the first time; results go to MIOPEN_USER_DB_PATH)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    kernel_timing = args.full and not args.no_kernel_timing
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(_self_launch(args.gpus))  # before anything touches the GPU: the ranks are fresh child processes
@@ -467,6 +548,7 @@ def main():
     if args.miopen_benchmark:
         torch.backends.cudnn.benchmark = True
     step = TrainStep(args.workload, device, seed=1234, feature_storage=args.feature_storage)
+    start = Checkpoint(step)
     torch.manual_seed(1000 + rank)  # level-dropout draws differ per rank, like independent workers
     img = synthetic_pairs(args.batch, H, W, frames=step.model_cfg.get('n_frames', 2), device=device, seed=100 + rank)
 
@@ -476,9 +558,10 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
+        start.restore()
         step(img)
     sync()
-    if not args.no_kernel_timing:
+    if kernel_timing:
         AF.start_kernel_timing()
     # HIP events bracket the launches of every 4th timed step (sampling keeps the host-side cost of the
     # event records out of a launch-bound step; the averages are still taken live inside the timed region)
@@ -488,16 +571,24 @@ def main():
     # the timed steps -- what a training loop would do between epochs
     gc.collect()
     gc.disable()
+    res = {}
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if not args.no_kernel_timing:
+        if kernel_timing:
             AF.pause_kernel_timing(i % 4 != 0)
+        if args.dump_outputs and i == args.steps - 1:  # keep the model's output of the last step for dump_outputs()
+            hook = step.model.register_forward_hook(lambda mod, inp, out: res.update(out))
+        start.restore()
         step(img)
     sync()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    timing = AF.stop_kernel_timing() if not args.no_kernel_timing else {}
+    if args.dump_outputs:
+        hook.remove()
+    timing = AF.stop_kernel_timing() if kernel_timing else {}
     finite = bool(torch.isfinite(step.last).item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, res)
 
     per_rank_ms = [1e3 * elapsed / args.steps]
     if use_dist:
@@ -520,6 +611,7 @@ def main():
             'config': {'workload': '%s, %dx%d pairs, batch %d per GPU, fwd(both directions)+loss+bwd+allreduce+Adam'
                                    % (args.workload, H, W, args.batch),
                        'global_batch': args.batch * world, 'parallelism': 'dp%d' % world,
+                       'step_start': 'seeded weights + fresh Adam state, restored before every step',
                        'loss_finite': finite},
             # ranks that took part in the gradient all-reduce and the backend that carried it ('nccl' = RCCL)
             # rccl_ranks counts ranks only when RCCL ('nccl') carried the all-reduce; a gloo rehearsal reports 0 there
@@ -576,7 +668,7 @@ def main():
                                                                            'traffic': roofs[k]['traffic'],
                                                                            'valu_busy_pmc': roofs[k]['valu_busy_pmc']}
                                             for k, v in sorted(per.items(), key=lambda kv: -kv[1][0])}}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 line['cpu_baseline'] = cpu_baseline(args.workload, H, W, args.batch)
             except Exception as e:  # never lose the GPU number because the baseline leg failed

@@ -13,11 +13,11 @@ Who may import it: ``tests/``, ``__graft_entry__.smoke()`` and the ``cpu_baselin
 HIP library is missing or a tensor is not on the GPU.
 
 Parity pin: the oracle is pinned against the reference itself.  ``oracle/make_golden.py``
-imports the reference's pure-PyTorch modules from ``/root/reference`` (possible only in the
-build container; the reference never travels) and freezes inputs + reference outputs +
-reference autograd gradients as ``tests/golden/*.npz``; ``tests/test_oracle_golden.py`` checks
-every oracle function against those vectors, and ``tests/test_oracle_vs_reference.py`` re-runs
-the comparison live whenever ``/root/reference`` is present.  The bilinear sampler, pooling and
+imports the reference's pure-PyTorch modules from a checkout of the reference (``ARFLOW_REFERENCE``;
+the tests never need one) and freezes inputs + reference outputs + reference autograd gradients
+as ``tests/golden/*.npz``; ``tests/test_oracle_golden.py`` checks every oracle function against
+those vectors, and ``tests/test_oracle_vs_reference.py`` replays a seeded random sweep of them
+(``tests/golden/reference_sweep.npz``).  The bilinear sampler, pooling and
 resize arithmetic that the reference delegates to torch (``F.grid_sample``, ``scatter_add_``,
 ``AvgPool2d``, ``F.interpolate``; torch is unpinned in the reference's requirements.txt:5, the
 version here is 2.10.0) is restated explicitly in ``oracle/ops.py`` and additionally checked

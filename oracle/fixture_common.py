@@ -70,3 +70,70 @@ def pool_to_quarter(f, full_h):
     k = f.shape[2] * 4 // full_h
     return torch.nn.functional.avg_pool2d(f, k) if k > 1 else f
 
+
+
+# ---- the seeded sweep of tests/test_oracle_vs_reference.py (fixture tests/golden/reference_sweep.npz) ----------------
+# Its inputs are regenerated from their seeds and checked against stored CRC-32 fingerprints.  The reference's
+# correlation and warp outputs are stored losslessly as the difference of their IEEE-754 bit patterns from a float64
+# prediction (plain torch below, independent of oracle/ops.py): small integers that compress ~5x better than the floats.
+SWEEP_CORR_SHAPES = [(2, 32, 24, 40), (1, 7, 9, 33), (3, 16, 8, 14)]
+
+
+def sweep_corr_inputs(shape):
+    g = torch.Generator().manual_seed(sum(shape))
+    x1 = torch.randn(*shape, generator=g)
+    x2 = torch.randn(*shape, generator=g)
+    return x1, x2, torch.randn(shape[0], 81, *shape[2:], generator=g)
+
+
+def sweep_warp_inputs():
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(2, 6, 19, 27, generator=g)
+    flow = 3 * torch.randn(2, 2, 19, 27, generator=g)
+    return x, flow, torch.randn(2, 6, 19, 27, generator=g)
+
+
+def sweep_mask_inputs():
+    g = torch.Generator().manual_seed(11)
+    flow = 2.5 * torch.randn(2, 2, 24, 31, generator=g)
+    im1, im2 = torch.rand(2, 3, 24, 31, generator=g), torch.rand(2, 3, 24, 31, generator=g)
+    return flow, im1, im2, (torch.rand(2, 1, 24, 31, generator=g) > 0.3).float()
+
+
+def fingerprint(t):
+    """CRC-32 of a tensor's float32 bytes: detects a changed random stream."""
+    import zlib
+    return torch.tensor(zlib.crc32(t.detach().float().contiguous().numpy().tobytes()), dtype=torch.int64)
+
+
+def predict_corr(x1, x2, d=4):
+    """float64 cost volume and its input gradients for the gradient `go` (a closure over autograd)."""
+    def run(go):
+        a, b = x1.double().requires_grad_(True), x2.double().requires_grad_(True)
+        H, W = a.shape[2:]
+        bp = torch.nn.functional.pad(b, (d, d, d, d))
+        y = torch.stack([(a * bp[:, :, i:i + H, j:j + W]).mean(1) for i in range(2 * d + 1) for j in range(2 * d + 1)], 1)
+        return (y.detach(),) + tuple(g.detach() for g in torch.autograd.grad(y, [a, b], go.double()))
+    return run
+
+
+def predict_flow_warp(x, flow, pad, align_corners):
+    """float64 bilinear warp (grid normalised by (W-1, H-1) whatever align_corners is) and its gradients for `go`."""
+    def run(go):
+        a, f = x.double().requires_grad_(True), flow.double().requires_grad_(True)
+        B, _, H, W = f.shape
+        ys, xs = torch.meshgrid(torch.arange(H, dtype=a.dtype), torch.arange(W, dtype=a.dtype), indexing='ij')
+        grid = torch.stack([2 * (xs + f[:, 0]) / (W - 1) - 1, 2 * (ys + f[:, 1]) / (H - 1) - 1], -1)
+        y = torch.nn.functional.grid_sample(a, grid, mode='bilinear', padding_mode=pad, align_corners=align_corners)
+        return (y.detach(),) + tuple(g.detach() for g in torch.autograd.grad(y, [a, f], go.double()))
+    return run
+
+
+def residual_encode(ref, pred):
+    """fp32 `ref` as integer steps of its bit pattern from fp32(`pred`): exact, whatever the prediction."""
+    r = ref.detach().float().contiguous().view(torch.int32).long() - pred.float().contiguous().view(torch.int32).long()
+    return r.int() if int(r.abs().max()) < 2 ** 31 else r
+
+
+def residual_decode(r, pred):
+    return (pred.float().contiguous().view(torch.int32).long() + r.long()).int().view(torch.float32)

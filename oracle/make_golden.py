@@ -2,7 +2,7 @@
 
 Run only in the build container, where the reference is mounted read-only at /root/reference:
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py [--only ops|losses|models]
+    PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py [--only ops|losses|models|models5|examples|general|sweep]
 
 Each fixture stores the inputs, the reference outputs and the reference autograd gradients for
 one hot-path function, so that tests on the GPU box (where the reference does not exist) can pin
@@ -26,6 +26,8 @@ OUT = os.path.join(os.path.dirname(HERE), 'tests', 'golden')
 sys.path[:] = [p for p in sys.path if os.path.abspath(p or '.') != HERE]
 sys.path.insert(0, os.path.dirname(HERE))
 from oracle.fixture_common import Cfg, fill_deterministic, loss_cfgs, pool_to_quarter, synth_pair  # noqa: E402
+from oracle.fixture_common import (SWEEP_CORR_SHAPES, fingerprint, predict_corr, predict_flow_warp, residual_decode,  # noqa: E402
+                                   residual_encode, sweep_corr_inputs, sweep_mask_inputs, sweep_warp_inputs)
 
 
 def field(B, C, H, W, a, b, c, d):
@@ -369,6 +371,54 @@ def gen_general():
     save('general', **out)
 
 
+def gen_sweep():
+    """The seeded random sweep of tests/test_oracle_vs_reference.py: correlation at three shapes, flow_warp over
+    pad x align_corners, the masks, census, SSIM and smoothness terms.  Inputs as fingerprints (the tests regenerate
+    them), correlation / warp outputs and gradients as residuals from a float64 prediction, the rest as arrays."""
+    from models.correlation_native import Correlation
+    from utils import warp_utils, uflow_utils
+    from losses import loss_blocks
+    out = {}
+
+    def residual(key, ref, pred):
+        out[key + '_r'] = residual_encode(ref, pred)
+        out[key + '_sum'] = ref.detach().double().sum()
+        assert torch.equal(residual_decode(out[key + '_r'], pred), ref.detach().float()), key
+
+    for shape in SWEEP_CORR_SHAPES:
+        tag = 'corr_%s' % 'x'.join(str(s) for s in shape)
+        x1, x2, go = sweep_corr_inputs(shape)
+        a, b = x1.clone().requires_grad_(True), x2.clone().requires_grad_(True)
+        y = Correlation(pad_size=4, kernel_size=1, max_displacement=4, stride1=1, stride2=1, corr_multiply=1)(a, b)
+        pred = predict_corr(x1, x2)(go)
+        for k, ref, p in zip(('_y', '_gx1', '_gx2'), (y,) + grads(y, [a, b], go), pred):
+            residual(tag + k, ref, p)
+        out.update({tag + '_fp_x1': fingerprint(x1), tag + '_fp_x2': fingerprint(x2), tag + '_fp_g': fingerprint(go)})
+
+    x, fl, go = sweep_warp_inputs()
+    out.update(warp_fp_x=fingerprint(x), warp_fp_flow=fingerprint(fl), warp_fp_g=fingerprint(go))
+    for pad in ('zeros', 'border'):
+        for ac in (True, False):
+            a, f = x.clone().requires_grad_(True), fl.clone().requires_grad_(True)
+            y = warp_utils.flow_warp(a, f, pad=pad, align_corners=ac)
+            pred = predict_flow_warp(x, fl, pad, ac)(go)
+            tag = 'warp_%s_%d' % (pad, int(ac))
+            for k, ref, p in zip(('_y', '_gsrc', '_gflow'), (y,) + grads(y, [a, f], go), pred):
+                residual(tag + k, ref, p)
+
+    fl, im1, im2, mask = sweep_mask_inputs()
+    out.update(m_fp_flow=fingerprint(fl), m_fp_im1=fingerprint(im1), m_fp_im2=fingerprint(im2), m_fp_mask=fingerprint(mask),
+               m_range_map=uflow_utils.compute_range_map(fl), m_border_mask=warp_utils.border_mask(fl),
+               m_mask_invalid=uflow_utils.mask_invalid(uflow_utils.flow_to_warp(fl)),
+               m_ssim=loss_blocks.SSIM(im1, im2), m_smooth1=loss_blocks.smooth_grad_1st(fl, im1, 10.),
+               m_smooth2=loss_blocks.smooth_grad_2nd(fl, im1, 10.))
+    for ps in (7, 3):
+        b = im2.clone().requires_grad_(True)
+        y = uflow_utils.census_loss(im1, b, mask, ps)
+        out.update({'m_census%d' % ps: y, 'm_census%d_g' % ps: torch.autograd.grad(y, [b])[0]})
+    save('reference_sweep', **out)
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default='all')
@@ -391,3 +441,5 @@ if __name__ == '__main__':
             gen_examples()
         if args.only in ('all', 'general'):
             gen_general()
+        if args.only in ('all', 'sweep'):
+            gen_sweep()

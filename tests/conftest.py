@@ -13,15 +13,11 @@ GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 
 def pytest_configure(config):
     config.addinivalue_line('markers', 'gpu: needs a real MI355X (run with -m gpu on the GPU box)')
-    config.addinivalue_line('markers', 'reference: needs /root/reference (build container only)')
 
 
 def pytest_collection_modifyitems(config, items):
-    have_ref = os.path.isdir(os.environ.get('ARFLOW_REFERENCE', '/root/reference'))
     have_gpu = torch.cuda.is_available()
     for item in items:
-        if 'reference' in item.keywords and not have_ref:
-            item.add_marker(pytest.mark.skip(reason='reference not mounted'))
         if 'gpu' in item.keywords and not have_gpu:
             item.add_marker(pytest.mark.skip(reason='no GPU visible'))
 

@@ -81,3 +81,67 @@ def test_valu_slot_model_against_issued_instructions():
         assert 0.33 <= ratio <= 1.25, '%s: modelled %.3g slots vs %.3g issued lane-instructions (ratio %.2f)' % (name, plain, issued, ratio)
         checked += 1
     assert checked >= 4
+
+
+def test_dump_outputs_names_dtype_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: every array of the last step lands as float32 <name>.npy, small arrays whole, the total
+    under 64 MB, and a cut array is the same fixed sample of its elements every time (runs stay comparable)."""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    step = types.SimpleNamespace(last=torch.tensor(1.5), reducer=types.SimpleNamespace(flat=torch.randn(17 * 2 ** 20, generator=g)))
+    flows = [torch.randn(2, 2, 8 // s, 12 // s, generator=g) for s in (1, 2)]
+    res = {'flows_fw': flows, 'flows_bw': [[f + 1 for f in flows], [f + 2 for f in flows]]}
+    dirs = [str(tmp_path / n) for n in ('a', 'b')]
+    for d in dirs:
+        bench.dump_outputs(d, step, res)
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(['loss.npy', 'grads.npy', 'flows_fw_0.npy', 'flows_fw_1.npy', 'flows_bw_0_0.npy',
+                            'flows_bw_0_1.npy', 'flows_bw_1_0.npy', 'flows_bw_1_1.npy'])
+    total = sum(os.path.getsize(os.path.join(dirs[0], n)) for n in names)
+    assert total <= 64 * 2 ** 20
+    a = {n[:-4]: np.load(os.path.join(dirs[0], n)) for n in names}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a['loss'].tolist() == [1.5]
+    assert np.array_equal(a['flows_fw_1'], flows[1].numpy()) and np.array_equal(a['flows_bw_1_0'], flows[0].numpy() + 2)
+    flat = step.reducer.flat.numpy()
+    keep = a['grads'].size
+    assert 0 < keep < flat.size  # the one array over its share: a sample, by the rule bench.dump_outputs() states
+    assert np.array_equal(a['grads'], flat[np.sort(np.random.default_rng(0).choice(flat.size, keep, replace=False))])
+    for n in a:
+        assert np.array_equal(a[n], np.load(os.path.join(dirs[1], n + '.npy'))), n
+
+
+def test_checkpoint_restore_repeats_the_first_step():
+    """bench.Checkpoint: after restore(), a training step computes exactly what the first step of a freshly built model and
+    optimizer computes -- seeded weights, zero Adam moments, step count 0 -- however many steps ran before."""
+    import types
+    import torch
+    import bench
+
+    def build():
+        torch.manual_seed(0)
+        model = torch.nn.Sequential(torch.nn.Linear(6, 5), torch.nn.Tanh(), torch.nn.Linear(5, 3))
+        return types.SimpleNamespace(model=model, opt=torch.optim.Adam(model.parameters(), lr=1e-2))
+
+    x = torch.randn(8, 6, generator=torch.Generator().manual_seed(1))
+
+    def train(s):
+        s.opt.zero_grad()
+        s.model(x).square().mean().backward()
+        s.opt.step()
+        return [p.detach().clone() for p in s.model.parameters()]
+
+    fresh = train(build())
+    s = build()
+    start = bench.Checkpoint(s)
+    start.restore()  # before the first step: no optimizer state yet
+    assert all(torch.equal(a, b) for a, b in zip(train(s), fresh))
+    for _ in range(3):
+        train(s)
+    start.restore()
+    assert all(torch.equal(p, w) for p, w in zip(s.model.parameters(), start.weights))
+    assert all(int(s.opt.state[p]['step']) == 0 for p in s.model.parameters())
+    assert all(torch.equal(a, b) for a, b in zip(train(s), fresh))
