@@ -467,9 +467,14 @@ class LevelFunction(torch.autograd.Function):
         else:
             x1n = torch.empty_like(x1)
             x1n_ptr, x1n_bs = x1n.data_ptr(), C * H * W
+        for name, rows in (('x1_rows', x1_rows), ('x2_rows', x2_rows)):
+            if rows is None:
+                continue
+            if rows.dtype != torch.float64 or rows.dim() != 3 or rows.shape[0] != B or rows.shape[2] != 2:
+                raise ValueError('%s must be [B, rows, 2] float64' % name)
+            if rows.device != x1.device:
+                raise ValueError('%s must be on the device of the feature maps' % name)
         if x1_rows is not None:
-            if x1_rows.dtype != torch.float64 or x1_rows.shape[0] != B or x1_rows.shape[2] != 2:
-                raise ValueError('x1_rows must be [B, rows, 2] float64')
             x1_rows = x1_rows.contiguous()
         if x2_rows is not None:
             x2_rows = x2_rows.contiguous() if (not has_flow and x1_rows is not None) else None

@@ -122,3 +122,16 @@ def test_correlation_signature_follows_correlation_native():
     assert c.general is None and c.output_dim == 9
     c = Correlation(pad_size=3, kernel_size=3, max_displacement=2, stride1=1, stride2=2)
     assert c.general == (3, 3, 2, 1, 2) and c.pad_size == 3 and c.output_dim == 3
+
+
+def test_level_dispatch_mirror_matches_the_library(lib):
+    """tests/test_level_gpu.py::level_branch restates the level's dispatch to assert which kernels each test shape reaches.
+    Its channel split (af_channel_split, which decides between the both-roles and the split backward) is pinned here against
+    the library: arflow_level_acc_rows(.., has_flow=1) is tiles per sample x the split."""
+    from tests.test_level_gpu import PAD_ALIGN_SHAPES, level_branch
+    shapes = [s[:4] for s in PAD_ALIGN_SHAPES] + [(2, 8, 48, 80), (5, 4, 256, 448), (9, 32, 96, 160), (18, 32, 96, 160)]
+    for B, C, H, W in shapes:
+        per = -(-W // 32) * -(-H // 8)
+        split = lib.arflow_level_acc_rows(B, C, H, W, 1) // per
+        bwd = level_branch(B, C, H, W, env={})[1]
+        assert bwd == ('both' if per * B * split <= 2048 else 'split'), (B, C, H, W, split, bwd)

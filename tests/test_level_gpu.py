@@ -42,11 +42,14 @@ def smooth(t):
     return F.avg_pool2d(F.pad(t, (1, 1, 1, 1), mode='replicate'), 3, 1)
 
 
-def oracle_level(O, x1, x2, flow_c, mode, up_align, pad, member, coord='arflow'):
+def oracle_level(O, x1, x2, flow_c, mode, up_align, pad, member, coord='arflow', align=None, coarse=True):
+    """align: the warp's align_corners (default: up_align, as PWCLiteUflow ties them); coarse=False: flow_c already is
+    the full-resolution flow (no upsample, not concatenated)."""
+    align = up_align if align is None else align
     if flow_c is not None:
-        flow = F.interpolate(flow_c * 2, scale_factor=2, mode='bilinear', align_corners=up_align)
+        flow = F.interpolate(flow_c * 2, scale_factor=2, mode='bilinear', align_corners=up_align) if coarse else flow_c
         if coord == 'arflow':
-            x2w = O.flow_warp(x2, flow, pad=pad, align_corners=up_align)
+            x2w = O.flow_warp(x2, flow, pad=pad, align_corners=align)
         else:
             x2w = O.resample(x2, O.flow_to_warp(flow))
     else:
@@ -58,7 +61,7 @@ def oracle_level(O, x1, x2, flow_c, mode, up_align, pad, member, coord='arflow')
                                             moments_across_images=True)
     pre = O.correlation(y1, y2, 4)
     vol = F.leaky_relu(pre, 0.1)
-    parts = [vol, y1] + ([flow] if flow is not None else []) + [member]
+    parts = [vol, y1] + ([flow] if (flow is not None and coarse) else []) + [member]
     return torch.cat(parts, 1), flow, pre, x2w
 
 
@@ -85,7 +88,7 @@ def test_level_forward_backward_vs_oracle(AF, O, shape, mode):
     member = torch.randn(B, 5, H, W, generator=gen)
     for t in (x1, x2, member) + ((flow_c,) if has_flow else ()):
         t.requires_grad_(True)
-    ref_buf, ref_flow, pre, ref_x2w = oracle_level(O, x1, x2, flow_c, mode, True, 'zeros', member)
+    ref_buf, ref_flow, pre, ref_x2w = oracle_level(O, x1, x2, flow_c, mode, True, 'zeros', member, align=True)
     gbuf = torch.randn(ref_buf.shape, generator=gen)
     gbuf[:, :81] *= (pre.detach().abs() > 1e-6).float()  # at a LeakyReLU kink either derivative is right
     gflow = torch.randn(B, 2, H, W, generator=gen) if has_flow else None
@@ -164,6 +167,10 @@ def test_level_uflow_layout(AF, O, shape):
     """The level as PWCFlow runs it (models/uflow_model.py:160-198): upsample(flow, is_flow=True) (align_corners=False),
     resample(f2, flow_to_warp(flow_up)), 'avg' statistics, cat([context_up, flow_up, volume, features1]) -- the
     normalised first map is NOT concatenated (kept on the side for the backward), the raw one is a member."""
+    _uflow_layout_case(AF, O, shape)
+
+
+def _uflow_layout_case(AF, O, shape, mask_ties=False):
     B, C, H, W = shape
     gen = torch.Generator().manual_seed(H)
     x1 = (smooth(torch.randn(B, C, H, W, generator=gen)) + 0.2).requires_grad_(True)
@@ -177,7 +184,9 @@ def test_level_uflow_layout(AF, O, shape):
     pre = O.correlation(y1, y2, 4)
     ref = torch.cat([ctx, flow, F.leaky_relu(pre, 0.1), x1], 1)
     gbuf = torch.randn(ref.shape, generator=gen)
-    gbuf[:, 8:8 + 81] *= (pre.detach().abs() > 1e-6).float()
+    vol_atol = (2e-6 + 2e-5 * float(x2.detach().abs().max())) / 2
+    # (mask_ties: the kink mask at the volume bound, as in run_level_case)
+    gbuf[:, 8:8 + 81] *= (pre.detach().abs() > (vol_atol if mask_ties else 1e-6)).float()
     gflow = torch.randn(B, 2, H, W, generator=gen)
     refs = torch.autograd.grad((ref * gbuf).sum() + (flow * gflow).sum(), [x1, x2, flow_c, ctx])
 
@@ -186,12 +195,419 @@ def test_level_uflow_layout(AF, O, shape):
     buf, fu = AF.level(a, b, fc, cfg, cx, a)
     fmax = float(flow.detach().abs().max())
     assert_close(fu, flow, 4e-7 * max(fmax, 1.0), 0, 'flow_up')
-    assert_close(buf[:, 8:8 + 81], ref[:, 8:8 + 81], (2e-6 + 2e-5 * float(x2.detach().abs().max())) / 2, 5e-6, 'volume')
+    assert_close(buf[:, 8:8 + 81], ref[:, 8:8 + 81], vol_atol, 5e-6, 'volume')
     assert_close(buf[:, :6], ctx, 0, 0, 'context copy')
     assert_close(buf[:, -C:], x1, 0, 0, 'features1 copy')
     got = torch.autograd.grad((buf * gbuf.cuda()).sum() + (fu * gflow.cuda()).sum(), [a, b, fc, cx])
+    keep = tie_mask(O, flow, H, W, True, True, coord='uflow') if mask_ties else None
     for n, g, r in zip(['d x1', 'd x2', 'd flow', 'd context'], got, refs):
-        assert_close(g, r, 2e-5 * float(r.abs().max()) + 1e-6, 1e-4, n)
+        tol = 2e-5 * float(r.abs().max()) + 1e-6
+        if n == 'd flow' and keep is not None:
+            g, r = g.cpu()[keep], r[keep]
+        assert_close(g, r, tol, 1e-4, n)
+
+
+# ---- which kernels a level call takes ------------------------------------------------------------------------------------
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def level_branch(B, C, H, W, has_flow=True, coarse=True, env=None):
+    """Test-side mirror of the dispatch in level.hip / level_small.hip / warp.hip: (forward, backward) kernels of a level
+    call.  forward: 'small' (af_level_small_ok: one workgroup per sample), 'tiled4' (level_warp_fwd_kernel<true, 4>, a
+    coarse flow and >= 768 tiles) or 'tiled'; backward: 'both' (level_warp_bwd_both_kernel, tiles * split <= 2048), 'split'
+    (lds_scatter::warp_bwd_src_kernel<true> + level_warp_bwd_flow_kernel<false>), 'slab' / 'gather' (ARFLOW_WARP_SLAB /
+    ARFLOW_WARP_GATHER, read from `env`, default os.environ).  tests/test_abi_cpu.py pins the channel split against the
+    library's own arflow_level_acc_rows."""
+    import os
+    env = os.environ if env is None else env
+    per = _ceil(W, 32) * _ceil(H, 8)
+    tiles = per * B
+    small = (env.get('ARFLOW_LEVEL_SMALL', '')[:1] != '0' and H * W <= 256 and (H + 8) * (W + 8) <= 1536 and W % 4 == 0
+             and C % 8 == 0 and H * (W // 4) * 3 <= 768 and C * H * W <= 32768)
+    fwd = 'small' if small else ('tiled4' if has_flow and coarse and tiles >= 768 else 'tiled')
+    if not has_flow:
+        return fwd, None
+    nsplit = 1
+    while nsplit * 2 <= C // 4 and tiles * nsplit * 2 <= 2048:
+        nsplit *= 2
+    slab = env.get('ARFLOW_WARP_SLAB', '')[:1] == '1' and tiles >= 768 and tiles // B <= 1024 and per <= 1024
+    gather = (env.get('ARFLOW_WARP_GATHER', '')[:1] == '1' and not slab and tiles >= 768 and H <= 4095 and W <= 4095)
+    if gather:
+        bwd = 'gather'
+    elif tiles * nsplit <= 2048 and not slab:
+        bwd = 'both'
+    else:
+        bwd = 'slab' if slab else 'split'
+    return fwd, bwd
+
+
+def check_branch(shape, fwd, bwd, coarse=True):
+    """The shape still takes the kernels it was chosen for (default environment); returns what it takes in this process."""
+    B, C, H, W = shape[:4]
+    got = level_branch(B, C, H, W, True, coarse, env={})
+    assert got == (fwd, bwd), '%s no longer reaches the %s forward / %s backward form (the dispatch rules now give %s)' \
+        % ('x'.join(map(str, shape[:4])), fwd, bwd, got)
+    return level_branch(B, C, H, W, True, coarse)
+
+
+# The split backward: 7 x 16 tiles x 20 = 2240 > 2048 at channel split 1, ragged in x (220 = 6.9 x 32) and y (126 = 15.75 x 8).
+# Coordinates stay below 256, the range the tolerances behind the warp were measured in: they are 2 ulp of the coordinate
+# times the feature slope (module docstring), and at 380 x 636 (coordinates past 512, 4x the ulp) the volume differs from
+# the oracle by up to 1.35e-4 against the 4e-5 of this bound -- that size needs a bound scaled by ulp(W) of its own.
+SPLIT = (20, 8, 126, 220)
+# (B, C, H, W, forward, backward) under the default environment (check_branch asserts it)
+PAD_ALIGN_SHAPES = [
+    (1, 32, 10, 12, 'small', 'both'), (2, 32, 12, 16, 'small', 'both'),  # one workgroup per sample
+    (16, 32, 24, 40, 'tiled', 'both'), (3, 8, 6, 44, 'tiled', 'both'),    # channel split 8 / 2, + up2_bwd
+    (16, 32, 96, 160, 'tiled4', 'both'),                                 # 960 tiles; slab / gather when opted in
+    SPLIT + ('tiled4', 'split'),                                         # the split form
+]
+
+
+def shape_id(s):
+    return 'x'.join(str(v) for v in s[:4])
+
+
+def smooth_inputs(shape, seed, coarse_flow=None):
+    B, C, H, W = shape[:4]
+    gen = torch.Generator().manual_seed(seed)
+    x1 = smooth(torch.randn(B, C, H, W, generator=gen)) + 0.3
+    x2 = smooth(torch.randn(B, C, H, W, generator=gen)) + 0.1
+    flow_c = smooth(1.5 * torch.randn(B, 2, H // 2, W // 2, generator=gen)) if coarse_flow is None else coarse_flow
+    member = torch.randn(B, 5, H, W, generator=gen)
+    return gen, x1, x2, flow_c, member
+
+
+def sample_coords(O, flow, Hs, Ws, align, coord='arflow'):
+    """The oracle's own fp32 sampling coordinates (O.flow_warp / O.resample) for a full-resolution flow."""
+    B, _, H, W = flow.shape
+    flow = flow.detach()
+    xs, ys = O._pixel_grid(B, H, W, flow)
+    if coord == 'arflow':
+        gx, gy = 2.0 * (xs + flow[:, 0]) / (W - 1) - 1.0, 2.0 * (ys + flow[:, 1]) / (H - 1) - 1.0
+        return O._unnormalize(gx, Ws, align), O._unnormalize(gy, Hs, align), xs, ys
+    gx = 2.0 * (xs + flow[:, 0]) / max(Ws - 1, 1) - 1.0
+    gy = 2.0 * (ys + flow[:, 1]) / max(Hs - 1, 1) - 1.0
+    return O._unnormalize(gx, Ws, True), O._unnormalize(gy, Hs, True), xs, ys
+
+
+def tie_mask(O, flow, Hs, Ws, align, coarse, coord='arflow', pad='zeros'):
+    """Where d/dflow has no unique value: the oracle's coordinate lies within a few ulp of a tie of the bilinear sampler --
+    an integer (the tap cell changes there; 0 and size-1, where `border` clamps, are integers too).  The kernel's
+    coordinate may sit an ulp or two of |p| + |flow| away from the oracle's (the upsampled flow is rounded in a different
+    order), so a tie counts within 8 ulp of that -- where a tap can be in the image (integers -1 .. size under `zeros`,
+    0 .. size-1 under `border`: further out both sides agree on a zero gradient).  Computed from the ORACLE's coordinates
+    only.  Returns the positions
+    of the flow gradient ([B, 2, h, w] bool) to compare: with a coarse flow every coarse cell the up2 adjoint feeds from
+    a tie pixel (fine rows / columns 2q-3 .. 2q+3) is left out."""
+    ix, iy, xs, ys = sample_coords(O, flow, Hs, Ws, align, coord)
+    f = flow.detach()
+    tie = torch.zeros_like(ix, dtype=torch.bool)
+    lo = 0 if pad == 'border' else -1
+    for c, p, u, n in ((ix, xs, f[:, 0], Ws), (iy, ys, f[:, 1], Hs)):
+        k = torch.round(c)
+        tie |= ((c - k).abs() <= 2.0 ** -20 * (p.abs() + u.abs() + 1.0)) & (k >= lo) & (k <= n - 1 - lo)
+    if coarse:
+        tie = F.max_pool2d(tie[:, None].float(), 7, stride=2, padding=3)[:, 0] > 0
+    return (~tie)[:, None].expand(-1, 2, -1, -1)
+
+
+def run_level_case(AF, O, x1, x2, flow_c, member, pad, align, up_align, tag, mode='joint', coarse=True,
+                   mask_ties=True, dx2_grow=1.0):
+    """One fused level call against oracle_level: forward (flow_up, volume, x1n, member copy) and every input gradient,
+    at the tolerances of test_level_forward_backward_vs_oracle.  d/dflow is compared away from the sampler's ties
+    (tie_mask) unless mask_ties=False (coordinates known bit-equal).  dx2_grow scales the bound of the atomic-fed d x2
+    (explained where it is passed)."""
+    B, C, H, W = x1.shape
+    gen = torch.Generator().manual_seed(B * 7 + H + W)
+    for t in (x1, x2, member, flow_c):
+        t.requires_grad_(True)
+    ref_buf, ref_flow, pre, _ = oracle_level(O, x1, x2, flow_c, mode, up_align, pad, member, align=align, coarse=coarse)
+    xmax = float(x2.detach().abs().max())
+    vol_atol = 2e-6 + 2e-5 * xmax
+    gbuf = torch.randn(ref_buf.shape, generator=gen)
+    # at a LeakyReLU kink either derivative is right.  The kernel takes the slope from the sign of ITS pre-activation, which
+    # the volume check below holds within vol_atol of the oracle's: only entries with |pre| > vol_atol have one sign on
+    # both sides (behind the warp, at a few million pixels, a 1e-6 threshold leaves sign flips: O(1) in d x1 at C = 8)
+    gbuf[:, :81] *= (pre.detach().abs() > vol_atol).float()
+    gflow = torch.randn(B, 2, H, W, generator=gen) if coarse else None
+    loss = (ref_buf * gbuf).sum() + ((ref_flow * gflow).sum() if coarse else 0.0)
+    refs = torch.autograd.grad(loss, [x1, x2, member, flow_c])
+
+    a, b, m, fc = [t.detach().cuda().requires_grad_(True) for t in (x1, x2, member, flow_c)]
+    if coarse:
+        cfg = AF.LevelCfg(['vol', 'x1n', 'flow', 0], mode, 0.1, 4, True, up_align, pad, align)
+        buf, flow = AF.level(a, b, fc, cfg, m)
+    else:
+        cfg = AF.LevelCfg(['vol', 'x1n', 0], mode, 0.1, 4, False, up_align, pad, align)
+        buf, flow = AF.level(a, b, fc, cfg, m), None
+    assert buf.shape == ref_buf.shape
+    fmax = float(ref_flow.detach().abs().max())
+    if coarse:
+        assert_close(flow, ref_flow, 4e-7 * max(fmax, 1.0), 0, 'flow_up ' + tag)
+        assert_close(buf[:, 81 + C:81 + C + 2], ref_flow, 4e-7 * max(fmax, 1.0), 0, 'flow slot ' + tag)
+    assert_close(buf[:, 81:81 + C], ref_buf[:, 81:81 + C], 1e-6, 5e-6, 'x1n ' + tag)
+    assert_close(buf[:, :81], ref_buf[:, :81], vol_atol, 1e-5, 'volume ' + tag)
+    assert_close(buf[:, -5:], member, 0, 0, 'member copy ' + tag)
+    loss_g = (buf * gbuf.cuda()).sum() + ((flow * gflow.cuda()).sum() if coarse else 0.0)
+    got = torch.autograd.grad(loss_g, [a, b, m, fc])
+    keep = tie_mask(O, ref_flow, H, W, align, coarse, pad=pad) if mask_ties else None
+    for n, g, r in zip(['d x1', 'd x2', 'd member', 'd flow_c' if coarse else 'd flow'], got, refs):
+        if n == 'd member':
+            assert_close(g, r, 0, 0, n + ' ' + tag)
+            continue
+        atol, rtol = 2e-5 * float(r.abs().max()) + 1e-6, 1e-4
+        if n == 'd x2':
+            atol, rtol = atol * dx2_grow, rtol * dx2_grow
+        if n.startswith('d flow') and keep is not None:
+            assert float(keep.float().mean()) > 0.9, 'tie mask leaves %.3f of %s' % (float(keep.float().mean()), tag)
+            g, r = g.cpu()[keep], r[keep]
+        assert_close(g, r, atol, rtol, n + ' ' + tag)
+
+
+PAD_ALIGN = [('border', True), ('border', False), ('zeros', False)]
+
+
+@pytest.mark.parametrize('pad,align', PAD_ALIGN, ids=lambda v: str(v))
+@pytest.mark.parametrize('shape', PAD_ALIGN_SHAPES, ids=shape_id)
+def test_level_pad_align(AF, O, shape, pad, align):
+    """`border` padding and align_corners=False (PWCLiteUflow passes both from its config, up_align = align) through every
+    forward and backward form of the fused level; the shapes are chosen by the branch they take (check_branch)."""
+    check_branch(shape, shape[4], shape[5])
+    _, x1, x2, flow_c, member = smooth_inputs(shape, sum(shape[:4]) + 3 * align + (5 if pad == 'border' else 0))
+    run_level_case(AF, O, x1, x2, flow_c, member, pad, align, align, '%s %s %s' % (shape_id(shape), pad, align))
+
+
+@pytest.mark.parametrize('shape,pad,align,up_align', [((2, 32, 12, 16), 'border', True, False),
+                                                      ((16, 32, 24, 40), 'zeros', False, True)],
+                         ids=['small-border-up_align0', 'tiled-zeros-align0'])
+def test_level_up_align_differs_from_align(AF, O, shape, pad, align, up_align):
+    """The upsample's and the warp's align_corners are separate arguments of the level: each reaches its own stage."""
+    check_branch(shape, 'small' if shape[2] == 12 else 'tiled', 'both')
+    _, x1, x2, flow_c, member = smooth_inputs(shape, 41 + shape[2])
+    run_level_case(AF, O, x1, x2, flow_c, member, pad, align, up_align, '%s %s align %s up %s' % (shape, pad, align,
+                                                                                                  up_align))
+
+
+def adversarial_flow(kind, B, H, W, gen):
+    """Coarse flows ([B, 2, H/2, W/2], upsampled x2 by the level) that the smooth test fields never produce."""
+    h, w = H // 2, W // 2
+    if kind == 'mixed':  # smooth, with a band of two fine tile rows (rows 8 .. 23) carrying 9 px noise
+        f = smooth(1.5 * torch.randn(B, 2, h, w, generator=gen))
+        f[:, :, 4:12] += 9.0 / 2 * torch.randn(B, 2, 8, w, generator=gen)
+        return f
+    if kind == 'noise':
+        return 60.0 / 2 * torch.randn(B, 2, h, w, generator=gen)
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing='ij')
+    if kind == 'converging':  # every fine pixel moves 90 % of the way to the centre: ~100 sources per cell
+        cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+        return torch.stack([(cx - 2 * xs) * 0.45, (cy - 2 * ys) * 0.45])[None].repeat(B, 1, 1, 1)
+    if kind == 'leaving':  # +500 px both ways
+        return torch.full((B, 2, h, w), 250.0)
+    if kind == 'half_leaving':  # the left third flows ~200 px past the left border, the rest is smooth
+        f = smooth(1.5 * torch.randn(B, 2, h, w, generator=gen))
+        f[:, 0, :, :w // 3] = -100.3
+        return f
+    raise ValueError(kind)
+
+
+def contributions(O, flow, Hs, Ws, pad, align):
+    """Largest number of output pixels whose bilinear taps land on one source cell (the terms an atomic d x2 sums)."""
+    ix, iy, _, _ = sample_coords(O, flow, Hs, Ws, align)
+    if pad == 'border':
+        ix, iy = ix.clamp(0, Ws - 1), iy.clamp(0, Hs - 1)
+    inside = (ix > -1) & (ix < Ws) & (iy > -1) & (iy < Hs)
+    x0, y0 = ix.floor().clamp(0, Ws - 1).long(), iy.floor().clamp(0, Hs - 1).long()
+    cell = (torch.arange(ix.shape[0]).view(-1, 1, 1) * Hs + y0) * Ws + x0
+    return int(torch.bincount(cell[inside].flatten(), minlength=1).max()) if bool(inside.any()) else 0
+
+
+ADV_SHAPE = (2, 8, 48, 80)  # 3 x 6 tiles x 2, channel split 2: both roles in one launch, + up2_bwd
+
+
+def _adversarial_case(AF, O, shape, kind, pad, align):
+    B, C, H, W = shape[:4]
+    gen = torch.Generator().manual_seed(B + H + len(kind) + 3 * align + (5 if pad == 'border' else 0))
+    flow_c = adversarial_flow(kind, B, H, W, gen)
+    _, x1, x2, _, member = smooth_inputs(shape, H + W + len(kind), flow_c)
+    tag = '%s %s %s %s' % (shape_id(shape), kind, pad, align)
+    fine = F.interpolate(flow_c * 2, scale_factor=2, mode='bilinear', align_corners=align)
+    k = contributions(O, fine, H, W, pad, align)
+    # d x2 is a float-atomic sum over the k output pixels that sample one source cell, each term carrying its own rounding:
+    # its error grows with k where the sums are long (converging fields, every sample clamped onto the last row and column
+    # under `border`).  The bound of the smooth fields holds up to 16 terms and grows as sqrt(k / 16) above that.
+    grow = max(1.0, (k / 16.0) ** 0.5)
+    run_level_case(AF, O, x1, x2, flow_c, member, pad, align, align, tag + ' k=%d' % k, dx2_grow=grow)
+
+
+ADV_KINDS = ['mixed', 'noise', 'converging', 'leaving', 'half_leaving']
+
+
+@pytest.mark.parametrize('align', [True, False], ids=['align1', 'align0'])
+@pytest.mark.parametrize('pad', ['zeros', 'border'])
+@pytest.mark.parametrize('kind', ADV_KINDS)
+def test_level_adversarial_flows(AF, O, kind, pad, align):
+    """Rough, converging and leaving coarse flows through the fused level (the normalisation folded into the same kernels):
+    the scatter's LDS-window overflow to direct atomics, oversize gather boxes, sources with many contributors, all
+    samples out of the image (`zeros`: x2w = 0) or clamped onto the last row and column (`border`)."""
+    check_branch(ADV_SHAPE, 'tiled', 'both')
+    _adversarial_case(AF, O, ADV_SHAPE, kind, pad, align)
+
+
+@pytest.mark.parametrize('pad,align', [('border', False), ('zeros', True)], ids=lambda v: str(v))
+@pytest.mark.parametrize('kind', ['mixed', 'converging'])
+def test_level_adversarial_flows_split_form(AF, O, kind, pad, align):
+    """The mixed and the converging field at the shape that takes the split backward (slab / gather when opted in)."""
+    check_branch(SPLIT, 'tiled4', 'split')
+    _adversarial_case(AF, O, SPLIT, kind, pad, align)
+
+
+@pytest.mark.parametrize('align', [True, False], ids=['align1', 'align0'])
+@pytest.mark.parametrize('pad', ['zeros', 'border'])
+@pytest.mark.parametrize('shape', [(2, 32, 12, 16), (2, 8, 48, 80)], ids=shape_id)
+def test_level_full_resolution_integer_flow(AF, O, shape, pad, align):
+    """flow_is_coarse=False (level_warp_fwd_kernel<false>, and the per-sample kernel at 12 x 16) with INTEGER flows whose
+    targets include 0 and size-1 exactly: the flow reaches the kernel unmodified, so kernel and oracle coordinates are
+    bit-equal and d/dflow is compared everywhere -- at the tap cell boundaries and on the clamp points of `border`."""
+    B, C, H, W = shape
+    check_branch(shape, 'small' if H == 12 else 'tiled', 'both', coarse=False)
+    gen = torch.Generator().manual_seed(H + W + 3 * align + (5 if pad == 'border' else 0))
+    tx = torch.randint(-2, W + 2, (B, H, W), generator=gen)
+    ty = torch.randint(-2, H + 2, (B, H, W), generator=gen)
+    # a quarter of the pixels exactly on the first / last row and column
+    pick = torch.randint(0, 8, (B, H, W), generator=gen)
+    tx = torch.where(pick == 0, torch.zeros_like(tx), torch.where(pick == 1, torch.full_like(tx, W - 1), tx))
+    ty = torch.where(pick == 2, torch.zeros_like(ty), torch.where(pick == 3, torch.full_like(ty, H - 1), ty))
+    ys, xs = torch.meshgrid(torch.arange(H), torch.arange(W), indexing='ij')
+    flow = torch.stack([tx - xs, ty - ys], 1).float()
+    _, x1, x2, _, member = smooth_inputs(shape, H + W + 1, flow)
+    run_level_case(AF, O, x1, x2, flow, member, pad, align, align, '%s integer %s %s' % (shape_id(shape), pad, align),
+                   coarse=False, mask_ties=False)
+
+
+def test_level_uflow_layout_split_form(AF, O):
+    """The PWCFlow layout (NORM_UFLOW coordinates, 'avg' statistics, upsample with align_corners=False) at the shape that
+    takes the split backward."""
+    check_branch(SPLIT, 'tiled4', 'split')
+    _uflow_layout_case(AF, O, SPLIT, mask_ties=True)
+
+
+def _act_with_rows(AF, B, C, H, W, gen):
+    """A feature map as the extractor produces it (bias + LeakyReLU epilogue) and the partial moments that epilogue leaves."""
+    raw = smooth(torch.randn(B, C, H, W, generator=gen)) + 0.2
+    bias = 0.1 * torch.randn(C, generator=gen)
+    with torch.no_grad():
+        y, rows = AF.bias_leaky_relu_moments(raw.cuda().contiguous(), bias.cuda(), 0.1)
+    return y, rows
+
+
+@pytest.mark.parametrize('shape,has_flow', [((2, 32, 12, 16), True), ((4, 32, 24, 40), True), ((4, 32, 12, 20), False),
+                                            ((4, 32, 14, 32), False)],
+                         ids=['flow-small', 'flow-tiled', 'noflow-small', 'noflow-tiled'])
+def test_level_moment_rows(AF, O, shape, has_flow):
+    """x1_rows (and, at the level without a flow, x2_rows) from bias_leaky_relu_moments -- the moments taken in the conv
+    epilogue -- give the same level as the call without rows, and as the oracle, forward and every gradient."""
+    B, C, H, W = shape
+    check_branch(shape, 'small' if H * W <= 256 else 'tiled', 'both')
+    gen = torch.Generator().manual_seed(H * W + has_flow)
+    y1, r1 = _act_with_rows(AF, B, C, H, W, gen)
+    y2, r2 = _act_with_rows(AF, B, C, H, W, gen)
+    flow_c = smooth(1.5 * torch.randn(B, 2, H // 2, W // 2, generator=gen)) if has_flow else None
+    member = torch.randn(B, 5, H, W, generator=gen)
+    x1, x2 = y1.detach().cpu().requires_grad_(True), y2.detach().cpu().requires_grad_(True)
+    m = member.clone().requires_grad_(True)
+    fc = flow_c.clone().requires_grad_(True) if has_flow else None
+    ref_buf, ref_flow, pre, _ = oracle_level(O, x1, x2, fc, 'joint', True, 'zeros', m, align=True)
+    gbuf = torch.randn(ref_buf.shape, generator=gen)
+    gbuf[:, :81] *= (pre.detach().abs() > 1e-6).float()
+    gflow = torch.randn(B, 2, H, W, generator=gen) if has_flow else None
+    inputs = [x1, x2, m] + ([fc] if has_flow else [])
+    refs = torch.autograd.grad((ref_buf * gbuf).sum() + ((ref_flow * gflow).sum() if has_flow else 0.0), inputs)
+    names = ['d x1', 'd x2', 'd member'] + (['d flow_c'] if has_flow else [])
+
+    def run(rows):
+        a, b, mm = [t.detach().cuda().requires_grad_(True) for t in (x1, x2, member)]
+        f = flow_c.cuda().requires_grad_(True) if has_flow else None
+        if has_flow:
+            cfg = AF.LevelCfg(['vol', 'x1n', 'flow', 0], 'joint', 0.1, 4, True, True, 'zeros', True)
+            buf, fu = AF.level(a, b, f, cfg, mm, x1_rows=r1 if rows else None)
+        else:
+            cfg = AF.LevelCfg(['vol', 'x1n', 0], 'joint', 0.1, 4)
+            buf, fu = AF.level(a, b, None, cfg, mm, x1_rows=r1 if rows else None, x2_rows=r2 if rows else None), None
+        gin = [a, b, mm] + ([f] if has_flow else [])
+        loss = (buf * gbuf.cuda()).sum() + ((fu * gflow.cuda()).sum() if has_flow else 0.0)
+        return buf.detach(), torch.autograd.grad(loss, gin)
+
+    buf_r, got_r = run(True)
+    buf_n, got_n = run(False)
+    xmax = float(x2.detach().abs().max())
+    vol_tol = 2e-6 + (2e-5 * xmax if has_flow else 0.0)
+    for tag, buf in (('rows', buf_r), ('no rows', buf_n)):
+        assert_close(buf[:, 81:81 + C], ref_buf[:, 81:81 + C], 1e-6, 5e-6, 'x1n ' + tag)
+        assert_close(buf[:, :81], ref_buf[:, :81], vol_tol, 1e-5, 'volume ' + tag)
+    assert_close(buf_r[:, 81:81 + C], buf_n[:, 81:81 + C], 1e-6, 5e-6, 'x1n rows vs no rows')
+    assert_close(buf_r[:, :81], buf_n[:, :81], 2e-6, 1e-5, 'volume rows vs no rows')
+    if has_flow:
+        assert_close(buf_r[:, 81 + C:], buf_n[:, 81 + C:], 0, 0, 'flow slot and member, rows vs no rows')
+    for n, gr, gn, r in zip(names, got_r, got_n, refs):
+        tol = 0 if n == 'd member' else 2e-5 * float(r.abs().max()) + 1e-6
+        rtol = 0 if n == 'd member' else 1e-4
+        assert_close(gr, r, tol, rtol, n + ' rows')
+        assert_close(gn, r, tol, rtol, n + ' no rows')
+        assert_close(gr, gn, tol, rtol, n + ' rows vs no rows')
+
+
+def test_level_moment_rows_are_validated(AF):
+    """Wrong x1_rows / x2_rows raise ValueError.  Each wrong input would still be read in bounds if the check were missing
+    (rows of float32 over a buffer of the right byte size, a larger batch)."""
+    B, C, H, W = 2, 32, 12, 20
+    gen = torch.Generator().manual_seed(3)
+    y1, r1 = _act_with_rows(AF, B, C, H, W, gen)
+    y2, r2 = _act_with_rows(AF, B, C, H, W, gen)
+    member = torch.zeros(B, 1, H, W, device='cuda')
+    cfg = AF.LevelCfg(['vol', 'x1n', 0], 'joint', 0.1, 4)
+    AF.level(y1, y2, None, cfg, member, x1_rows=r1, x2_rows=r2)  # the right rows pass
+    f32 = r2.view(torch.float32).view(-1)[:r2.numel()].view(r2.shape)  # float32 [B, rows, 2] over r2's bytes
+    big = torch.cat([r2, r2[:1]], 0)                                 # [B + 1, rows, 2]
+    for bad in (f32, big):
+        with pytest.raises(ValueError, match='x2_rows'):
+            AF.level(y1, y2, None, cfg, member, x1_rows=r1, x2_rows=bad)
+    with pytest.raises(ValueError, match='x1_rows'):
+        AF.level(y1, y2, None, cfg, member, x1_rows=r1.view(torch.float32).view(-1)[:r1.numel()].view(r1.shape))
+    with pytest.raises(ValueError, match='x1_rows'):
+        AF.level(y1, y2, None, cfg, member, x1_rows=torch.cat([r1, r1[:1]], 0))
+
+
+def test_level_small_path_rejects_bad_arguments():
+    """arflow_level_fwd_m at a shape the per-sample kernel takes: the pad mode, the coordinate normalisation and the flow
+    batch stride are checked before the dispatch, as on the tiled path.  Each bad value would read in bounds."""
+    from arflow_amd import _lib
+    lib = _lib.load()
+    B, C, H, W = 2, 32, 12, 16
+    assert level_branch(B, C, H, W, env={})[0] == 'small'
+    gen = torch.Generator().manual_seed(11)
+    x1, x2 = torch.randn(B, C, H, W, generator=gen).cuda(), torch.randn(B, C, H, W, generator=gen).cuda()
+    flow = torch.randn(B, 2, H // 2, W // 2, generator=gen).cuda()
+    out = torch.zeros(B, 81 + C, H, W, device='cuda')
+    fup, x2w = torch.zeros(B, 2, H, W, device='cuda'), torch.zeros_like(x1)
+    sign = torch.zeros(B, 3, H, W, device='cuda', dtype=torch.int32)
+    stats = torch.zeros(B, 4, device='cuda')
+    acc = torch.zeros(4 * B * lib.arflow_level_acc_rows(B, C, H, W, 1), device='cuda', dtype=torch.float64)
+    st = torch.cuda.current_stream().cuda_stream
+    bs = (81 + C) * H * W
+
+    def call(pad=0, norm=0, fbs=2 * (H // 2) * (W // 2)):
+        return lib.arflow_level_fwd_m(x1.data_ptr(), x2.data_ptr(), flow.data_ptr(), fbs, 1, 1, fup.data_ptr(), None, 0,
+                                      x2w.data_ptr(), 0, out.data_ptr(), bs, out[:, 81:].data_ptr(), bs, sign.data_ptr(),
+                                      stats.data_ptr(), acc.data_ptr(), None, 0, None, 0, B, C, H, W, 4, 0.1, pad, 1, norm,
+                                      st)
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert call(pad=2) == -1003  # ARFLOW_EPARAM
+    assert call(norm=2) == -1003  # ARFLOW_NORM_UFLOW_ABS: not a level mode
+    assert call(fbs=0) == -1002  # ARFLOW_ESHAPE
+    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize('env', [{'ARFLOW_WARP_SLAB': '1'}, {'ARFLOW_LEVEL_SMALL': '0'}, {'ARFLOW_WARP_GATHER': '1'}],
@@ -204,9 +620,22 @@ def test_opt_in_kernel_variants_in_a_fresh_process(env):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    name = next(iter(env))
+    # the new cases at the shapes where the variant engages (asserted here with the dispatch mirror): A's pad / align
+    # cases at 960 tiles and at the split shape, B's mixed and converging fields at the split shape; A's cases at the
+    # small shapes
+    fine = '(16x32x96x160 or %s)' % shape_id(SPLIT)
+    new = {'ARFLOW_WARP_SLAB': fine, 'ARFLOW_WARP_GATHER': fine, 'ARFLOW_LEVEL_SMALL': '(1x32x10x12 or 2x32x12x16)'}[name]
+    want = {'ARFLOW_WARP_SLAB': ('bwd', 'slab'), 'ARFLOW_WARP_GATHER': ('bwd', 'gather'),
+            'ARFLOW_LEVEL_SMALL': ('fwd', 'tiled')}[name]
+    for shape in ([(16, 32, 96, 160), SPLIT] if name != 'ARFLOW_LEVEL_SMALL' else [(1, 32, 10, 12), (2, 32, 12, 16)]):
+        got = dict(zip(('fwd', 'bwd'), level_branch(*shape, env=env)))
+        assert got[want[0]] == want[1], '%s does not engage %s at %s' % (name, want[1], shape_id(shape))
     sel = {'ARFLOW_WARP_SLAB': '16x32x96x160 and joint', 'ARFLOW_LEVEL_SMALL': '16x32x12x20',
-           'ARFLOW_WARP_GATHER': '(16x32x96x160 or 8x32x112x256)'}[next(iter(env))]
+           'ARFLOW_WARP_GATHER': '(16x32x96x160 or 8x32x112x256)'}[name]
     cmd = [sys.executable, '-m', 'pytest', os.path.join(root, 'tests', 'test_level_gpu.py'), '-q', '-x', '-m', 'gpu', '-k',
-           'test_level_forward_backward_vs_oracle and ' + sel]
+           '(test_level_forward_backward_vs_oracle and %s) or (test_level_pad_align and %s)' % (sel, new)
+           + ('' if name == 'ARFLOW_LEVEL_SMALL' else
+              ' or test_level_adversarial_flows_split_form')]
     r = subprocess.run(cmd, cwd=root, env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and ' passed' in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])

@@ -16,6 +16,22 @@ pytestmark = pytest.mark.gpu
 # parameter, on an objective without thresholds); op-level gradients are pinned tightly in test_hip_parity.py.
 TOL = 2e-2
 
+# Models that are not in the golden file (tests/helpers.py::model_cases mirrors oracle/make_golden.py::gen_models), checked
+# against their CPU oracle twin instead: PWCLiteUflow with feature_norm on (the fused level) AND `border` padding with
+# align_corners=False, which the fused level then takes from its config.
+EXTRA_CASES = {
+    'pwclite_uflow_border': ('PWCLiteUflow', dict(level_dropout=0.0, feature_norm=True, warp_pad='border', align_corners=False,
+                                                  n_frames=2, reduce_dense=False)),
+}
+
+
+def _case(tag):
+    from arflow_amd.config import AttrDict
+    if tag in EXTRA_CASES:
+        return EXTRA_CASES[tag][0], AttrDict(EXTRA_CASES[tag][1])
+    case = [c for c in model_cases() if c[0] == tag][0]
+    return case[1], case[2]
+
 
 def _loss_for(tag):
     from arflow_amd import losses as L
@@ -159,7 +175,8 @@ def _worst_rel(ga, gb, names):
 
 
 @pytest.mark.parametrize('tag,linear', [('pwclite2', True), ('pwclite2', False), ('pwclite_uflow_0', False),
-                                        ('pwclite_uflow_1', False), ('pwcflow', False), ('pwcflow', True)])
+                                        ('pwclite_uflow_1', False), ('pwcflow', False), ('pwcflow', True),
+                                        ('pwclite_uflow_border', False)])
 # (ADVICE r2 asked for a fixed-tolerance `linear` variant per architecture.  PWCFlow has one (1e-3, like pwclite2).  For
 #  PWCLiteUflow it cannot be held: with the conv activations removed some bias gradients nearly cancel (max|g| 2e-5 against
 #  3e-2 elsewhere) and the ORACLE twin on the GPU differs from the oracle twin on the CPU by 0.74 of that maximum -- more
@@ -182,8 +199,7 @@ def test_model_parameter_gradients_elementwise(tag, linear):
         parameter upstream of it and fails either bound (and the op-level tests at the bench shapes,
         tests/test_bench_shapes_gpu.py, pin each kernel's gradient to 1e-5 .. 1e-4 on their own)."""
     from oracle.fixture_common import synth_pair
-    case = [c for c in model_cases() if c[0] == tag][0]
-    _, cls, cfg, frames, _ = case
+    cls, cfg = _case(tag)
     x = synth_pair(2, 192, 256, torch.Generator().manual_seed(5))[0]
     torch.set_num_threads(16)
     l_hip, g_hip, names = _param_grads(cls, cfg, x, 'cuda', True, linear)
@@ -221,3 +237,42 @@ def test_pwclite_five_frames_on_hip_ops(golden):
             for i, f in enumerate(flows):
                 e = epe(pool_to_quarter(f, x.shape[2]), g['pwclite5_%s_%d_%d' % (k, w, i)])
                 assert e <= 1e-3, '5-frame %s window %d level %d: EPE %.3e px' % (k, w, i, e)
+
+
+def test_pwclite_uflow_border_align0_vs_oracle_twin():
+    """PWCLiteUflow(feature_norm=True, warp_pad='border', align_corners=False) -- the fused level with `border` and
+    align_corners=False at every level, the per-sample kernel at 12 x 16 with a flow -- against the same host model with
+    the oracle ops patched in, on the CPU: flow EPE <= 1e-3 px at every output level of both directions."""
+    import arflow_amd.functional as AF
+    import arflow_amd.models as M
+    from oracle.fixture_common import synth_pair
+    from oracle.host_models import oracle_ops
+    cls, cfg = _case('pwclite_uflow_border')
+    x = synth_pair(2, 192, 256, torch.Generator().manual_seed(7))[0]
+    torch.set_num_threads(16)
+    calls = []
+    fused = AF.level
+
+    def spy(x1, x2, flow, c, *members, **kw):
+        calls.append((tuple(x1.shape), flow is not None, c.pad, c.align, c.up_align))
+        return fused(x1, x2, flow, c, *members, **kw)
+    AF.level = spy
+    try:
+        with torch.no_grad():
+            hip = fill_deterministic(getattr(M, cls)(cfg)).cuda().eval()(x.cuda(), with_bk=True)
+    finally:
+        AF.level = fused
+    # every level fused, each with a flow taking `border` / align_corners=False (PAD['border'] == 1)
+    assert sorted({c[0][2:] for c in calls}) == [(6, 8), (12, 16), (24, 32), (48, 64)], calls
+    assert all(c[2:] == (1, 0, False) for c in calls if c[1]) and sum(c[1] for c in calls) == 3, calls
+    from tests.test_level_gpu import level_branch
+    assert [level_branch(*c[0])[0] for c in calls if c[1] and c[0][2:] == (12, 16)] == ['small'], calls
+    ref_model = fill_deterministic(getattr(M, cls)(cfg)).eval()
+    with torch.no_grad(), oracle_ops(ref_model):
+        ref = ref_model(x, with_bk=True)
+    for k in ('flows_fw', 'flows_bw'):
+        assert len(hip[k]) == len(ref[k])
+        for i, (a, b) in enumerate(zip(hip[k], ref[k])):
+            e = epe(a, b)
+            assert e <= 1e-3, 'border / align_corners=False %s level %d (%s): EPE %.3e px vs the oracle twin' % (
+                k, i, tuple(b.shape[2:]), e)
