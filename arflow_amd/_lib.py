@@ -57,6 +57,10 @@ PROTOTYPES = {
     'arflow_level_corr_bwd': [c_fp, c_l, c_fp, c_fp, c_l, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_fp],
     'arflow_bias_act_fwd': [c_fp, c_fp, c_fp, c_i, c_i, c_l, c_f, c_fp],
     'arflow_bias_act_bwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_l, c_f, c_fp],
+    'arflow_headconv_fwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_headconv_bwd_data': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_headconv_bwd_weight_ws_bytes': [c_i, c_i, c_i, c_i],
+    'arflow_headconv_bwd_weight': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
     'arflow_warp_fwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_i, c_i, c_i, c_fp],
     'arflow_warp_bwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_i, c_i, c_i, c_fp],
     'arflow_splat_map': [c_fp, c_fp, c_i, c_i, c_i, c_l, c_i, c_fp],
@@ -106,7 +110,7 @@ def load():
     for name, argtypes in PROTOTYPES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
-        fn.restype = c_l if name == 'arflow_level_bwd_ws_bytes' else c_i
+        fn.restype = c_l if name.endswith('_ws_bytes') else c_i
     lib.arflow_strerror.argtypes = [c_i]
     lib.arflow_strerror.restype = ctypes.c_char_p
     if lib.arflow_abi_version() != ABI_VERSION:

@@ -581,6 +581,62 @@ def bias_leaky_relu(x, bias, slope=0.1):
     return BiasLeakyReLUFunction.apply(x, bias, slope)
 
 
+_HEADCONV = __import__('os').environ.get('ARFLOW_HEADCONV', '1') != '0'  # A/B switch for tools/ and tests: 0 = MIOpen
+
+
+class HeadConvFunction(torch.autograd.Function):
+    """y = conv2d(x, w, bias) for w: [2, C, 3, 3], stride 1, padding 1 -- the flow heads built by conv(..., isReLU=False)
+    (models/pwclite.py:10-23, :48-106) -- through the direct kernels of csrc/headconv.hip: one pass over x forward, one
+    store stream for dx, one pass over x for dw and dbias; every result is bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _need_gpu(x, weight, bias)
+        if x.dim() != 4 or tuple(weight.shape) != (2, x.shape[1], 3, 3):
+            raise ValueError('head_conv expects x [B,C,H,W] and weight [2,C,3,3]')
+        x, weight = x.contiguous(), weight.contiguous()
+        if bias is not None:
+            bias = bias.contiguous()
+        B, C, H, W = x.shape
+        y = torch.empty(B, 2, H, W, device=x.device, dtype=torch.float32)
+        with torch.cuda.device_of(x):
+            _call('arflow_headconv_fwd', _p(x), _p(weight), _p(bias), _p(y), B, C, H, W, _stream())
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        B, C, H, W = x.shape
+        dy = dy.contiguous()
+        dx = dw = db = None
+        with torch.cuda.device_of(x):
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty_like(x)
+                _call('arflow_headconv_bwd_data', _p(dy), _p(weight), _p(dx), B, C, H, W, _stream())
+            want_b = ctx.has_bias and ctx.needs_input_grad[2]
+            if ctx.needs_input_grad[1] or want_b:
+                nbytes = _lib.load().arflow_headconv_bwd_weight_ws_bytes(B, C, H, W)
+                if nbytes < 0:
+                    _lib.check(int(nbytes), 'arflow_headconv_bwd_weight_ws_bytes')
+                ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+                dw = torch.empty_like(weight)
+                db = torch.empty(2, device=x.device, dtype=torch.float32) if want_b else None
+                _call('arflow_headconv_bwd_weight', _p(x), _p(dy), _p(dw), _p(db), _p(ws), B, C, H, W, _stream())
+                if not ctx.needs_input_grad[1]:
+                    dw = None
+        return dx, dw, db
+
+
+def head_conv(x, weight, bias):
+    return HeadConvFunction.apply(x, weight, bias)
+
+
+def head_conv_enabled():
+    return _HEADCONV
+
+
 class BiasLeakyReLUMomentsFunction(torch.autograd.Function):
     """bias_leaky_relu that also returns the partial moments (sum y, sum y^2) of its output as rows of 2 doubles
     ([B, rows, 2], arflow_bias_act_fwd_mom): normalize_features' moments taken where the feature map is produced."""

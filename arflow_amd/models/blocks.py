@@ -28,6 +28,26 @@ class ConvAct(nn.Sequential):
         return bias_act(y, c.bias, act.negative_slope)
 
 
+class HeadConv(nn.Sequential):
+    """Sequential(Conv2d(bias=True)) with the reference's parameter names (``0.weight``, ``0.bias``): the layers conv()
+    builds with isReLU=False, i.e. the two-channel flow heads.  A CUDA fp32 input of a 3x3 / stride 1 / padding 1 /
+    dilation 1 / two-output layer goes through the direct kernels (AF.head_conv); any other layer, every CPU tensor and
+    a twin that has swapped `bias_act` out keep F.conv2d."""
+
+    def native(self, x):
+        c = self[0]
+        return (AF.head_conv_enabled() and bias_act is AF.bias_leaky_relu and x.is_cuda and x.dtype == torch.float32 and
+                x.dim() == 4 and c.weight.dtype == torch.float32 and c.out_channels == 2 and c.kernel_size == (3, 3) and
+                c.stride == (1, 1) and c.padding == (1, 1) and c.dilation == (1, 1) and c.groups == 1 and
+                c.padding_mode == 'zeros')
+
+    def forward(self, x):
+        c = self[0]
+        if self.native(x):
+            return AF.head_conv(x, c.weight, c.bias)
+        return F.conv2d(x, c.weight, c.bias, c.stride, c.padding, c.dilation, c.groups)
+
+
 def conv(in_planes, out_planes, kernel_size=3, stride=1, dilation=1, isReLU=True):
     """models/pwclite.py:10-23 -- Sequential(Conv2d[, LeakyReLU(0.1)]) -> keys ``<name>.0.weight``."""
     layers = [nn.Conv2d(in_planes, out_planes, kernel_size=kernel_size, stride=stride, dilation=dilation,
@@ -35,7 +55,7 @@ def conv(in_planes, out_planes, kernel_size=3, stride=1, dilation=1, isReLU=True
     if isReLU:
         layers.append(nn.LeakyReLU(0.1, inplace=True))
         return ConvAct(*layers)
-    return nn.Sequential(*layers)
+    return HeadConv(*layers)
 
 
 def deconv(in_planes, out_planes, kernel_size=4, stride=2, padding=1):

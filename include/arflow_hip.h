@@ -217,6 +217,24 @@ int arflow_bias_act_fwd_mom(const float* x, const float* bias, float* y, double*
 int arflow_bias_act_bwd(const float* gout, const float* y, float* gin, float* gbias, int B, int C, long HW,
                         float negative_slope, arflow_stream_t stream);
 
+/* ---- two-channel 3x3 head convolution ----------------------------------------------------------
+ * y = conv2d(x, w, bias) for w: [2, C, 3, 3], stride 1, padding 1, dilation 1, groups 1 -- the flow heads of the
+ * reference models (conv_last / predict_flow / the last ContextNetwork conv, models/pwclite.py:48-106, built by
+ * conv(..., isReLU=False), models/pwclite.py:10-23), which the vendor library pads into 32-wide tiles.  One pass over
+ * x per call, bias folded in; x: [B,C,H,W], y / dy: [B,2,H,W], any B, C, H, W >= 1 (float4 paths when W % 4 == 0 and
+ * the pointers are 16-byte aligned).  No atomics anywhere: every result is bitwise reproducible.  All sums are
+ * accumulated in double and rounded to fp32 once: the correctly rounded result up to double rounding.
+ * bias and dbias are nullable.  The weight gradient leaves per-wave partial sums in `ws`
+ * (arflow_headconv_bwd_weight_ws_bytes() bytes, 16-byte aligned, need not be initialised; < 0 = ARFLOW_ESHAPE) and
+ * adds them in a second kernel; dbias[o] = sum dy[:, o] comes out of the same pass. */
+int arflow_headconv_fwd(const float* x, const float* w, const float* bias, float* y, int B, int C, int H, int W,
+                        arflow_stream_t stream);
+int arflow_headconv_bwd_data(const float* dy, const float* w, float* dx, int B, int C, int H, int W,
+                             arflow_stream_t stream);
+long arflow_headconv_bwd_weight_ws_bytes(int B, int C, int H, int W);
+int arflow_headconv_bwd_weight(const float* x, const float* dy, float* dw, float* dbias, void* ws, int B, int C, int H,
+                               int W, arflow_stream_t stream);
+
 /* ---- bilinear warp ----------------------------------------------------------------------------
  * out[b,c,y,x] = bilinear(src[b,c], x + flow[b,0,y,x], y + flow[b,1,y,x]) with torch grid_sample
  * semantics (pad zeros|border, align_corners) after the reference's normalise/un-normalise round

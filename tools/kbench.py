@@ -147,6 +147,24 @@ def main():
             rec('arflow_level_fwd', (B2, C, h, w, 4, 3, fk), timeit(lfwd, args.iters))
             rec('arflow_level_fwd_m', (B2, C, h, w, 4, 3, fk, 1), timeit(lfwd_m, args.iters))
             rec('arflow_level_bwd', (B2, C, h, w, 4, 3, fk), timeit(lbwd, args.iters))
+    if want('headconv'):  # the two-channel flow heads of the flagship (csrc/headconv.hip); tools/headconv_miopen.py times MIOpen's
+        for C, h, w in ((595, H0 // 4, W0 // 4), (595, H0 // 8, W0 // 8), (595, H0 // 16, W0 // 16), (563, H0 // 32, W0 // 32),
+                        (32, H0 // 4, W0 // 4)):
+            x = torch.randn(B2, C, h, w, device=dev, generator=g)
+            wt = 0.05 * torch.randn(2, C, 3, 3, device=dev, generator=g)
+            bias = torch.randn(2, device=dev, generator=g)
+            y, dy = torch.empty(B2, 2, h, w, device=dev), torch.randn(B2, 2, h, w, device=dev, generator=g)
+            dx, dw, db = torch.empty_like(x), torch.empty_like(wt), torch.empty_like(bias)
+            ws = torch.empty(lib.arflow_headconv_bwd_weight_ws_bytes(B2, C, h, w), device=dev, dtype=torch.uint8)
+            wide = 4 * B2 * h * w * (C + 2)  # the wide tensor once plus the two-channel side; weights are noise
+
+            def hrec(name, us):
+                MANIFEST[-1].update(name=name, shape=[B2, C, h, w], us=us)
+                print('%-22s %-26s %9.1f us %9.1f GB/s  %5.1f%% of HBM peak' % (name, [B2, C, h, w], us, wide / us / 1e3, 100 * wide / us / 1e3 / HBM_PEAK_GBS), flush=True)
+            hrec('arflow_headconv_fwd', timeit(lambda: lib.arflow_headconv_fwd(p(x), p(wt), p(bias), p(y), B2, C, h, w, s), args.iters))
+            hrec('arflow_headconv_bwd_data', timeit(lambda: lib.arflow_headconv_bwd_data(p(dy), p(wt), p(dx), B2, C, h, w, s), args.iters))
+            hrec('arflow_headconv_bwd_weight', timeit(lambda: lib.arflow_headconv_bwd_weight(p(x), p(dy), p(dw), p(db), p(ws), B2, C, h, w, s), args.iters))
+            del x, dx, ws
     # loss side: B = batch/2 image pairs at full resolution, per direction
     B = max(1, B2 // 2)
     im1 = torch.rand(B, 3, H0, W0, device=dev, generator=g)
@@ -227,6 +245,8 @@ def main():
         rec('arflow_up4_clamp_mul', (B, H0 // 4, W0 // 4), timeit(lambda: lib.arflow_up4_clamp_mul(p(sm), p(mask), p(dham), B, H0 // 4, W0 // 4, s), args.iters))
     if args.manifest:
         json.dump(MANIFEST, open(args.manifest, 'w'), indent=1)
+    if not rows:  # only ops that keep their own byte model (the head convolutions) were selected
+        return
     tot_us = sum(r[2] for r in rows)
     tot_b = sum(algorithmic_bytes(r[0], r[1]) for r in rows)
     print(json.dumps({'kernels': len(rows), 'sum_us': tot_us, 'sum_GB': tot_b / 1e9, 'aggregate_GBps': tot_b / tot_us / 1e3,
