@@ -79,6 +79,11 @@ PROTOTYPES = {
     'arflow_down4_gray': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'arflow_photo_fwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
     'arflow_photo_bwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_photo_warp_rows': [c_i, c_i, c_i],
+    'arflow_photo_warp_fwd': [c_fp, c_l, c_l, c_fp, c_l, c_l, c_fp, c_l, c_l, c_fp, c_l, c_l, c_i, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_photo_warp_bwd': [c_fp, c_l, c_l, c_fp, c_l, c_l, c_fp, c_l, c_l, c_fp, c_l, c_l, c_i, c_i, c_i, c_i, c_fp, c_fp, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_area_pyramid_ws_bytes': [c_i, c_i, c_i, c_fp, c_i],
+    'arflow_area_pyramid': [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_i, c_fp],
     'arflow_smooth_fwd': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_l, c_f, c_f, c_i, c_i, c_i, c_fp],
     'arflow_smooth_bwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_l, c_f, c_f, c_i, c_i, c_i, c_fp],
     'arflow_down4': [c_fp, c_fp, c_i, c_i, c_i, c_fp],

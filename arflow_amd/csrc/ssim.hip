@@ -4,6 +4,7 @@
 // costs more v_mov than it saves here: forward 28.4 -> 23.5 us, backward 53.3 -> 45.6 us at 8x3x384x640), the census
 // kernels with it (backward 59 -> 69 us without).
 #include "common.hpp"
+#include "ssim_dev.hpp"  // Win, div9, fdiv_pos, frcp_pos, photo4::read6 / read8 / stats6
 
 namespace {
 
@@ -12,34 +13,6 @@ constexpr int TX = 32, TY = 8;  // pixel tile = 256 threads, lanes run along x
 // ------------------------------------------------------------------------------------------------
 // SSIM (3x3, un-padded) + L1
 // ------------------------------------------------------------------------------------------------
-constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
-
-struct Win {
-  float mx, my, sx, sy, sxy;
-};
-
-// x / 9 exactly as IEEE division rounds it, in 3 VALU instructions instead of the ~12 of the generic
-// sequence: q = x*c; r = fma(-9, q, x); q = fma(r, c, q) with c = RN(1/9).  Bit-identical to x / 9.0f for
-// every finite float (all 2^32 patterns compared on the GPU, tools/ubench/div9_check.hip; only +-inf and one
-// value next to overflow differ).  The SSIM kernels are VALU-bound and did six divisions per window.
-__device__ __forceinline__ float div9(float x) {
-  const float c = 1.0f / 9.0f;
-  float q = x * c;
-  const float r = fmaf(-9.0f, q, x);
-  return fmaf(r, c, q);
-}
-// n / d and 1 / d for d > 0 (the SSIM denominators are >= C1*C2 > 0): hardware reciprocal + one Newton
-// step, within 1 ulp of the IEEE quotient (enters (1 - n/d)/2 with absolute error <= 6e-8).
-__device__ __forceinline__ float fdiv_pos(float n, float d) {
-  const float r = __builtin_amdgcn_rcpf(d);
-  const float q = n * r;
-  return fmaf(fmaf(-d, q, n), r, q);
-}
-__device__ __forceinline__ float frcp_pos(float d) {
-  const float r = __builtin_amdgcn_rcpf(d);
-  return fmaf(fmaf(-d, r, 1.0f), r, r);
-}
-
 template <int PITCH>
 __device__ __forceinline__ Win window_stats(const float (*tx)[PITCH], const float (*ty)[PITCH], int r, int c) {
   float sxv = 0.f, syv = 0.f, sxx = 0.f, syy = 0.f, sxyv = 0.f;
@@ -211,44 +184,6 @@ __global__ __launch_bounds__(TX* TY) void photo_bwd_kernel(const float* __restri
 // ------------------------------------------------------------------------------------------------
 namespace photo4 {
 constexpr int TXW = 64, TYH = 16, NT = 256, P = 128;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void read6(const float* row, float (&v)[6]) {
-  f32x4 t = *reinterpret_cast<const f32x4*>(row);
-  f32x2 u = *reinterpret_cast<const f32x2*>(row + 4);
-  asm volatile("" : "+v"(t), "+v"(u));
-  v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w, v[4] = u.x, v[5] = u.y;
-}
-__device__ __forceinline__ void read8(const float* row, float (&v)[8]) {
-  f32x4 t = *reinterpret_cast<const f32x4*>(row);
-  f32x4 u = *reinterpret_cast<const f32x4*>(row + 4);
-  asm volatile("" : "+v"(t), "+v"(u));
-  v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w, v[4] = u.x, v[5] = u.y, v[6] = u.z, v[7] = u.w;
-}
-// statistics of the 3x3 window whose left column is `e` of the 6-wide strips (same order as window_stats)
-__device__ __forceinline__ Win stats6(const float (&a)[3][6], const float (&b)[3][6], int e) {
-  float sxv = 0.f, syv = 0.f, sxx = 0.f, syy = 0.f, sxyv = 0.f;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float x = a[i][e + j], y = b[i][e + j];
-      sxv += x;
-      syv += y;
-      sxx += x * x;
-      syy += y * y;
-      sxyv += x * y;
-    }
-  Win w;
-  w.mx = div9(sxv);
-  w.my = div9(syv);
-  w.sx = div9(sxx) - w.mx * w.mx;
-  w.sy = div9(syy) - w.my * w.my;
-  w.sxy = div9(sxyv) - w.mx * w.my;
-  return w;
-}
-
 // masked tiles x = recons*mask, y = im*mask: `rows` x `nq` float4 starting at image (gy0, gx0) (gx0 % 4 == 0)
 template <int ROWS, int NQ, bool L1>
 __device__ __forceinline__ float stage(float* __restrict__ X, float* __restrict__ Y, const float* __restrict__ imc,

@@ -1391,3 +1391,159 @@ def up4_clamp_mul(small, valid=None):
     with torch.cuda.device_of(small):
         _call('arflow_up4_clamp_mul', _p(small), _p(valid), _p(out), B, h, w, _stream(), key=(B, h, w))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Fused warp + mask + L1/SSIM sums of one pyramid scale (csrc/photo_warp.hip)
+_PHOTO_WARP = __import__('os').environ.get('ARFLOW_PHOTO_WARP', '1') != '0'  # A/B switch for tools/ and tests: 0 = composed path
+MASK_MODE = {'plane': 0, 'nearest': 1, 'border': 2}
+
+
+def photo_warp_enabled():
+    return _PHOTO_WARP
+
+
+def _group_views(views, C, H, W, what):
+    """(base pointer, sample stride, second-group offset) in floats of G same-shaped [B,C,H,W] views whose planes are dense
+    -- slices of one tensor or separate tensors: the kernel reads them where they are."""
+    v0 = views[0]
+    for v in views:
+        if v.shape != v0.shape or v.stride() != v0.stride():
+            raise ValueError('%s: the groups must share shape and strides' % what)
+    B = v0.shape[0]
+    st = v0.stride()
+    if tuple(v0.shape[1:]) != (C, H, W) or st[3] != 1 or st[2] != W or (C > 1 and st[1] != H * W):
+        raise ValueError('%s: expected [B,%d,%d,%d] views with dense planes, got %s strides %s' % (what, C, H, W, tuple(v0.shape), st))
+    half = 0
+    if len(views) == 2:
+        d = views[1].data_ptr() - v0.data_ptr()
+        assert d % 4 == 0
+        half = d // 4
+    return v0.data_ptr(), (st[0] if B > 1 else C * H * W), half
+
+
+def photo_warp_supported(frames, flow, mask_size=None):
+    """Can the fused pass run this scale?  frames: the full-resolution [B,3k,H0,W0] tensor the images are area-resized
+    from; flow: this scale's flow; mask_size: (H, W) of a fine mask plane that is nearest-resized to this scale."""
+    h, w = flow.shape[-2:]
+    H0, W0 = frames.shape[-2:]
+    if h < 3 or w < 3 or H0 % h or W0 % w or H0 // h != W0 // w:
+        return False
+    if mask_size is not None and (mask_size[0] % h or mask_size[1] % w):
+        return False
+    return all(t.is_cuda and t.dtype == torch.float32 for t in (frames, flow))
+
+
+class PhotoWarpSumsFunction(torch.autograd.Function):
+    """[G,3] = per group [sum |tgt-rec|*m, sum SSIMdist(rec*m, tgt*m), sum m] with rec = flow_warp(src, flow, pad), in one
+    launch; the backward is one launch that writes d/d flow.  flow_a alone: a [B,2G,H,W] tensor holding the groups' flows
+    in its channels; flow_a and flow_b: two [B,2,H,W] tensors.  No gradient w.r.t. images or mask."""
+
+    @staticmethod
+    def forward(ctx, flow_a, flow_b, tgt, src, mask, pad, mask_mode, mask_invert, want_mask):
+        G = len(tgt)
+        _need_gpu(flow_a, flow_b, *tgt, *src, *(mask or ()))
+        B, C, H, W = tgt[0].shape
+        if flow_b is None:
+            if flow_a.shape != (B, 2 * G, H, W) or not flow_a.is_contiguous():
+                flow_a = flow_a.contiguous()
+            if flow_a.shape != (B, 2 * G, H, W):
+                raise ValueError('flow must be [B,%d,H,W] for %d groups' % (2 * G, G))
+            fl = (_p(flow_a), 2 * G * H * W, 2 * H * W)
+        else:
+            if G != 2:
+                raise ValueError('two flow tensors need two groups')
+            flow_a, flow_b = flow_a.contiguous(), flow_b.contiguous()
+            fl = _group_views((flow_a, flow_b), 2, H, W, 'flow')
+        tg = _group_views(tgt, C, H, W, 'target')
+        sr = _group_views(src, C, H, W, 'source')
+        mh, mw = H, W
+        if mask_mode == MASK_MODE['border']:
+            mk = (None, 0, 0)
+        else:
+            mh, mw = mask[0].shape[-2:]
+            if mask_mode == MASK_MODE['plane'] and (mh, mw) != (H, W):
+                raise ValueError('mask plane must have the size of the flow')
+            mk = _group_views(mask, 1, mh, mw, 'mask')
+        lib = _lib.load()
+        nrows = lib.arflow_photo_warp_rows(G * B, H, W)
+        if nrows <= 0:
+            _lib.check(nrows, 'arflow_photo_warp_rows')
+        rows = torch.empty(nrows, SUM_COLS, device=flow_a.device, dtype=torch.float32)
+        mout = torch.empty(G * B, 1, H, W, device=flow_a.device, dtype=torch.float32) if want_mask else None
+        ctx.common = (*tg, *sr, *fl, *mk, int(mask_mode), int(bool(mask_invert)), mh, mw)
+        ctx.dims = (B, G, C, H, W, int(pad))
+        with torch.cuda.device_of(flow_a):
+            _call('arflow_photo_warp_fwd', *ctx.common, _p(mout), _p(rows), *ctx.dims, _stream(), key=(G * B, C, H, W))
+        ctx.save_for_backward(flow_a, flow_b, *tgt, *src, *(mask or ()))  # (keeps the addressed storage alive)
+        sums = rows.view(G, nrows // G, SUM_COLS)[:, :, :3].sum(1)  # fixed order: reproducible
+        if want_mask:
+            ctx.mark_non_differentiable(mout)
+            return sums, mout
+        return sums
+
+    @staticmethod
+    def backward(ctx, gsums, *unused):
+        flow_a, flow_b = ctx.saved_tensors[:2]
+        B, G, C, H, W, pad = ctx.dims
+        coef = gsums[:, :2].contiguous()
+        ga = torch.empty_like(flow_a)
+        gb = None
+        if flow_b is None:
+            gf = (_p(ga), 2 * G * H * W, 2 * H * W)
+        else:
+            gb = torch.empty_like(flow_b)
+            gf = _group_views((ga, gb), 2, H, W, 'flow gradient')
+        with torch.cuda.device_of(flow_a):
+            _call('arflow_photo_warp_bwd', *ctx.common, _p(coef), *gf, *ctx.dims, _stream(), key=(G * B, C, H, W))
+        return ga, gb, None, None, None, None, None, None, None
+
+
+def photo_warp_sums(tgt, src, flow, mask=None, pad='zeros', mask_mode='plane', mask_invert=False, want_mask=False):
+    """Photometric sums of one pyramid scale without the warped image ever existing in memory.
+
+    tgt, src: tuples of G (1 or 2) [B,C,H,W] views (C <= 3) -- target / source image of every group, read in place (slices
+    of one tensor or separate tensors with equal strides).  flow: one [B,2G,H,W] tensor (group g = channels 2g:2g+2) or a
+    tuple of two [B,2,H,W] tensors.  mask: tuple of G [B,1,h,w] views for mask_mode 'plane' (h, w = H, W) and 'nearest'
+    (a fine plane, integer factors), ignored for 'border' (= border_mask(flow)); mask_invert uses 1 - mask.
+    Returns the [G,3] sums (and the [G*B,1,H,W] mask planes used when want_mask)."""
+    tgt, src = tuple(tgt), tuple(src)
+    if isinstance(flow, (tuple, list)):
+        fa, fb = flow if len(flow) == 2 else (flow[0], None)
+    else:
+        fa, fb = flow, None
+    mask = None if mask is None else tuple(mask)
+    if len(tgt) not in (1, 2) or len(src) != len(tgt) or (mask is not None and len(mask) != len(tgt)):
+        raise ValueError('photo_warp_sums: one or two groups, the same number of targets, sources and masks')
+    if mask is None and mask_mode != 'border':
+        raise ValueError("photo_warp_sums: mask_mode %r needs a mask" % mask_mode)
+    return PhotoWarpSumsFunction.apply(fa, fb, tgt, src, mask, PAD[pad], MASK_MODE[mask_mode], mask_invert, want_mask)
+
+
+def area_pyramid(frames, sizes):
+    """[F.interpolate(frames, s, mode='area') for s in sizes] in one launch (integer factors; every scale from the
+    full-resolution pixels).  A size equal to the frames' own returns `frames` itself."""
+    import ctypes
+    _need_gpu(frames)
+    frames = frames.contiguous()
+    B, C, H, W = frames.shape
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    n = len(sizes)
+    arr = (ctypes.c_int * (2 * n))(*[v for s in sizes for v in s])
+    host = ctypes.cast(arr, ctypes.c_void_p)
+    lib = _lib.load()
+    nbytes = lib.arflow_area_pyramid_ws_bytes(B * C, H, W, host, n)
+    if nbytes < 0:
+        _lib.check(nbytes, 'arflow_area_pyramid_ws_bytes')
+    buf = torch.empty(nbytes // 4, device=frames.device, dtype=torch.float32)
+    if nbytes:
+        with torch.cuda.device_of(frames):
+            _call('arflow_area_pyramid', _p(frames), _p(buf), B * C, H, W, host, n, _stream(), key=(B * C, H, W, n))
+    out, off = [], 0
+    for h, w in sizes:
+        if (h, w) == (H, W):
+            out.append(frames)
+        else:
+            out.append(buf[off:off + B * C * h * w].view(B, C, h, w))
+            off += B * C * h * w
+    return out

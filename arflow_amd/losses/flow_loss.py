@@ -44,22 +44,73 @@ class unFlowLoss(nn.Module):
 
     pair = True  # False: the two directions one after the other (the reference's order)
 
+    def _photo_from_sums(self, s, b, c, h, w):
+        """loss_photomatric on the three sums of one direction."""
+        cfg = self.cfg
+        total = 0.
+        if cfg.w_l1 > 0:
+            total = total + cfg.w_l1 * s[0] / float(b * c * h * w)
+        if cfg.w_ssim > 0:
+            total = total + cfg.w_ssim * s[1] / float(b * c * (h - 2) * (w - 2))
+        return total / (global_denominator(s[2]) / float(b * h * w))
+
+    def _occlusion_planes(self, flow):
+        """Finest scale, fused path: the occlusion plane of each direction as a [B,1,h,w] view (the mask is 1 - plane,
+        formed inside the fused pass).  flow: contiguous [B,4,h,w] = 2B two-channel flows interleaved, used in place."""
+        B, _, h, w = flow.shape
+        if self.cfg.occ_from_back:  # direction 1 is occluded where flow 2 -> 1 leaves holes, and vice versa
+            occ = get_occu_mask_backward(flow.view(2 * B, 2, h, w), th=0.2).view(B, 2, h, w)
+            return occ[:, 1:2], occ[:, 0:1]
+        return get_occu_mask_bidirection(flow[:, :2], flow[:, 2:]), get_occu_mask_bidirection(flow[:, 2:], flow[:, :2])
+
     def _forward_stacked(self, output, target):
         """with_bk as ONE pass over 2B samples (first B: direction 1 -> 2, last B: direction 2 -> 1; every op on this path is
-        per sample): one area resize, one warp, one occlusion / mask resize and one smoothness launch per pyramid scale instead
-        of two -- the photometric sums stay per direction (each is divided by its own mask mean, losses/flow_loss.py:27)."""
+        per sample).  Per pyramid scale the photometric sums of both directions come from one fused launch
+        (AF.photo_warp_sums: warp, mask and L1/SSIM; images, flows and occlusion planes are read where they are, the area
+        resizes of all scales come from one AF.area_pyramid launch) and the smoothness term is launched only where its weight
+        is non-zero.  A scale the fused pass does not cover (AF.photo_warp_supported), or ARFLOW_PHOTO_WARP=0, takes the
+        composed path: one area resize, one warp, one mask resize and one photometric launch per direction -- the
+        photometric sums stay per direction (each is divided by its own mask mean, losses/flow_loss.py:27)."""
         cfg = self.cfg
         B = target.shape[0]
-        imgs = torch.cat([target[:, :3], target[:, 3:]], 0)
+        target = target.contiguous()
+        size0 = output[0].shape[-2:]
+        fused = [AF.photo_warp_enabled() and cfg.w_scales[i] != 0 and AF.photo_warp_supported(target, flow, size0)
+                 for i, flow in enumerate(output)]
+        if any(fused) and cfg.w_ternary > 0:
+            self.loss_photomatric(None, None, None)  # raises: broken in the reference as well
+        sizes = [tuple(flow.shape[-2:]) for flow, u in zip(output, fused) if u]
+        pyramid = dict(zip(sizes, AF.area_pyramid(target, sizes))) if sizes else {}
+        imgs = None
         warp_losses, smooth_losses = [], []
         self.pyramid_occu_mask1, self.pyramid_occu_mask2 = [], []
-        s, m0 = 1., None
+        s, m0, planes, invert = 1., None, None, False
         for i, flow in enumerate(output):
             if cfg.w_scales[i] == 0:
                 warp_losses.append(0)
                 smooth_losses.append(0)
                 continue
             _, _, h, w = flow.shape
+            if i == 0:
+                s = min(h, w)
+            if fused[i]:
+                flow = flow.contiguous()
+                im = pyramid[(h, w)]  # [B,6,h,w]: image 1 and 2 of every pair
+                if i == 0:
+                    planes, invert = self._occlusion_planes(flow.detach()), True
+                sums, m = AF.photo_warp_sums((im[:, :3], im[:, 3:]), (im[:, 3:], im[:, :3]), flow, planes, pad=cfg.warp_pad,
+                                             mask_mode='plane' if i == 0 else 'nearest', mask_invert=invert, want_mask=True)
+                if i == 0:
+                    m0 = m
+                self.pyramid_occu_mask1.append(m[:B])
+                self.pyramid_occu_mask2.append(m[B:])
+                warp_losses.append((self._photo_from_sums(sums[0], B, 3, h, w) + self._photo_from_sums(sums[1], B, 3, h, w)) / 2.)
+                # 2B two-channel flows / 2B images, interleaved and in place; the mean over them IS the directions' average
+                smooth_losses.append(self.loss_smooth(flow.view(2 * B, 2, h, w), im.view(2 * B, 3, h, w), 1.0 / s)
+                                     if cfg.w_sm_scales[i] != 0 else 0)
+                continue
+            if imgs is None:
+                imgs = torch.cat([target[:, :3], target[:, 3:]], 0)
             im = F.interpolate(imgs, (h, w), mode='area')
             f = torch.cat([flow[:, :2], flow[:, 2:]], 0)
             rec = flow_warp(torch.roll(im, B, 0), f, pad=cfg.warp_pad)
@@ -67,7 +118,7 @@ class unFlowLoss(nn.Module):
                 fsw = torch.roll(f, B, 0)
                 m = 1 - (get_occu_mask_backward(fsw, th=0.2) if cfg.occ_from_back else get_occu_mask_bidirection(f, fsw))
                 m0 = m
-                s = min(h, w)
+                planes, invert = (m0[:B], m0[B:]), False
             else:
                 m = F.interpolate(m0, (h, w), mode='nearest')
             self.pyramid_occu_mask1.append(m[:B])

@@ -364,6 +364,50 @@ int arflow_photo_bwd(const float* im, const float* recons, const float* mask, co
                      const float* coef, float* g_recons, int B, int C, int H, int W,
                      arflow_stream_t stream);
 
+/* ---- fused warp + mask + L1/SSIM pass of one pyramid scale (unFlowLoss, MvLoss) ---------------------
+ * N = G * B samples in G groups (directions / views) of B.  For sample (g, b):
+ *   rec = flow_warp(src, flow, pad_mode)            bilinear, align_corners=True (utils/warp_utils.py:83-90)
+ *   rows -> per group  sum |tgt - rec| * m,  sum SSIMdist(rec * m, tgt * m),  sum m   (the sums of arflow_photo_fwd)
+ * Nothing is copied to feed it: target image, source image ([C,H,W] planes, 1 <= C <= 3, else ARFLOW_EPARAM), flow
+ * ([2,H,W]) and mask plane of sample (g, b) start at  base + b * X_bs + g * X_half  floats (X_half may be negative), so
+ * two images inside one [B,6,H,W] tensor, a [B,4,H,W] flow pair or two separate tensors are read in place.
+ * mask_mode: ARFLOW_PW_MASK_PLANE    m = mask[y, x] of an [H,W] plane;
+ *            ARFLOW_PW_MASK_NEAREST  m = mask[y * (mask_h / H), x * (mask_w / W)] of a [mask_h, mask_w] plane -- the
+ *                                    F.interpolate(mode='nearest') resize for integer factors (others: ARFLOW_ESHAPE);
+ *            ARFLOW_PW_MASK_BORDER   m = border_mask(flow) (utils/warp_utils.py:119-134; `mask` is ignored).
+ * mask_invert != 0 uses 1 - m instead.  mask_out (nullable): [N,1,H,W], receives the plane actually used.
+ * rows: arflow_photo_warp_rows(N, H, W) rows of ARFLOW_SUM_COLS floats, one per 16 x 64 tile in (sample, tile row,
+ * tile column) order, every one written by the call: group g owns rows [g, g + 1) * rows / G and quantity k of the
+ * group is the sum of column k over them.  No atomics: bitwise reproducible.  H, W >= 3. */
+#define ARFLOW_PW_MASK_PLANE 0
+#define ARFLOW_PW_MASK_NEAREST 1
+#define ARFLOW_PW_MASK_BORDER 2
+int arflow_photo_warp_rows(int N, int H, int W);
+int arflow_photo_warp_fwd(const float* tgt, long tgt_bs, long tgt_half, const float* src, long src_bs, long src_half,
+                          const float* flow, long flow_bs, long flow_half, const float* mask, long mask_bs,
+                          long mask_half, int mask_mode, int mask_invert, int mask_h, int mask_w, float* mask_out,
+                          float* rows, int B, int G, int C, int H, int W, int pad_mode, arflow_stream_t stream);
+
+/* d/d flow of  sum_g coef[2g] * (L1 sum of group g) + coef[2g+1] * (SSIM sum of group g)  (coef: 2 G device floats; the
+ * mask sum has no gradient), written for sample (g, b) at  gflow + b * gflow_bs + g * gflow_half  ([2,H,W]): the
+ * gradient of the tensor the flow was read from, so no slice / cat backward is needed.  Warp, mask and window statistics
+ * are recomputed; every pixel owns its two outputs (pure gather, no atomics).  No gradient w.r.t. the images. */
+int arflow_photo_warp_bwd(const float* tgt, long tgt_bs, long tgt_half, const float* src, long src_bs, long src_half,
+                          const float* flow, long flow_bs, long flow_half, const float* mask, long mask_bs,
+                          long mask_half, int mask_mode, int mask_invert, int mask_h, int mask_w, const float* coef,
+                          float* gflow, long gflow_bs, long gflow_half, int B, int G, int C, int H, int W, int pad_mode,
+                          arflow_stream_t stream);
+
+/* Every F.interpolate(frames, (h, w), mode='area') copy of a pyramid loss in one launch.  frames: [planes,H,W];
+ * sizes: HOST array of n (h, w) pairs, n <= ARFLOW_AREA_PYRAMID_MAX (else ARFLOW_EPARAM), h | H and w | W (else
+ * ARFLOW_ESHAPE).  Pair i with a factor > 1 is written as [planes,h,w] behind the pairs before it in the packed `out`
+ * (arflow_area_pyramid_ws_bytes() bytes in all); a pair with h == H and w == W produces nothing.  Every scale is
+ * computed from the full-resolution pixels; a block's pixels are added as lane partials that meet in a shuffle tree. */
+#define ARFLOW_AREA_PYRAMID_MAX 8
+long arflow_area_pyramid_ws_bytes(int planes, int H, int W, const int* sizes, int n);
+int arflow_area_pyramid(const float* frames, float* out, int planes, int H, int W, const int* sizes, int n,
+                        arflow_stream_t stream);
+
 /* ---- edge-aware smoothness ------------------------------------------------------------------------
  * sums[0] += sum_{b,ch,y,x} wx * pen(Dx flow),  sums[1] += sum wy * pen(Dy flow)
  * order 1: Dx f = f[x+1]-f[x];           wx = exp(-alpha * mean_c |img[x+1]-img[x]|)
