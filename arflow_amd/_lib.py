@@ -61,6 +61,9 @@ PROTOTYPES = {
     'arflow_headconv_bwd_data': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
     'arflow_headconv_bwd_weight_ws_bytes': [c_i, c_i, c_i, c_i],
     'arflow_headconv_bwd_weight': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_dense_cat_fwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_l, c_f, c_fp],
+    'arflow_dense_gbias_rows': [c_i, c_l],
+    'arflow_dense_grad_gather': [c_fp, c_i, c_fp, c_l, c_fp, c_fp, c_i, c_i, c_l, c_f, c_fp],
     'arflow_warp_fwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_i, c_i, c_i, c_fp],
     'arflow_warp_bwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_i, c_i, c_i, c_fp],
     'arflow_splat_map': [c_fp, c_fp, c_i, c_i, c_i, c_l, c_i, c_fp],

@@ -637,6 +637,185 @@ def head_conv_enabled():
     return _HEADCONV
 
 
+# ------------------------------------------------------------------------------------------------
+# The dense flow estimator as one autograd node (csrc/dense.hip)
+_DENSE_BLOCK = __import__('os').environ.get('ARFLOW_DENSE_BLOCK', '1') != '0'  # A/B switch for tools/ and tests: 0 = composed path
+DENSE_MAX_SRC = 8  # ARFLOW_DENSE_MAX_SRC of include/arflow_hip.h
+
+
+def dense_block_enabled():
+    return _DENSE_BLOCK
+
+
+def _dense_src_type():
+    import ctypes
+
+    class DenseSrc(ctypes.Structure):  # arflow_dense_src
+        _fields_ = [('ptr', ctypes.c_void_p), ('bstride', ctypes.c_long), ('scale', ctypes.c_void_p)]
+    return DenseSrc
+
+
+_DenseSrc = _dense_src_type()
+
+
+def dense_cat(y, bias, x, slope):
+    """torch.cat([bias_leaky_relu(y, bias, slope), x], 1) in one launch, into a fresh tensor (no autograd: the kernel
+    behind DenseEstimatorFunction's forward)."""
+    _need_gpu(y, bias, x)
+    if y.dim() != 4 or x.dim() != 4 or y.shape[0] != x.shape[0] or y.shape[2:] != x.shape[2:]:
+        raise ValueError('dense_cat expects y [B,oc,H,W] and x [B,C,H,W]')
+    y, x = y.contiguous(), x.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    B, oc, H, W = y.shape
+    C = x.shape[1]
+    out = torch.empty(B, oc + C, H, W, device=y.device, dtype=torch.float32)
+    with torch.cuda.device_of(y):
+        _call('arflow_dense_cat_fwd', _p(y), _p(bias), _p(x), _p(out), B, oc, C, H * W, float(slope), _stream(),
+              key=(B, oc, C, H * W))
+    return out
+
+
+def dense_grad_gather(sources, oc, act=None, slope=0.1, want_bias=False):
+    """gy = lrelu'(act[:, :oc]) * (s_0 + s_1 + ...) in one launch, the sum nested innermost first (acc = s_0; acc = s_1 + acc;
+    ...).  sources: list of (tensor [B,*,H,W] with dense planes, first channel of the slice, per-sample scale [B] or None);
+    act: the tensor whose first oc channels hold the saved activation (None: no activation factor).  Returns (gy packed
+    [B,oc,H,W], bias gradient [oc] or None -- per-workgroup rows folded in a fixed order)."""
+    import ctypes
+    if not 1 <= len(sources) <= DENSE_MAX_SRC:
+        raise ValueError('dense_grad_gather takes 1..%d sources' % DENSE_MAX_SRC)
+    t0 = sources[0][0]
+    B, _, H, W = t0.shape
+    hw = H * W
+    arr = (_DenseSrc * len(sources))()
+    keep = []
+    for j, (t, off, scale) in enumerate(sources):
+        _need_gpu(t, scale)
+        st = t.stride()
+        if t.dim() != 4 or t.shape[0] != B or tuple(t.shape[2:]) != (H, W) or off < 0 or off + oc > t.shape[1]:
+            raise ValueError('dense_grad_gather: source %d does not hold channels %d:%d of a [%d,*,%d,%d] tensor' % (j, off, off + oc, B, H, W))
+        if st[3] != 1 or st[2] != W or st[1] != hw:
+            t = t.contiguous()
+            st = t.stride()
+        if scale is not None:
+            scale = scale.reshape(-1).contiguous()
+            if scale.numel() != B:
+                raise ValueError('dense_grad_gather: a scale holds one value per sample')
+        keep.append((t, scale))
+        arr[j].ptr = t.data_ptr() + 4 * off * hw
+        arr[j].bstride = st[0] if B > 1 else t.shape[1] * hw
+        arr[j].scale = _p(scale)
+    act_bs = 0
+    if act is not None:
+        _need_gpu(act)
+        if act.dim() != 4 or act.shape[0] != B or tuple(act.shape[2:]) != (H, W) or act.shape[1] < oc or not act.is_contiguous():
+            raise ValueError('dense_grad_gather: act must be a contiguous [B,>=oc,H,W] tensor')
+        act_bs = act.shape[1] * hw
+    gy = torch.empty(B, oc, H, W, device=t0.device, dtype=torch.float32)
+    rows = None
+    if want_bias:
+        n = _lib.load().arflow_dense_gbias_rows(B, hw)
+        if n <= 0:
+            _lib.check(n, 'arflow_dense_gbias_rows')
+        rows = torch.empty(n, oc, device=t0.device, dtype=torch.float32)
+    with torch.cuda.device_of(t0):
+        _call('arflow_dense_grad_gather', ctypes.cast(arr, ctypes.c_void_p), len(sources), _p(act), act_bs, _p(gy), _p(rows), B,
+              oc, hw, float(slope), _stream(), key=(B, oc, hw, len(sources), int(act is not None)))
+    return gy, (None if rows is None else rows.sum(0))
+
+
+class DenseEstimatorFunction(torch.autograd.Function):
+    """FlowEstimatorDense (models/pwclite.py:48-66) behind ONE autograd node:
+
+        for k in 1..5:  x_{k+1} = cat([leaky_relu(conv2d(x_k, w_k) + b_k), x_k], 1)
+        flow = conv2d(x_6, w_head) + b_head                         -> (x_6, flow)
+
+    The convolutions stay MIOpen's (bias-free F.conv2d forward, aten.convolution_backward backward: the calls autograd makes);
+    arflow_dense_cat_fwd writes activation and input into their slots of the next tensor, and backward the gradient of layer
+    m's activation is gathered by ONE launch from every tensor that holds a slice of it -- the gradient of x_6, the head's
+    data gradient and the data gradients of the layers above -- in the nesting autograd's accumulation has, so the values
+    MIOpen's backward kernels receive are bit-identical to the composed path's.  Saves x_1 .. x_6 (the activations live
+    inside them) and the weights."""
+
+    @staticmethod
+    def forward(ctx, x, slope, *params):
+        if len(params) != 12:
+            raise ValueError('dense_estimator expects (w, b) of five layers and of the head')
+        _need_gpu(x, *params)
+        slope = float(slope)
+        ws, bs = params[0:10:2], params[1:10:2]
+        w_head, b_head = params[10], params[11]
+        xs = [x.contiguous()]
+        for w, b in zip(ws, bs):
+            y = torch.nn.functional.conv2d(xs[-1], w, None, 1, 1)
+            xs.append(dense_cat(y, b, xs[-1], slope))
+        x6 = xs[-1]
+        B, C6, H, W = x6.shape
+        w_head = w_head.contiguous()
+        flow = torch.empty(B, 2, H, W, device=x.device, dtype=torch.float32)
+        with torch.cuda.device_of(x6):
+            _call('arflow_headconv_fwd', _p(x6), _p(w_head), _p(b_head.contiguous()), _p(flow), B, C6, H, W, _stream())
+        ctx.save_for_backward(*xs, *ws, w_head)
+        ctx.slope = slope
+        ctx.set_materialize_grads(False)
+        return x6, flow
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gx6, gflow):
+        xs, ws, w_head = ctx.saved_tensors[:6], ctx.saved_tensors[6:11], ctx.saved_tensors[11]
+        need = ctx.needs_input_grad
+        grads = [None] * 14
+        if gx6 is None and gflow is None:
+            return tuple(grads)
+        x6 = xs[5]
+        B, C6, H, W = x6.shape
+        ocs = [int(w.shape[0]) for w in ws]
+        # the lowest layer whose gradient chain has to be followed: 0 = down to the estimator's input
+        lowest = 0 if need[0] else next((m for m in range(1, 6) if need[2 * m] or need[2 * m + 1]), 6)
+        dx_head = None
+        with torch.cuda.device_of(x6):
+            if gflow is not None:
+                gflow = gflow.contiguous()
+                if lowest < 6:
+                    dx_head = torch.empty_like(x6)
+                    _call('arflow_headconv_bwd_data', _p(gflow), _p(w_head), _p(dx_head), B, C6, H, W, _stream())
+                if need[12] or need[13]:
+                    nbytes = _lib.load().arflow_headconv_bwd_weight_ws_bytes(B, C6, H, W)
+                    if nbytes < 0:
+                        _lib.check(int(nbytes), 'arflow_headconv_bwd_weight_ws_bytes')
+                    wsb = torch.empty(nbytes, device=x6.device, dtype=torch.uint8)
+                    dw = torch.empty_like(w_head)
+                    db = torch.empty(2, device=x6.device, dtype=torch.float32) if need[13] else None
+                    _call('arflow_headconv_bwd_weight', _p(x6), _p(gflow), _p(dw), _p(db), _p(wsb), B, C6, H, W, _stream())
+                    grads[12], grads[13] = (dw if need[12] else None), db
+        if lowest == 6:
+            return tuple(grads)
+        # sources in the order autograd adds them: x_6's own gradient, the head's, then the layers' from the top down
+        top = [t for t in (gx6, dx_head) if t is not None]
+        dxs = []  # (dx_k, k) for k = 5, 4, ...: the gradient of layer k's input x_k
+        for m in range(5, max(lowest, 1) - 1, -1):
+            # x_k = [a_{k-1}, ..., a_1, x_1]: a_m starts at sum(oc_j, m < j < k)
+            srcs = [(t, sum(ocs[m:5]), None) for t in top] + [(dx, sum(ocs[m:k - 1]), None) for dx, k in dxs]
+            gy, gb = dense_grad_gather(srcs, ocs[m - 1], act=xs[m], slope=ctx.slope, want_bias=need[2 * m + 1])
+            want_dx = m > lowest
+            dx = dw = None
+            if want_dx or need[2 * m]:  # (a layer of which only the bias is trained needs neither)
+                dx, dw, _ = torch.ops.aten.convolution_backward(gy, xs[m - 1], ws[m - 1], None, [1, 1], [1, 1], [1, 1], False,
+                                                                [0, 0], 1, [want_dx, bool(need[2 * m]), False])
+            grads[2 * m], grads[2 * m + 1] = (dw if need[2 * m] else None), gb
+            if want_dx:
+                dxs.append((dx, m))
+        if need[0]:
+            srcs = [(t, sum(ocs), None) for t in top] + [(dx, sum(ocs[:k - 1]), None) for dx, k in dxs]
+            grads[0] = dense_grad_gather(srcs, int(xs[0].shape[1]))[0]
+        return tuple(grads)
+
+
+def dense_estimator(x, slope, params):
+    """(x6, flow) of FlowEstimatorDense; params = (w1, b1, ..., w5, b5, w_head, b_head)."""
+    return DenseEstimatorFunction.apply(x, slope, *params)
+
+
 class BiasLeakyReLUMomentsFunction(torch.autograd.Function):
     """bias_leaky_relu that also returns the partial moments (sum y, sum y^2) of its output as rows of 2 doubles
     ([B, rows, 2], arflow_bias_act_fwd_mom): normalize_features' moments taken where the feature map is produced."""

@@ -106,8 +106,17 @@ class FlowEstimatorDense(nn.Module):
         self.feat_dim = ch_in + 448
         self.conv_last = conv(ch_in + 448, 2, isReLU=False)
 
+    def native(self, x):
+        """The whole estimator as one autograd node (AF.dense_estimator) under the rule HeadConv.native applies: a CUDA fp32
+        4-D input and the package's own bias_act (a twin that has swapped it out keeps the tensor expression below)."""
+        return AF.dense_block_enabled() and self.conv_last.native(x) and self.conv1[0].weight.dtype == torch.float32
+
     def forward(self, x):
-        for layer in (self.conv1, self.conv2, self.conv3, self.conv4, self.conv5):
+        layers = (self.conv1, self.conv2, self.conv3, self.conv4, self.conv5)
+        if self.native(x):
+            params = [p for layer in layers + (self.conv_last,) for p in (layer[0].weight, layer[0].bias)]
+            return AF.dense_estimator(x, self.conv1[1].negative_slope, params)
+        for layer in layers:
             x = torch.cat([layer(x), x], dim=1)
         return x, self.conv_last(x)
 

@@ -235,6 +235,34 @@ long arflow_headconv_bwd_weight_ws_bytes(int B, int C, int H, int W);
 int arflow_headconv_bwd_weight(const float* x, const float* dy, float* dw, float* dbias, void* ws, int B, int C, int H,
                                int W, arflow_stream_t stream);
 
+/* ---- dense flow estimator: concatenating epilogue and gradient gather ---------------------------
+ * FlowEstimatorDense (models/pwclite.py:48-66) runs five times x = cat([lrelu(conv(x) + bias), x], 1).
+ *
+ * arflow_dense_cat_fwd: out[:, :oc] = lrelu(y + bias[c]), out[:, oc:] = x, for y: [B, oc, HW] (the bias-free
+ * convolution output), x: [B, C, HW], out: [B, oc + C, HW], all packed; bias nullable.  The arithmetic is
+ * arflow_bias_act_fwd's; float4 accesses when HW % 4 == 0 (the pointers must then be 16-byte aligned: ARFLOW_EPARAM).
+ *
+ * arflow_dense_grad_gather: gy[b, c, :] = d[b, c, :] * (s_0 + s_1 + ... ) for c < oc, with
+ *     acc = s_0;  acc = s_1 + acc;  acc = s_2 + acc; ...        (each s_j multiplied by scale_j[b] first, if given)
+ * in exactly this nesting and without contraction -- the order autograd accumulates the gradients of a
+ * concatenation's slices in -- and d = (act > 0 ? 1 : negative_slope), or 1 when act is NULL.  `srcs` is a HOST array
+ * of n_src (1 .. ARFLOW_DENSE_MAX_SRC) descriptors; it travels in the kernel arguments and need not outlive the call.
+ * A source's `ptr` addresses channel 0 of the slice in sample 0 (planes of HW floats, dense), `bstride` is its sample
+ * stride in floats, `scale` an optional [B] device vector.  act is read in place (sample stride act_bs floats); gy is
+ * packed [B, oc, HW].  gbias_rows (nullable): [arflow_dense_gbias_rows(B, HW)][oc] floats, every entry written by
+ * the call; the bias gradient is the sum over the rows (fixed order: bitwise reproducible; no zero-fill, no atomics). */
+#define ARFLOW_DENSE_MAX_SRC 8
+typedef struct {
+  const float* ptr;
+  long bstride;
+  const float* scale;
+} arflow_dense_src;
+int arflow_dense_cat_fwd(const float* y, const float* bias, const float* x, float* out, int B, int oc, int C, long HW,
+                         float negative_slope, arflow_stream_t stream);
+int arflow_dense_gbias_rows(int B, long HW);
+int arflow_dense_grad_gather(const arflow_dense_src* srcs, int n_src, const float* act, long act_bs, float* gy,
+                             float* gbias_rows, int B, int oc, long HW, float negative_slope, arflow_stream_t stream);
+
 /* ---- bilinear warp ----------------------------------------------------------------------------
  * out[b,c,y,x] = bilinear(src[b,c], x + flow[b,0,y,x], y + flow[b,1,y,x]) with torch grid_sample
  * semantics (pad zeros|border, align_corners) after the reference's normalise/un-normalise round

@@ -165,6 +165,54 @@ def main():
             hrec('arflow_headconv_bwd_data', timeit(lambda: lib.arflow_headconv_bwd_data(p(dy), p(wt), p(dx), B2, C, h, w, s), args.iters))
             hrec('arflow_headconv_bwd_weight', timeit(lambda: lib.arflow_headconv_bwd_weight(p(x), p(dy), p(dw), p(db), p(ws), B2, C, h, w, s), args.iters))
             del x, dx, ws
+    if want('dense'):  # the dense estimator's concatenating epilogue and gradient gather (csrc/dense.hip), five layers x four levels
+        import ctypes
+        from arflow_amd.functional import _DenseSrc
+        ocs = (128, 128, 96, 64, 32)
+        for li, (_, h, w) in enumerate(levels[-4:]):
+            hw = h * w
+            cin = 115 if li == 0 else 147  # volume 81 + features 32 + flow 2 (+ 32 upsampled context channels below the top)
+            plane = 4 * B2 * hw
+
+            def drec(name, shape, us, planes):
+                MANIFEST[-1].update(name=name, shape=list(shape), us=us)
+                gbs = planes * plane / us / 1e3
+                print('%-22s %-26s %9.1f us %9.1f GB/s  %5.1f%% of HBM peak  (%d planes)' % (name, list(shape), us, gbs, 100 * gbs / HBM_PEAK_GBS, planes), flush=True)
+            # the yardstick of the same run: the in-place epilogue and its backward at 128 channels
+            t = torch.randn(B2, 128, h, w, device=dev, generator=g)
+            t2, t3 = torch.randn(B2, 128, h, w, device=dev, generator=g), torch.empty(B2, 128, h, w, device=dev)
+            b128, gb128 = torch.randn(128, device=dev, generator=g), torch.empty(128, device=dev)
+            drec('arflow_bias_act_fwd', (B2, 128, hw), timeit(lambda: lib.arflow_bias_act_fwd(p(t), p(b128), p(t), B2, 128, hw, 0.1, s), args.iters), 2 * 128)
+            drec('arflow_bias_act_bwd', (B2, 128, hw), timeit(lambda: lib.arflow_bias_act_bwd(p(t2), p(t), p(t3), p(gb128), B2, 128, hw, 0.1, s), args.iters), 3 * 128)
+            del t, t2, t3
+            chans = [cin + sum(ocs[:k]) for k in range(6)]  # channels of x_1 .. x_6
+            G = [torch.randn(B2, chans[5], h, w, device=dev, generator=g) for _ in range(2)]  # gradient of x_6, the head's data gradient
+            DX = {k: torch.randn(B2, chans[k - 1], h, w, device=dev, generator=g) for k in range(2, 6)}  # dx_k: gradient of x_k
+            DX[1] = torch.randn(B2, cin, h, w, device=dev, generator=g)
+            for m in range(1, 6):
+                C, oc = chans[m - 1], ocs[m - 1]
+                y = torch.randn(B2, oc, h, w, device=dev, generator=g)
+                x = torch.randn(B2, C, h, w, device=dev, generator=g)
+                bias = torch.randn(oc, device=dev, generator=g)
+                out = torch.empty(B2, oc + C, h, w, device=dev)
+                drec('arflow_dense_cat_fwd', (B2, oc, C, hw), timeit(lambda: lib.arflow_dense_cat_fwd(p(y), p(bias), p(x), p(out), B2, oc, C, hw, 0.1, s), args.iters), 2 * (oc + C))
+                srcs = [(G[0], sum(ocs[m:5])), (G[1], sum(ocs[m:5]))] + [(DX[k], sum(ocs[m:k - 1])) for k in range(5, m, -1)]
+                arr = (_DenseSrc * len(srcs))()
+                for j, (tt, off) in enumerate(srcs):
+                    arr[j].ptr, arr[j].bstride, arr[j].scale = tt.data_ptr() + 4 * off * hw, tt.shape[1] * hw, None
+                gy = torch.empty(B2, oc, h, w, device=dev)
+                rows = torch.empty(lib.arflow_dense_gbias_rows(B2, hw), oc, device=dev)
+                drec('arflow_dense_grad_gather', (B2, oc, hw, len(srcs), 1), timeit(lambda: lib.arflow_dense_grad_gather(
+                    ctypes.cast(arr, ctypes.c_void_p), len(srcs), p(out), (oc + C) * hw, p(gy), p(rows), B2, oc, hw, 0.1, s), args.iters), oc * (len(srcs) + 2))
+                del y, x, out, gy
+            srcs = [(G[0], sum(ocs)), (G[1], sum(ocs))] + [(DX[k], sum(ocs[:k - 1])) for k in range(5, 0, -1)]
+            arr = (_DenseSrc * len(srcs))()
+            for j, (tt, off) in enumerate(srcs):
+                arr[j].ptr, arr[j].bstride, arr[j].scale = tt.data_ptr() + 4 * off * hw, tt.shape[1] * hw, None
+            gx = torch.empty(B2, cin, h, w, device=dev)
+            drec('arflow_dense_grad_gather', (B2, cin, hw, len(srcs), 0), timeit(lambda: lib.arflow_dense_grad_gather(
+                ctypes.cast(arr, ctypes.c_void_p), len(srcs), None, 0, p(gx), None, B2, cin, hw, 0.1, s), args.iters), cin * (len(srcs) + 1))
+            del G, DX, gx
     # loss side: B = batch/2 image pairs at full resolution, per direction
     B = max(1, B2 // 2)
     im1 = torch.rand(B, 3, H0, W0, device=dev, generator=g)
