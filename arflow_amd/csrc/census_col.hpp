@@ -60,14 +60,6 @@ __device__ __forceinline__ void load_plane(float* __restrict__ tile, const float
   }
 }
 
-__device__ __forceinline__ float sample1(const TapPlan& p, const float (&a)[4]) {
-  float r = p.ok[0] ? a[0] * p.w[0] : 0.f;  // the per-channel expression of warp_fwd_kernel
-  r = p.ok[1] ? fmaf(a[1], p.w[1], r) : r;
-  r = p.ok[2] ? fmaf(a[2], p.w[2], r) : r;
-  r = p.ok[3] ? fmaf(a[3], p.w[3], r) : r;
-  return r;
-}
-
 // grey tile of the WARPED image b over the same rectangle (zero outside the image: the census transform zero-pads).
 // Two batches: all flow loads of a batch are issued together, then all its 4 x taps.
 template <int R>
@@ -104,7 +96,7 @@ __device__ __forceinline__ void load_gray_warped(float* __restrict__ tile, const
     for (int k = 0; k < HB; ++k) {
       const int i = threadIdx.x + (k0 + k) * NT;
       const int r = i / NC, c = i - r * NC;
-      if (k0 + k < ITER && i < NR * NC) tile[r * PITCH + c] = in[k] ? sample1(p[k], a[k]) : 0.f;
+      if (k0 + k < ITER && i < NR * NC) tile[r * PITCH + c] = in[k] ? tap_blend(p[k], a[k]) : 0.f;
     }
   }
 }
@@ -161,13 +153,14 @@ __device__ __forceinline__ void fill_tiles(float* __restrict__ ta, float* __rest
       if (k0 + k < ITER && i < NR * NC) {
         const int o = r * PITCH + c;
         ta[o] = in[k] ? pa[k] : 0.f;
-        tb[o] = in[k] ? sample1(p[k], a[k]) : 0.f;
+        tb[o] = in[k] ? tap_blend(p[k], a[k]) : 0.f;
         if (BWD) {
           t2[o] = in[k] ? pg[k] : 0.f;
-          const float nw = p[k].ok[0] ? a[k][0] : 0.f, ne = p[k].ok[1] ? a[k][1] : 0.f;
-          const float sw = p[k].ok[2] ? a[k][2] : 0.f, se = p[k].ok[3] ? a[k][3] : 0.f;
-          t3[o] = ((ne - nw) * t[k].wy0 + (se - sw) * t[k].wy1) * t[k].dx;
-          t4[o] = ((sw - nw) * t[k].wx0 + (se - ne) * t[k].wx1) * t[k].dy;
+          float sx, sy;
+          tap_select(p[k], a[k], a[k]);
+          tap_corner_grad(t[k], a[k], sx, sy);
+          t3[o] = sx * t[k].dx;
+          t4[o] = sy * t[k].dy;
         } else {
           // mask_invalid(flow_to_warp(flow)), utils/uflow_utils.py:35-50 (as warp_fwd_kernel's `valid`)
           const float cx = (float)gx[k] + u[k], cy = (float)gy[k] + v[k];

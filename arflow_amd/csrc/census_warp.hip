@@ -47,14 +47,6 @@ __device__ __forceinline__ void load_plane(float* __restrict__ tile, const float
   }
 }
 
-__device__ __forceinline__ float sample1(const TapPlan& p, const float (&a)[4]) {
-  float r = p.ok[0] ? a[0] * p.w[0] : 0.f;  // the per-channel expression of warp_fwd_kernel
-  r = p.ok[1] ? fmaf(a[1], p.w[1], r) : r;
-  r = p.ok[2] ? fmaf(a[2], p.w[2], r) : r;
-  r = p.ok[3] ? fmaf(a[3], p.w[3], r) : r;
-  return r;
-}
-
 // Grey tile of the WARPED image b: rows [ty0-R, ty0+TYH+R), columns [tx0-R, tx0+TXW+R); zero outside the image
 // (the census transform zero-pads).  All flow loads of a thread are issued together, then all its 4 x ITER taps:
 // two round trips for the whole fill instead of a dependent chain per pixel.
@@ -90,7 +82,7 @@ __device__ __forceinline__ void load_gray_warped(float* __restrict__ tile, const
   for (int k = 0; k < ITER; ++k) {
     const int i = threadIdx.x + k * NT;
     const int r = i / NC, c = i - r * NC;
-    if (i < NR * NC) tile[r * PITCH + (c + 4 - R)] = in[k] ? sample1(p[k], a[k]) : 0.f;
+    if (i < NR * NC) tile[r * PITCH + (c + 4 - R)] = in[k] ? tap_blend(p[k], a[k]) : 0.f;
   }
 }
 
@@ -222,13 +214,13 @@ __device__ __forceinline__ void bwd_body(const float* __restrict__ gray_a, const
   for (int p = 0; p < 4; ++p) {
     const Taps t = make_taps((float)(x0 + p), (float)y, uu[p], vv[p], H, W, H, W, ARFLOW_PAD_ZEROS, true, ARFLOW_NORM_UFLOW);
     const TapPlan pl = plan_taps(t, H, W);
-    float a[4];
+    float a[4], sx, sy;
 #pragma unroll
     for (int q = 0; q < 4; ++q) a[q] = sb[pl.o[q]];
-    const float nw = pl.ok[0] ? a[0] : 0.f, ne = pl.ok[1] ? a[1] : 0.f;
-    const float sw = pl.ok[2] ? a[2] : 0.f, se = pl.ok[3] ? a[3] : 0.f;
-    cdx[p] = ((ne - nw) * t.wy0 + (se - sw) * t.wy1) * t.dx;
-    cdy[p] = ((sw - nw) * t.wx0 + (se - ne) * t.wx1) * t.dy;
+    tap_select(pl, a, a);
+    tap_corner_grad(t, a, sx, sy);
+    cdx[p] = sx * t.dx;
+    cdy[p] = sy * t.dy;
   }
   float ca[4], cb[4], cg[4], acc[4] = {0.f, 0.f, 0.f, 0.f};
   {

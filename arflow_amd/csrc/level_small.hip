@@ -122,10 +122,8 @@ __global__ __launch_bounds__(NT) void fwd_kernel(FwdArgs a) {
 #pragma unroll 8
       for (int c = 0; c < C; ++c) {
         const float* s = arena + c * HW;
-        float r = tp[k].ok[0] ? s[tp[k].o[0]] * tp[k].w[0] : 0.f;
-        r = tp[k].ok[1] ? fmaf(s[tp[k].o[1]], tp[k].w[1], r) : r;
-        r = tp[k].ok[2] ? fmaf(s[tp[k].o[2]], tp[k].w[2], r) : r;
-        r = tp[k].ok[3] ? fmaf(s[tp[k].o[3]], tp[k].w[3], r) : r;
+        const float v[4] = {s[tp[k].o[0]], s[tp[k].o[1]], s[tp[k].o[2]], s[tp[k].o[3]]};
+        const float r = tap_blend(tp[k], v);
         x2wb[(long)c * HW + px] = r;  // every row-shift workgroup writes the same values and reads its own
         mom[2] += r, mom[3] = fmaf(r, r, mom[3]);
       }

@@ -67,15 +67,8 @@ __device__ __forceinline__ Pixel pixel(const Args& a, const float* __restrict__ 
 __device__ __forceinline__ void taps4(const float* __restrict__ s, const TapPlan& p, float (&v)[4]) {
   float a0 = s[p.o[0]], a1 = s[p.o[1]], a2 = s[p.o[2]], a3 = s[p.o[3]];
   asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));
-  v[0] = p.ok[0] ? a0 : 0.f, v[1] = p.ok[1] ? a1 : 0.f, v[2] = p.ok[2] ? a2 : 0.f, v[3] = p.ok[3] ? a3 : 0.f;
-}
-// warp_fwd_kernel's accumulation order
-__device__ __forceinline__ float bilinear(const float (&v)[4], const TapPlan& p) {
-  float r = p.ok[0] ? v[0] * p.w[0] : 0.f;
-  r = p.ok[1] ? fmaf(v[1], p.w[1], r) : r;
-  r = p.ok[2] ? fmaf(v[2], p.w[2], r) : r;
-  r = p.ok[3] ? fmaf(v[3], p.w[3], r) : r;
-  return r;
+  const float a[4] = {a0, a1, a2, a3};
+  tap_select(p, a, v);
 }
 
 __global__ __launch_bounds__(NT) void fwd_kernel(Args a, float* __restrict__ mask_out, float* __restrict__ rows) {
@@ -109,7 +102,7 @@ __global__ __launch_bounds__(NT) void fwd_kernel(Args a, float* __restrict__ mas
         if (c < a.C) {
           float v[4];
           taps4(sr + c * cs, px.p, v);
-          const float rec = bilinear(v, px.p), iv = tg[c * cs + o];
+          const float rec = tap_blend(px.p, v), iv = tg[c * cs + o];
           xv[c] = rec * px.m;
           yv[c] = iv * px.m;
           l1 += fabsf(iv - rec) * px.m;
@@ -181,7 +174,7 @@ __global__ __launch_bounds__(NT) void bwd_kernel(Args a, const float* __restrict
         if (c < a.C) {
           float v[4];
           taps4(sr + c * cs, px.p, v);
-          xv[c] = bilinear(v, px.p) * px.m;
+          xv[c] = tap_blend(px.p, v) * px.m;
           yv[c] = tg[c * cs + o] * px.m;
         }
       }
@@ -248,15 +241,16 @@ __global__ __launch_bounds__(NT) void bwd_kernel(Args a, const float* __restrict
         }
       float v[4];
       taps4(sr + c * cs, px[e].p, v);
-      const float rec = bilinear(v, px[e].p);
+      const float rec = tap_blend(px[e].p, v);
       const float iv = tg[c * cs + (in[e] ? (long)y * a.W + x0 + e : 0)];
       const float diff = rec - iv;
       const float sg = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
       // photo4::bwd_kernel's d / d rec, fed into warp_bwd_flow_kernel's d rec / d coordinate
       const float gr = px[e].m * (c_l1 * sg + sa + sb * xc[4 + e] + sc * yc[4 + e]);
-      const Taps& t = px[e].t;
-      gix[e] = fmaf(gr, (v[1] - v[0]) * t.wy0 + (v[3] - v[2]) * t.wy1, gix[e]);
-      giy[e] = fmaf(gr, (v[2] - v[0]) * t.wx0 + (v[3] - v[1]) * t.wx1, giy[e]);
+      float sx, sy;
+      tap_corner_grad(px[e].t, v, sx, sy);
+      gix[e] = fmaf(gr, sx, gix[e]);
+      giy[e] = fmaf(gr, sy, giy[e]);
     }
   }
   float* gf = gflow + b * gflow_bs + g * gflow_half + (long)y * a.W + x0;

@@ -55,6 +55,35 @@ __device__ __forceinline__ TapPlan plan_taps(const Taps& t, int Hs, int Ws) {
   return p;
 }
 
+// The tap arithmetic, stated ONCE: tests compare fused paths against unfused ones bit for bit, so every kernel that
+// samples calls these (a[k] = the value loaded at p.o[k]; the loads and their scheduling stay with the caller).
+// Bilinear sample, accumulated north-west, north-east, south-west, south-east; a tap outside the source adds nothing.
+__device__ __forceinline__ float tap_blend(const TapPlan& p, const float (&a)[4]) {
+  float r = p.ok[0] ? a[0] * p.w[0] : 0.f;
+  r = p.ok[1] ? fmaf(a[1], p.w[1], r) : r;
+  r = p.ok[2] ? fmaf(a[2], p.w[2], r) : r;
+  r = p.ok[3] ? fmaf(a[3], p.w[3], r) : r;
+  return r;
+}
+// The taps as the gradient kernels read them: zero outside the source.
+__device__ __forceinline__ void tap_select(const TapPlan& p, const float (&a)[4], float (&v)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = p.ok[k] ? a[k] : 0.f;
+}
+// ... read from plane (or LDS window) s at offsets o: only the taps inside the source are read.  The staged flow-gradient
+// loop uses this form: with four unconditional LDS reads per channel ahead of the selects warp_bwd_flow_kernel<2> needs
+// 66 VGPRs (7 waves per SIMD) instead of 62 (8).
+__device__ __forceinline__ void tap_select(const TapPlan& p, const float* __restrict__ s, const int (&o)[4], float (&v)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = p.ok[k] ? s[o[k]] : 0.f;
+}
+// d sample / d coordinate of tap values v (from tap_select): the corner differences along x blended over y, and along
+// y blended over x.  Times t.dx / t.dy this is d sample / d flow.
+__device__ __forceinline__ void tap_corner_grad(const Taps& t, const float (&v)[4], float& sx, float& sy) {
+  sx = (v[1] - v[0]) * t.wy0 + (v[3] - v[2]) * t.wy1;
+  sy = (v[2] - v[0]) * t.wx0 + (v[3] - v[1]) * t.wx1;
+}
+
 // Source rows / weights of output index d of the x2 bilinear upsample n_in -> n_out = 2 n_in:
 // ATen/native/UpSample.h area_pixel_compute_source_index + the index / lambda arithmetic of upsample_bilinear2d.
 __device__ __forceinline__ void up2_source(int d, int n_in, int n_out, bool align, int& i0, int& i1, float& l0,

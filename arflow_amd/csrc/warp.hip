@@ -8,6 +8,7 @@
 // channel plane and (for small displacements) the four source taps are coalesced.  Coordinates
 // and bilinear weights are computed once per pixel and reused for all channels.  HBM traffic is
 // the compulsory 4*px*(2C+2) bytes forward, 4*px*(3C+4) backward.
+#include <type_traits>
 #include "common.hpp"
 #include "taps.hpp"
 #include "featnorm_stats.hpp"
@@ -32,12 +33,76 @@ __device__ __forceinline__ float4 load4(const bf16_t* p) {  // 4 bf16 = one 8-by
                      __uint_as_float(r.y & 0xffff0000u));
 }
 
+// Shared prologue of the tile kernels: the bounding box, over the workgroup's 256 threads, of what each of them touches.
+// A thread passes its own inclusive box (lo > hi: nothing) and every thread gets the union; `red` / `box` are the
+// calling kernel's LDS.  Two barriers: all threads of the workgroup must call.
+struct TileBox {
+  int x0, y0, x1, y1;  // inclusive; empty when x1 < x0
+};
+__device__ __forceinline__ TileBox block_bbox(int lo_x, int lo_y, int hi_x, int hi_y, int (*red)[4], int* box) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    lo_x = min(lo_x, __shfl_xor(lo_x, off, 64));
+    lo_y = min(lo_y, __shfl_xor(lo_y, off, 64));
+    hi_x = max(hi_x, __shfl_xor(hi_x, off, 64));
+    hi_y = max(hi_y, __shfl_xor(hi_y, off, 64));
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[0][wave] = lo_x, red[1][wave] = lo_y, red[2][wave] = hi_x, red[3][wave] = hi_y;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int a = red[0][0], bb = red[1][0], c = red[2][0], d = red[3][0];
+    for (int w = 1; w < 4; ++w) a = min(a, red[0][w]), bb = min(bb, red[1][w]), c = max(c, red[2][w]), d = max(d, red[3][w]);
+    box[0] = a, box[1] = bb, box[2] = c, box[3] = d;
+  }
+  __syncthreads();
+  TileBox r;
+  r.x0 = box[0], r.y0 = box[1], r.x1 = box[2], r.y1 = box[3];
+  return r;
+}
+// the box of the valid taps of the workgroup's pixels
+__device__ __forceinline__ TileBox tile_bbox(const Taps& t, int (*red)[4], int* box) {
+  const bool any = (t.vx0 || t.vx1) && (t.vy0 || t.vy1);
+  return block_bbox(any ? t.x0 + (t.vx0 ? 0 : 1) : 0x7fffffff, any ? t.y0 + (t.vy0 ? 0 : 1) : 0x7fffffff,
+                    any ? t.x0 + (t.vx1 ? 1 : 0) : -0x7fffffff, any ? t.y0 + (t.vy1 ? 1 : 0) : -0x7fffffff, red, box);
+}
+
 namespace fwd_win {
 constexpr int TX = 32, TY = 8, NT = 256, HMAX = 24;
 // CCH = channels staged per chunk.  These kernels are latency-bound chains (flow -> taps -> box -> window -> taps),
 // so what counts is how many workgroups a CU holds, i.e. the LDS window: 4 channels (27.6 KB, 5 per CU) ran the
 // B16 C32 96x160 forward in 24.5 us, 2 channels (13.8 KB, 8 per CU = the wave limit) in 18.8 us; the 3-channel
 // image warps of the losses use 3 (20.7 KB, 7 per CU): 30.0 -> 24.7 us
+
+// The source window of a tile, described ONCE for the four kernels that stage it (forward, flow gradient, and their level
+// forms): the rows by0 .. by0 + bh - 1 of the source from the 16-byte aligned column ax0, in LDS rows of wq float4 -- 12
+// when 48 floats from ax0 cover the box, else 18 (this is the only place that chooses).  It is staged (`fits`) when the
+// source rows are 16-byte aligned and the box needs at most HMAX rows of 72 floats; otherwise the kernels gather from
+// global memory, and an `empty` box (no tap of the tile inside the source) has nothing to read at all.
+constexpr int WQ_NARROW = 12, WQ_WIDE = 18, WMAX = 4 * WQ_WIDE;
+struct SrcWindow {
+  bool empty, fits;  // workgroup-uniform, like wq, ax0, by0, bh
+  int wq, ax0, by0, bh;
+  int l[4];  // LDS offsets of this pixel's four taps at that pitch
+};
+__device__ __forceinline__ SrcWindow src_window(const TileBox& bb, const Taps& t, int Hs, int Ws) {
+  SrcWindow wd;
+  wd.by0 = bb.y0, wd.bh = bb.y1 - bb.y0 + 1;
+  wd.ax0 = bb.x0 & ~3;                  // 16-byte aligned window start
+  const int aw = bb.x1 - wd.ax0 + 1;    // floats needed from ax0
+  wd.empty = bb.x1 < bb.x0;
+  wd.fits = !wd.empty && (Ws & 3) == 0 && wd.bh <= HMAX && aw <= WMAX;
+  wd.wq = aw <= 4 * WQ_NARROW ? WQ_NARROW : WQ_WIDE;
+  // LDS offsets of the four taps (clamped like the global ones, relative to the window)
+  const int xa = min(max(t.x0, 0), Ws - 1) - wd.ax0, xb = min(max(t.x0 + 1, 0), Ws - 1) - wd.ax0;
+  const int ya = min(max(t.y0, 0), Hs - 1) - wd.by0, yb = min(max(t.y0 + 1, 0), Hs - 1) - wd.by0;
+  // taps of pixels without any valid tap may point outside the window: clamp (their weight is unused)
+  const int cxa = min(max(xa, 0), WMAX - 1), cxb = min(max(xb, 0), WMAX - 1);
+  const int cya = min(max(ya, 0), HMAX - 1), cyb = min(max(yb, 0), HMAX - 1);
+  const int wp = 4 * wd.wq;
+  wd.l[0] = cya * wp + cxa, wd.l[1] = cya * wp + cxb, wd.l[2] = cyb * wp + cxa, wd.l[3] = cyb * wp + cxb;
+  return wd;
+}
 
 // Stage CCH channels of the source window (bh rows x WQ aligned float4 each) into LDS.  All loads of a
 // thread are issued before the first LDS write and none is branched around (a slot outside the window
@@ -93,13 +158,12 @@ __device__ __forceinline__ void window_store(float* __restrict__ win, const floa
 // MOM: also accumulate this thread's share of the moments the feature normalisation needs -- (sum, sum of squares) of
 // the first feature map at the thread's pixel (`x1p`, read one chunk ahead like the window) and of the warped values
 // it has just produced -- into mom[0..3] (fp32 over <= C values per thread; the caller continues in double).
-template <int WQ, int CCH, typename TS, bool MOM = false>  // window row = WQ float4
-__device__ __forceinline__ void run(float* __restrict__ win, const TS* __restrict__ sp, float* __restrict__ op,
-                                    const TapPlan& p, bool inside, int C, int ss, int os, int Ws, int ax0, int by0,
-                                    int bh, int l0, int l1, int l2, int l3, const float* __restrict__ x1p = nullptr,
-                                    float* mom = nullptr) {
+template <int WQ, int CCH, typename TS, bool MOM>  // window row = WQ float4
+__device__ __forceinline__ void run_pitch(float* __restrict__ win, const TS* __restrict__ sp, float* __restrict__ op,
+                                          const TapPlan& p, bool inside, int C, int ss, int os, int Ws,
+                                          const SrcWindow& wd, const float* __restrict__ x1p, float* mom) {
   constexpr int WP = 4 * WQ;
-  const WindowPlan<WQ> pl = window_plan<WQ>(Ws, ax0, by0, bh);
+  const WindowPlan<WQ> pl = window_plan<WQ>(Ws, wd.ax0, wd.by0, wd.bh);
   float4 v[CCH][WindowPlan<WQ>::ITER];
   float xn[CCH];
   auto fetch_x1 = [&](int cc) {
@@ -127,10 +191,8 @@ __device__ __forceinline__ void run(float* __restrict__ win, const TS* __restric
       for (int c = 0; c < CCH; ++c) {
         if (c0 + c < C) {
           const float* w = win + c * HMAX * WP;
-          float r = p.ok[0] ? w[l0] * p.w[0] : 0.f;
-          r = p.ok[1] ? fmaf(w[l1], p.w[1], r) : r;
-          r = p.ok[2] ? fmaf(w[l2], p.w[2], r) : r;
-          r = p.ok[3] ? fmaf(w[l3], p.w[3], r) : r;
+          const float a[4] = {w[wd.l[0]], w[wd.l[1]], w[wd.l[2]], w[wd.l[3]]};
+          const float r = tap_blend(p, a);
           op[(long)(c0 + c) * os] = r;
           if (MOM) {
             mom[0] += xa[c], mom[1] = fmaf(xa[c], xa[c], mom[1]);
@@ -142,6 +204,16 @@ __device__ __forceinline__ void run(float* __restrict__ win, const TS* __restric
     __syncthreads();
   }
 }
+// the staged path of a tile whose window fits (wd.fits): all threads of the workgroup call
+template <int CCH, typename TS, bool MOM = false>
+__device__ __forceinline__ void run(float* __restrict__ win, const TS* __restrict__ sp, float* __restrict__ op,
+                                    const TapPlan& p, bool inside, int C, int ss, int os, int Ws, const SrcWindow& wd,
+                                    const float* __restrict__ x1p = nullptr, float* mom = nullptr) {
+  if (wd.wq == WQ_NARROW)
+    run_pitch<WQ_NARROW, CCH, TS, MOM>(win, sp, op, p, inside, C, ss, os, Ws, wd, x1p, mom);
+  else
+    run_pitch<WQ_WIDE, CCH, TS, MOM>(win, sp, op, p, inside, C, ss, os, Ws, wd, x1p, mom);
+}
 }  // namespace fwd_win
 
 template <int CCH, typename TS = float>
@@ -151,15 +223,14 @@ __global__ __launch_bounds__(256) void warp_fwd_kernel(const TS* __restrict__ sr
                                                        int nimg, int C, int Hs, int Ws, int H, int W, long fbs,
                                                        int pad, int align, int norm) {
   using namespace fwd_win;
-  __shared__ __attribute__((aligned(16))) float win[CCH * HMAX * 72];
+  __shared__ __attribute__((aligned(16))) float win[CCH * HMAX * WMAX];
   __shared__ int red[4][NT / 64];
   __shared__ int box[4];
   int btx, bty, b;
   if (!af_tile_of_block((W + TX - 1) / TX, (H + TY - 1) / TY, nimg, btx, bty, b)) return;
   const int x = btx * TX + (int)(threadIdx.x & 31), y = bty * TY + (int)(threadIdx.x >> 5);
   const bool inside = x < W && y < H;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  Taps t;
+  Taps t = no_taps();
   if (inside) {
     const float* fb = flow + (long)b * fbs + (long)y * W + x;
     const float u = fb[0], v = fb[(long)H * W];
@@ -170,58 +241,19 @@ __global__ __launch_bounds__(256) void warp_fwd_kernel(const TS* __restrict__ sr
       valid[((long)b * H + y) * W + x] =
           (cx >= 0.f && cx <= (float)(W - 1) && cy >= 0.f && cy <= (float)(H - 1)) ? 1.f : 0.f;
     }
-  } else {
-    t.vx0 = t.vx1 = t.vy0 = t.vy1 = false;
-    t.x0 = t.y0 = 0;
-    t.wx0 = t.wx1 = t.wy0 = t.wy1 = t.dx = t.dy = 0.f;
   }
   const TapPlan p = plan_taps(t, Hs, Ws);
-  // bounding box of the valid taps over the workgroup
-  const bool any = (t.vx0 || t.vx1) && (t.vy0 || t.vy1);
-  int lo_x = any ? t.x0 + (t.vx0 ? 0 : 1) : 0x7fffffff, hi_x = any ? t.x0 + (t.vx1 ? 1 : 0) : -0x7fffffff;
-  int lo_y = any ? t.y0 + (t.vy0 ? 0 : 1) : 0x7fffffff, hi_y = any ? t.y0 + (t.vy1 ? 1 : 0) : -0x7fffffff;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo_x = min(lo_x, __shfl_xor(lo_x, off, 64));
-    lo_y = min(lo_y, __shfl_xor(lo_y, off, 64));
-    hi_x = max(hi_x, __shfl_xor(hi_x, off, 64));
-    hi_y = max(hi_y, __shfl_xor(hi_y, off, 64));
-  }
-  if (lane == 0) red[0][wave] = lo_x, red[1][wave] = lo_y, red[2][wave] = hi_x, red[3][wave] = hi_y;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int a = red[0][0], bb = red[1][0], c = red[2][0], d = red[3][0];
-    for (int w = 1; w < NT / 64; ++w)
-      a = min(a, red[0][w]), bb = min(bb, red[1][w]), c = max(c, red[2][w]), d = max(d, red[3][w]);
-    box[0] = a, box[1] = bb, box[2] = c, box[3] = d;
-  }
-  __syncthreads();
-  const int bx0 = box[0], by0 = box[1];
-  const int bh = box[3] - by0 + 1;
-  const int ax0 = bx0 & ~3;                   // 16-byte aligned window start
-  const int aw = box[2] - ax0 + 1;            // floats needed from ax0
-  const bool empty = box[2] < bx0;
+  const SrcWindow wd = src_window(tile_bbox(t, red, box), t, Hs, Ws);
   const int ss = Hs * Ws, os = H * W;
   const TS* sp = src + (long)b * C * ss;
   float* op = out + (long)b * C * os + (long)y * W + x;
 
-  if (!empty && (Ws & 3) == 0 && bh <= HMAX && aw <= 72) {
-    // LDS offsets of the four taps (clamped like the global ones, relative to the window)
-    const int xa = min(max(t.x0, 0), Ws - 1) - ax0, xb = min(max(t.x0 + 1, 0), Ws - 1) - ax0;
-    const int ya = min(max(t.y0, 0), Hs - 1) - by0, yb = min(max(t.y0 + 1, 0), Hs - 1) - by0;
-    // taps of pixels without any valid tap may point outside the window: clamp (their weight is unused)
-    const int cxa = min(max(xa, 0), 71), cxb = min(max(xb, 0), 71);
-    const int cya = min(max(ya, 0), HMAX - 1), cyb = min(max(yb, 0), HMAX - 1);
-    if (aw <= 48)
-      run<12, CCH, TS>(win, sp, op, p, inside, C, ss, os, Ws, ax0, by0, bh, cya * 48 + cxa, cya * 48 + cxb, cyb * 48 + cxa,
-              cyb * 48 + cxb);
-    else
-      run<18, CCH, TS>(win, sp, op, p, inside, C, ss, os, Ws, ax0, by0, bh, cya * 72 + cxa, cya * 72 + cxb, cyb * 72 + cxa,
-              cyb * 72 + cxb);
+  if (wd.fits) {
+    run<CCH, TS>(win, sp, op, p, inside, C, ss, os, Ws, wd);
     return;
   }
   if (!inside) return;
-  if (empty) {
+  if (wd.empty) {
     for (int c = blockIdx.y; c < C; c += gridDim.y) op[(long)c * os] = 0.f;
     return;
   }
@@ -239,13 +271,8 @@ __global__ __launch_bounds__(256) void warp_fwd_kernel(const TS* __restrict__ sr
     for (int u = 0; u < U; ++u)
       asm volatile("" : "+v"(a[u][0]), "+v"(a[u][1]), "+v"(a[u][2]), "+v"(a[u][3]));  // loads may not be predicated away
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float r = p.ok[0] ? a[u][0] * p.w[0] : 0.f;
-      r = p.ok[1] ? fmaf(a[u][1], p.w[1], r) : r;
-      r = p.ok[2] ? fmaf(a[u][2], p.w[2], r) : r;
-      r = p.ok[3] ? fmaf(a[u][3], p.w[3], r) : r;
-      if (c0 + u < C) op[(long)(c0 + u) * os] = r;
-    }
+    for (int u = 0; u < U; ++u)
+      if (c0 + u < C) op[(long)(c0 + u) * os] = tap_blend(p, a[u]);
   }
 }
 
@@ -268,7 +295,7 @@ __global__ __launch_bounds__(256) void level_warp_fwd_kernel(const float* __rest
                                                              int C, int H, int W, long fbs, int pad, int align, int norm,
                                                              int up_align) {
   using namespace fwd_win;
-  __shared__ __attribute__((aligned(16))) float win[CCH * HMAX * 72];
+  __shared__ __attribute__((aligned(16))) float win[CCH * HMAX * WMAX];
   __shared__ int red[4][NT / 64];
   __shared__ int box[4];
   __shared__ double dscratch[4 * (NT / 64)];
@@ -277,7 +304,6 @@ __global__ __launch_bounds__(256) void level_warp_fwd_kernel(const float* __rest
   if (!af_tile_of_block(ntx, nty, nimg, btx, bty, b)) return;
   const int x = btx * TX + (int)(threadIdx.x & 31), y = bty * TY + (int)(threadIdx.x >> 5);
   const bool inside = x < W && y < H;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int Hs = H, Ws = W;
   Taps t = no_taps();
   if (inside) {
@@ -308,47 +334,15 @@ __global__ __launch_bounds__(256) void level_warp_fwd_kernel(const float* __rest
     t = make_taps((float)x, (float)y, u, v, H, W, Hs, Ws, pad, align != 0, norm);
   }
   const TapPlan p = plan_taps(t, Hs, Ws);
-  const bool any = (t.vx0 || t.vx1) && (t.vy0 || t.vy1);
-  int lo_x = any ? t.x0 + (t.vx0 ? 0 : 1) : 0x7fffffff, hi_x = any ? t.x0 + (t.vx1 ? 1 : 0) : -0x7fffffff;
-  int lo_y = any ? t.y0 + (t.vy0 ? 0 : 1) : 0x7fffffff, hi_y = any ? t.y0 + (t.vy1 ? 1 : 0) : -0x7fffffff;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo_x = min(lo_x, __shfl_xor(lo_x, off, 64));
-    lo_y = min(lo_y, __shfl_xor(lo_y, off, 64));
-    hi_x = max(hi_x, __shfl_xor(hi_x, off, 64));
-    hi_y = max(hi_y, __shfl_xor(hi_y, off, 64));
-  }
-  if (lane == 0) red[0][wave] = lo_x, red[1][wave] = lo_y, red[2][wave] = hi_x, red[3][wave] = hi_y;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int a = red[0][0], bb = red[1][0], c = red[2][0], d = red[3][0];
-    for (int w = 1; w < NT / 64; ++w)
-      a = min(a, red[0][w]), bb = min(bb, red[1][w]), c = max(c, red[2][w]), d = max(d, red[3][w]);
-    box[0] = a, box[1] = bb, box[2] = c, box[3] = d;
-  }
-  __syncthreads();
-  const int bx0 = box[0], by0 = box[1];
-  const int bh = box[3] - by0 + 1;
-  const int ax0 = bx0 & ~3;
-  const int aw = box[2] - ax0 + 1;
-  const bool empty = box[2] < bx0;
+  const SrcWindow wd = src_window(tile_bbox(t, red, box), t, Hs, Ws);
   const int ss = Hs * Ws, os = H * W;
   const float* sp = src + (long)b * C * ss;
   float* op = out + (long)b * C * os + (long)y * W + x;
   const float* x1p = x1 ? x1 + (long)b * C * os + (long)y * W + x : nullptr;  // null: the first map's moments come from elsewhere
   float mom[4] = {0.f, 0.f, 0.f, 0.f};
 
-  if (!empty && (Ws & 3) == 0 && bh <= HMAX && aw <= 72) {
-    const int xa = min(max(t.x0, 0), Ws - 1) - ax0, xb = min(max(t.x0 + 1, 0), Ws - 1) - ax0;
-    const int ya = min(max(t.y0, 0), Hs - 1) - by0, yb = min(max(t.y0 + 1, 0), Hs - 1) - by0;
-    const int cxa = min(max(xa, 0), 71), cxb = min(max(xb, 0), 71);
-    const int cya = min(max(ya, 0), HMAX - 1), cyb = min(max(yb, 0), HMAX - 1);
-    if (aw <= 48)
-      run<12, CCH, float, true>(win, sp, op, p, inside, C, ss, os, Ws, ax0, by0, bh, cya * 48 + cxa, cya * 48 + cxb,
-                                cyb * 48 + cxa, cyb * 48 + cxb, x1p, mom);
-    else
-      run<18, CCH, float, true>(win, sp, op, p, inside, C, ss, os, Ws, ax0, by0, bh, cya * 72 + cxa, cya * 72 + cxb,
-                                cyb * 72 + cxa, cyb * 72 + cxb, x1p, mom);
+  if (wd.fits) {
+    run<CCH, float, true>(win, sp, op, p, inside, C, ss, os, Ws, wd, x1p, mom);
   } else if (inside) {
     // no tap of the tile inside the source (zeros out), or a window too large / unaligned rows (direct gathers)
     for (int c = blockIdx.y * CCH; c < C; c += gridDim.y * CCH) {
@@ -356,13 +350,10 @@ __global__ __launch_bounds__(256) void level_warp_fwd_kernel(const float* __rest
       for (int u = 0; u < CCH; ++u) {
         if (c + u >= C) continue;
         float r = 0.f;
-        if (!empty) {
+        if (!wd.empty) {
           const float* s = sp + (long)(c + u) * ss;
-          const float a0 = s[p.o[0]], a1 = s[p.o[1]], a2 = s[p.o[2]], a3 = s[p.o[3]];
-          r = p.ok[0] ? a0 * p.w[0] : 0.f;
-          r = p.ok[1] ? fmaf(a1, p.w[1], r) : r;
-          r = p.ok[2] ? fmaf(a2, p.w[2], r) : r;
-          r = p.ok[3] ? fmaf(a3, p.w[3], r) : r;
+          const float a[4] = {s[p.o[0]], s[p.o[1]], s[p.o[2]], s[p.o[3]]};
+          r = tap_blend(p, a);
         }
         op[(long)(c + u) * os] = r;
         const float xv = x1p ? x1p[(long)(c + u) * os] : 0.f;
@@ -380,46 +371,32 @@ __global__ __launch_bounds__(256) void level_warp_fwd_kernel(const float* __rest
   }
 }
 
-// Shared prologue of the tile kernels: bounding box of the valid taps of the workgroup's 256 pixels.
-struct TileBox {
-  int x0, y0, x1, y1;  // inclusive; empty when x1 < x0
-};
-__device__ __forceinline__ TileBox tile_bbox(const Taps& t, int (*red)[4], int* box) {
-  const bool any = (t.vx0 || t.vx1) && (t.vy0 || t.vy1);
-  int lo_x = any ? t.x0 + (t.vx0 ? 0 : 1) : 0x7fffffff, hi_x = any ? t.x0 + (t.vx1 ? 1 : 0) : -0x7fffffff;
-  int lo_y = any ? t.y0 + (t.vy0 ? 0 : 1) : 0x7fffffff, hi_y = any ? t.y0 + (t.vy1 ? 1 : 0) : -0x7fffffff;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo_x = min(lo_x, __shfl_xor(lo_x, off, 64));
-    lo_y = min(lo_y, __shfl_xor(lo_y, off, 64));
-    hi_x = max(hi_x, __shfl_xor(hi_x, off, 64));
-    hi_y = max(hi_y, __shfl_xor(hi_y, off, 64));
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) red[0][wave] = lo_x, red[1][wave] = lo_y, red[2][wave] = hi_x, red[3][wave] = hi_y;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int a = red[0][0], bb = red[1][0], c = red[2][0], d = red[3][0];
-    for (int w = 1; w < 4; ++w) a = min(a, red[0][w]), bb = min(bb, red[1][w]), c = max(c, red[2][w]), d = max(d, red[3][w]);
-    box[0] = a, box[1] = bb, box[2] = c, box[3] = d;
-  }
-  __syncthreads();
-  TileBox r;
-  r.x0 = box[0], r.y0 = box[1], r.x1 = box[2], r.y1 = box[3];
-  return r;
+// The gather form of d/d src (inv_gather::gather_kernel, below) and the flow-gradient role partition the (target p,
+// source q) pairs between them: the gather kernel writes, per source pixel q, qinfo[q] = its window centre (13 + 13 bits,
+// biased by 4096) + bit 30 = "q is left to the atomics", and BOTH sides decide with `taken`.  This is the definition.
+namespace inv_gather {
+constexpr int TX = 32, TY = 8, NT = 256, M = 3, RW = 48, RH = 16, RMAX = RW * RH, K = 8, CCH = 4;
+constexpr int QFLAG = 1 << 30;
+__device__ __forceinline__ int pack_q(int cx, int cy, bool flag) {  // cx, cy in [-4096, 4095] after the clamp below
+  return ((cx + 4096) & 0x1fff) | (((cy + 4096) & 0x1fff) << 13) | (flag ? QFLAG : 0);
 }
+__device__ __forceinline__ void unpack_q(int v, int& cx, int& cy, bool& flag) {
+  cx = (v & 0x1fff) - 4096, cy = ((v >> 13) & 0x1fff) - 4096, flag = (v & QFLAG) != 0;
+}
+// does the gather kernel take the pair (target p, source q)?  (the ONE predicate both kernels use)
+__device__ __forceinline__ bool taken(int qinfo, int px, int py) {
+  int cx, cy;
+  bool flag;
+  unpack_q(qinfo, cx, cy, flag);
+  return !flag && abs(px - cx) <= M && abs(py - cy) <= M;
+}
+}  // namespace inv_gather
 
 // ------------------------------------------------------------------------------------------------
 // d loss / d flow of the warp: per pixel  sum_c gout_c * (bilinear corner differences of src_c), times
 // d coord / d flow.  Same tile / LDS source-window structure as the forward kernel; this is the whole
 // backward of the loss-side image warps (their source is detached, losses/uflow_loss.py:31,34).
 // ------------------------------------------------------------------------------------------------
-// (inverse-window gather of d/d src, inv_gather below: does that kernel take the pair (target p, source q)?  qinfo = window
-// centre of q (13 + 13 bits, biased by 4096) + bit 30 = "q is left to the atomics")
-__device__ __forceinline__ bool af_gather_takes(int qinfo, int px, int py, int m) {
-  const int cx = (qinfo & 0x1fff) - 4096, cy = ((qinfo >> 13) & 0x1fff) - 4096;
-  return !(qinfo & (1 << 30)) && abs(px - cx) <= m && abs(py - cy) <= m;
-}
 
 namespace flow_grad {
 using fwd_win::HMAX;
@@ -447,19 +424,21 @@ __device__ __forceinline__ float norm_bwd_apply(const NormBwd& nb, float g, floa
   return fmaf(nb.rf, g, -nb.cg) - nb.cq * (x - c);
 }
 
-template <int WQ, int CCH, typename TS, bool NB = false, bool FIX = false>
-__device__ __forceinline__ void run(float* __restrict__ win, const TS* __restrict__ sp,
-                                    const float* __restrict__ gop, const TapPlan& p, const Taps& t, bool inside, int C,
-                                    int ss, int os, int Ws, int ax0, int by0, int bh, int l0, int l1, int l2, int l3,
-                                    float& gix, float& giy, const NormBwd* nb = nullptr,
-                                    const float* __restrict__ g1p = nullptr, const float* __restrict__ gdp = nullptr,
-                                    const float* __restrict__ x1p = nullptr, float* __restrict__ d1p = nullptr,
-                                    float* __restrict__ fixp = nullptr, unsigned fixmask = 0u) {
-  // fixp / fixmask (level backward with the gather form of d/d src): taps of this pixel that the gather kernel did NOT
-  // take (bit k of fixmask) are added to d/d src here, with float atomics -- fixp = that tensor at this sample
+// x, the warped value, summed again from the taps the kernel holds (v from tap_select: a tap outside the source is a zero term)
+__device__ __forceinline__ float warped_value(const TapPlan& p, const float (&v)[4]) {
+  return fmaf(v[3], p.w[3], fmaf(v[2], p.w[2], fmaf(v[1], p.w[1], v[0] * p.w[0])));
+}
+
+template <int WQ, int CCH, typename TS, bool NB, bool FIX>
+__device__ __forceinline__ void run_pitch(float* __restrict__ win, const TS* __restrict__ sp,
+                                          const float* __restrict__ gop, const TapPlan& p, const Taps& t, bool inside,
+                                          int C, int ss, int os, int Ws, const fwd_win::SrcWindow& wd, float& gix,
+                                          float& giy, const NormBwd* nb, const float* __restrict__ g1p,
+                                          const float* __restrict__ gdp, const float* __restrict__ x1p,
+                                          float* __restrict__ d1p, float* __restrict__ fixp, unsigned fixmask) {
   constexpr int WP = 4 * WQ;
   using fwd_win::WindowPlan;
-  const WindowPlan<WQ> pl = fwd_win::window_plan<WQ>(Ws, ax0, by0, bh);
+  const WindowPlan<WQ> pl = fwd_win::window_plan<WQ>(Ws, wd.ax0, wd.by0, wd.bh);
   float4 v[CCH][WindowPlan<WQ>::ITER];
   float gn[CCH];  // the next chunk's output gradients travel with its window
   float an[CCH], xn[CCH];  // NB: first map's gradient (both parts added) and value
@@ -499,15 +478,13 @@ __device__ __forceinline__ void run(float* __restrict__ win, const TS* __restric
 #pragma unroll
     for (int c = 0; c < CCH; ++c) {
       const float* w = win + c * HMAX * WP;
-      const float nw = p.ok[0] ? w[l0] : 0.f, ne = p.ok[1] ? w[l1] : 0.f;
-      const float sw = p.ok[2] ? w[l2] : 0.f, se = p.ok[3] ? w[l3] : 0.f;
+      float s[4], sx, sy;
+      tap_select(p, w, wd.l, s);
       float gc = g[c];
-      if (NB) {
-        const float xw = fmaf(se, p.w[3], fmaf(sw, p.w[2], fmaf(ne, p.w[1], nw * p.w[0])));
-        gc = norm_bwd_apply(*nb, gc, xw, nb->c2);
-      }
-      gix = fmaf(gc, (ne - nw) * t.wy0 + (se - sw) * t.wy1, gix);
-      giy = fmaf(gc, (sw - nw) * t.wx0 + (se - ne) * t.wx1, giy);
+      if (NB) gc = norm_bwd_apply(*nb, gc, warped_value(p, s), nb->c2);
+      tap_corner_grad(t, s, sx, sy);
+      gix = fmaf(gc, sx, gix);
+      giy = fmaf(gc, sy, giy);
       if (NB && FIX && fixmask && c0 + c < C) {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -517,11 +494,52 @@ __device__ __forceinline__ void run(float* __restrict__ win, const TS* __restric
     __syncthreads();
   }
 }
+// the staged path of a tile whose window fits (wd.fits): all threads of the workgroup call.
+// fixp / fixmask (level backward with the gather form of d/d src): taps of this pixel that the gather kernel did NOT
+// take (bit k of fixmask) are added to d/d src here, with float atomics -- fixp = that tensor at this sample
+template <int CCH, typename TS, bool NB = false, bool FIX = false>
+__device__ __forceinline__ void run(float* __restrict__ win, const TS* __restrict__ sp, const float* __restrict__ gop,
+                                    const TapPlan& p, const Taps& t, bool inside, int C, int ss, int os, int Ws,
+                                    const fwd_win::SrcWindow& wd, float& gix, float& giy, const NormBwd* nb = nullptr,
+                                    const float* __restrict__ g1p = nullptr, const float* __restrict__ gdp = nullptr,
+                                    const float* __restrict__ x1p = nullptr, float* __restrict__ d1p = nullptr,
+                                    float* __restrict__ fixp = nullptr, unsigned fixmask = 0u) {
+  if (wd.wq == fwd_win::WQ_NARROW)
+    run_pitch<fwd_win::WQ_NARROW, CCH, TS, NB, FIX>(win, sp, gop, p, t, inside, C, ss, os, Ws, wd, gix, giy, nb, g1p, gdp, x1p,
+                                                    d1p, fixp, fixmask);
+  else
+    run_pitch<fwd_win::WQ_WIDE, CCH, TS, NB, FIX>(win, sp, gop, p, t, inside, C, ss, os, Ws, wd, gix, giy, nb, g1p, gdp, x1p,
+                                                  d1p, fixp, fixmask);
+}
+
+// Way out of the flow-gradient kernels, at the thread's pixel (o = y * W + x in sample b, os = H * W).
+// total: d loss / d coordinate times d coordinate / d flow, plus -- in the first workgroup of a channel split --
+// add1 / add2 (nullable): further gradients of the same flow tensor (sample b at add1 + b * add1_bs resp. add2 + b * 2 * H * W):
+// the level backward folds the gradient the decoder's concatenation and the residual sum return for the upsampled flow
+// in here instead of two ATen add passes.
+__device__ __forceinline__ void total(float gix, float giy, const Taps& t, int b, long o, int os,
+                                      const float* __restrict__ add1, long add1_bs, const float* __restrict__ add2,
+                                      float& rx, float& ry) {
+  rx = gix * t.dx, ry = giy * t.dy;
+  if (blockIdx.y == 0) {
+    if (add1) rx += add1[(long)b * add1_bs + o], ry += add1[(long)b * add1_bs + os + o];
+    if (add2) rx += add2[(long)b * 2 * os + o], ry += add2[(long)b * 2 * os + os + o];
+  }
+}
+// ... and into gflow (gf = the pixel's x component): one workgroup per tile stores, a channel-split launch adds its
+// partial sums into the pre-zeroed tensor
+__device__ __forceinline__ void store(float* __restrict__ gf, int os, float rx, float ry) {
+  if (gridDim.y == 1) {
+    gf[0] = rx;
+    gf[os] = ry;
+  } else {
+    atomicAdd(gf, rx);
+    atomicAdd(gf + os, ry);
+  }
+}
 }  // namespace flow_grad
 
-// add1 / add2 (nullable): further gradients of the same flow tensor that are added on the way out (sample b at
-// add1 + b * add1_bs resp. add2 + b * 2 * H * W) -- the level backward folds the gradient the decoder's concatenation
-// and the residual sum return for the upsampled flow in here instead of two ATen add passes.
+// add1 / add2: see flow_grad::total
 template <int CCH, typename TS = float>
 __global__ __launch_bounds__(256) void warp_bwd_flow_kernel(const float* __restrict__ gout,
                                                             const TS* __restrict__ src,
@@ -531,7 +549,7 @@ __global__ __launch_bounds__(256) void warp_bwd_flow_kernel(const float* __restr
                                                             const float* __restrict__ add1 = nullptr, long add1_bs = 0,
                                                             const float* __restrict__ add2 = nullptr) {
   using namespace fwd_win;
-  __shared__ __attribute__((aligned(16))) float win[CCH * HMAX * 72];
+  __shared__ __attribute__((aligned(16))) float win[CCH * HMAX * WMAX];
   __shared__ int red[4][4];
   __shared__ int box[4];
   int btx, bty, b;
@@ -544,50 +562,31 @@ __global__ __launch_bounds__(256) void warp_bwd_flow_kernel(const float* __restr
     t = make_taps((float)x, (float)y, fb[0], fb[(long)H * W], H, W, Hs, Ws, pad, align != 0, norm);
   }
   const TapPlan p = plan_taps(t, Hs, Ws);
-  const TileBox bb = tile_bbox(t, red, box);
-  const int bh = bb.y1 - bb.y0 + 1, ax0 = bb.x0 & ~3, aw = bb.x1 - ax0 + 1;
-  const bool empty = bb.x1 < bb.x0;
+  const SrcWindow wd = src_window(tile_bbox(t, red, box), t, Hs, Ws);
   const int ss = Hs * Ws, os = H * W;
   const TS* sp = src + (long)b * C * ss;
   const float* gop = gout + (long)b * C * os + (long)y * W + x;
   float gix = 0.f, giy = 0.f;
-  if (!empty && (Ws & 3) == 0 && bh <= HMAX && aw <= 72) {
-    const int xa = min(max(t.x0, 0), Ws - 1) - ax0, xb = min(max(t.x0 + 1, 0), Ws - 1) - ax0;
-    const int ya = min(max(t.y0, 0), Hs - 1) - bb.y0, yb = min(max(t.y0 + 1, 0), Hs - 1) - bb.y0;
-    const int cxa = min(max(xa, 0), 71), cxb = min(max(xb, 0), 71);
-    const int cya = min(max(ya, 0), HMAX - 1), cyb = min(max(yb, 0), HMAX - 1);
-    if (aw <= 48)
-      flow_grad::run<12, CCH, TS>(win, sp, gop, p, t, inside, C, ss, os, Ws, ax0, bb.y0, bh, cya * 48 + cxa, cya * 48 + cxb,
-                         cyb * 48 + cxa, cyb * 48 + cxb, gix, giy);
-    else
-      flow_grad::run<18, CCH, TS>(win, sp, gop, p, t, inside, C, ss, os, Ws, ax0, bb.y0, bh, cya * 72 + cxa, cya * 72 + cxb,
-                         cyb * 72 + cxa, cyb * 72 + cxb, gix, giy);
-  } else if (inside && !empty) {
+  if (wd.fits) {
+    flow_grad::run<CCH, TS>(win, sp, gop, p, t, inside, C, ss, os, Ws, wd, gix, giy);
+  } else if (inside && !wd.empty) {
     for (int c = blockIdx.y; c < C; c += gridDim.y) {  // direct gathers (window too large or unaligned rows)
       const float g = gop[(long)c * os];
       const TS* s = sp + (long)c * ss;
-      float a0 = to_f32(s[p.o[0]]), a1 = to_f32(s[p.o[1]]), a2 = to_f32(s[p.o[2]]), a3 = to_f32(s[p.o[3]]);
-      asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));
-      const float nw = p.ok[0] ? a0 : 0.f, ne = p.ok[1] ? a1 : 0.f, sw = p.ok[2] ? a2 : 0.f, se = p.ok[3] ? a3 : 0.f;
-      gix = fmaf(g, (ne - nw) * t.wy0 + (se - sw) * t.wy1, gix);
-      giy = fmaf(g, (sw - nw) * t.wx0 + (se - ne) * t.wx1, giy);
+      float a[4] = {to_f32(s[p.o[0]]), to_f32(s[p.o[1]]), to_f32(s[p.o[2]]), to_f32(s[p.o[3]])};
+      asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]));
+      float sx, sy;
+      tap_select(p, a, a);
+      tap_corner_grad(t, a, sx, sy);
+      gix = fmaf(g, sx, gix);
+      giy = fmaf(g, sy, giy);
     }
   }
   if (inside) {
-    float* gf = gflow + (long)b * 2 * os + (long)y * W + x;
-    float rx = gix * t.dx, ry = giy * t.dy;
-    if (blockIdx.y == 0) {
-      const long o = (long)y * W + x;
-      if (add1) rx += add1[(long)b * add1_bs + o], ry += add1[(long)b * add1_bs + os + o];
-      if (add2) rx += add2[(long)b * 2 * os + o], ry += add2[(long)b * 2 * os + os + o];
-    }
-    if (gridDim.y == 1) {
-      gf[0] = rx;
-      gf[os] = ry;
-    } else {  // channel-split launch: partial sums meet in the pre-zeroed gflow
-      atomicAdd(gf, rx);
-      atomicAdd(gf + os, ry);
-    }
+    const long o = (long)y * W + x;
+    float rx, ry;
+    flow_grad::total(gix, giy, t, b, o, os, add1, add1_bs, add2, rx, ry);
+    flow_grad::store(gflow + (long)b * 2 * os + o, os, rx, ry);
   }
 }
 
@@ -617,7 +616,7 @@ __device__ __forceinline__ void level_warp_bwd_flow_body(const float* __restrict
                                                          unsigned bx) {
   using namespace fwd_win;
   constexpr int CCH = 2;
-  __shared__ __attribute__((aligned(16))) float win[CCH * HMAX * 72];
+  __shared__ __attribute__((aligned(16))) float win[CCH * HMAX * WMAX];
   __shared__ int red[4][4];
   __shared__ int box[4];
   int btx, bty, b;
@@ -634,9 +633,7 @@ __device__ __forceinline__ void level_warp_bwd_flow_body(const float* __restrict
     t = make_taps((float)x, (float)y, fb[0], fb[(long)H * W], H, W, Hs, Ws, pad, align != 0, norm);
   }
   const TapPlan p = plan_taps(t, Hs, Ws);
-  const TileBox bb = tile_bbox(t, red, box);
-  const int bh = bb.y1 - bb.y0 + 1, ax0 = bb.x0 & ~3, aw = bb.x1 - ax0 + 1;
-  const bool empty = bb.x1 < bb.x0;
+  const SrcWindow wd = src_window(tile_bbox(t, red, box), t, Hs, Ws);
   const float* sp = src + (long)b * C * ss;
   const long po = (long)b * C * os + (long)y * W + x;
   const float* gop = g2n + po;
@@ -652,35 +649,26 @@ __device__ __forceinline__ void level_warp_bwd_flow_body(const float* __restrict
     const int* qi = la.qinfo + (long)b * ss;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (p.ok[k] && !af_gather_takes(qi[p.o[k]], x, y, 3)) fixmask |= 1u << k;
+      if (p.ok[k] && !inv_gather::taken(qi[p.o[k]], x, y)) fixmask |= 1u << k;
     fixp = la.gfix + (long)b * C * ss;
   }
-  if (!empty && (Ws & 3) == 0 && bh <= HMAX && aw <= 72) {
-    const int xa = min(max(t.x0, 0), Ws - 1) - ax0, xb = min(max(t.x0 + 1, 0), Ws - 1) - ax0;
-    const int ya = min(max(t.y0, 0), Hs - 1) - bb.y0, yb = min(max(t.y0 + 1, 0), Hs - 1) - bb.y0;
-    const int cxa = min(max(xa, 0), 71), cxb = min(max(xb, 0), 71);
-    const int cya = min(max(ya, 0), HMAX - 1), cyb = min(max(yb, 0), HMAX - 1);
-    if (aw <= 48)
-      flow_grad::run<12, CCH, float, true, FIX>(win, sp, gop, p, t, inside, C, ss, os, Ws, ax0, bb.y0, bh, cya * 48 + cxa,
-                                                cya * 48 + cxb, cyb * 48 + cxa, cyb * 48 + cxb, gix, giy, &nb, g1p, gdp, x1p, d1p,
-                                                fixp, fixmask);
-    else
-      flow_grad::run<18, CCH, float, true, FIX>(win, sp, gop, p, t, inside, C, ss, os, Ws, ax0, bb.y0, bh, cya * 72 + cxa,
-                                                cya * 72 + cxb, cyb * 72 + cxa, cyb * 72 + cxb, gix, giy, &nb, g1p, gdp, x1p, d1p,
-                                                fixp, fixmask);
+  if (wd.fits) {
+    flow_grad::run<CCH, float, true, FIX>(win, sp, gop, p, t, inside, C, ss, os, Ws, wd, gix, giy, &nb, g1p, gdp, x1p, d1p,
+                                          fixp, fixmask);
   } else if (inside) {
     for (int c = blockIdx.y; c < C; c += gridDim.y) {  // no tap inside the source, or a window too large: direct gathers
       const float gsum = g1p[(long)c * os] + (gdp ? gdp[(long)c * os] : 0.f);
       d1p[(long)c * os] = flow_grad::norm_bwd_apply(nb, gsum, x1p[(long)c * os], nb.c1);
-      if (empty) continue;
+      if (wd.empty) continue;
       const float* s = sp + (long)c * ss;
-      float a0 = s[p.o[0]], a1 = s[p.o[1]], a2 = s[p.o[2]], a3 = s[p.o[3]];
-      asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));
-      const float nw = p.ok[0] ? a0 : 0.f, ne = p.ok[1] ? a1 : 0.f, sw = p.ok[2] ? a2 : 0.f, se = p.ok[3] ? a3 : 0.f;
-      const float xw = fmaf(se, p.w[3], fmaf(sw, p.w[2], fmaf(ne, p.w[1], nw * p.w[0])));
-      const float g = flow_grad::norm_bwd_apply(nb, gop[(long)c * os], xw, nb.c2);
-      gix = fmaf(g, (ne - nw) * t.wy0 + (se - sw) * t.wy1, gix);
-      giy = fmaf(g, (sw - nw) * t.wx0 + (se - ne) * t.wx1, giy);
+      float a[4] = {s[p.o[0]], s[p.o[1]], s[p.o[2]], s[p.o[3]]};
+      asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]));
+      float sx, sy;
+      tap_select(p, a, a);
+      const float g = flow_grad::norm_bwd_apply(nb, gop[(long)c * os], flow_grad::warped_value(p, a), nb.c2);
+      tap_corner_grad(t, a, sx, sy);
+      gix = fmaf(g, sx, gix);
+      giy = fmaf(g, sy, giy);
       if (FIX && fixmask) {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -689,13 +677,9 @@ __device__ __forceinline__ void level_warp_bwd_flow_body(const float* __restrict
     }
   }
   if (inside) {
-    float* gf = gflow + (long)b * 2 * os + (long)y * W + x;
-    float rx = gix * t.dx, ry = giy * t.dy;
-    if (blockIdx.y == 0) {
-      const long o = (long)y * W + x;
-      if (add1) rx += add1[(long)b * add1_bs + o], ry += add1[(long)b * add1_bs + os + o];
-      if (add2) rx += add2[(long)b * 2 * os + o], ry += add2[(long)b * 2 * os + os + o];
-    }
+    const long o = (long)y * W + x;
+    float rx, ry;
+    flow_grad::total(gix, giy, t, b, o, os, add1, add1_bs, add2, rx, ry);
     if (la.gcoarse) {
       const int Hc = H / 2, Wc = W / 2;
       int xa, xb, ya, yb;
@@ -709,12 +693,8 @@ __device__ __forceinline__ void level_warp_bwd_flow_body(const float* __restrict
       atomicAdd(gc + yb * Wc + xa, wy1 * wx0 * rx), atomicAdd(gc + yb * Wc + xb, wy1 * wx1 * rx);
       atomicAdd(gc + cs + ya * Wc + xa, wy0 * wx0 * ry), atomicAdd(gc + cs + ya * Wc + xb, wy0 * wx1 * ry);
       atomicAdd(gc + cs + yb * Wc + xa, wy1 * wx0 * ry), atomicAdd(gc + cs + yb * Wc + xb, wy1 * wx1 * ry);
-    } else if (gridDim.y == 1) {
-      gf[0] = rx;
-      gf[os] = ry;
     } else {
-      atomicAdd(gf, rx);
-      atomicAdd(gf + os, ry);
+      flow_grad::store(gflow + (long)b * 2 * os + o, os, rx, ry);
     }
   }
 }
@@ -1151,22 +1131,7 @@ __global__ __launch_bounds__(256) void level_warp_bwd_both_kernel(const float* _
 // predicate on both sides: the pairs are partitioned, none is lost or counted twice).  On the flows of a training step
 // those atomics are rare.
 // ------------------------------------------------------------------------------------------------
-namespace inv_gather {
-constexpr int TX = 32, TY = 8, NT = 256, M = 3, RW = 48, RH = 16, RMAX = RW * RH, K = 8, CCH = 4;
-constexpr int QFLAG = 1 << 30;
-__device__ __forceinline__ int pack_q(int cx, int cy, bool flag) {  // cx, cy in [-4096, 4095] after the clamp below
-  return ((cx + 4096) & 0x1fff) | (((cy + 4096) & 0x1fff) << 13) | (flag ? QFLAG : 0);
-}
-__device__ __forceinline__ void unpack_q(int v, int& cx, int& cy, bool& flag) {
-  cx = (v & 0x1fff) - 4096, cy = ((v >> 13) & 0x1fff) - 4096, flag = (v & QFLAG) != 0;
-}
-// does the gather kernel take the pair (target p, source q)?  (the ONE predicate both kernels use)
-__device__ __forceinline__ bool taken(int qinfo, int px, int py) {
-  int cx, cy;
-  bool flag;
-  unpack_q(qinfo, cx, cy, flag);
-  return !flag && abs(px - cx) <= M && abs(py - cy) <= M;
-}
+namespace inv_gather {  // (constants and the predicate: above flow_grad)
 
 __global__ __launch_bounds__(NT) void gather_kernel(const float* __restrict__ g2n, const float* __restrict__ x2w,
                                                     const float* __restrict__ flow, float* __restrict__ gsrc,
@@ -1198,23 +1163,10 @@ __global__ __launch_bounds__(NT) void gather_kernel(const float* __restrict__ g2
   int lo_x = bad ? 0x7fffffff : max(cx - M, 0), hi_x = bad ? -0x7fffffff : min(cx + M, W - 1);
   int lo_y = bad ? 0x7fffffff : max(cy - M, 0), hi_y = bad ? -0x7fffffff : min(cy + M, H - 1);
   if (!bad && (lo_x > hi_x || lo_y > hi_y)) lo_x = 0x7fffffff, hi_x = -0x7fffffff, lo_y = 0x7fffffff, hi_y = -0x7fffffff;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo_x = min(lo_x, __shfl_xor(lo_x, off, 64)), lo_y = min(lo_y, __shfl_xor(lo_y, off, 64));
-    hi_x = max(hi_x, __shfl_xor(hi_x, off, 64)), hi_y = max(hi_y, __shfl_xor(hi_y, off, 64));
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) red[0][wave] = lo_x, red[1][wave] = lo_y, red[2][wave] = hi_x, red[3][wave] = hi_y;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int a = red[0][0], bb = red[1][0], c = red[2][0], d = red[3][0];
-    for (int w = 1; w < 4; ++w) a = min(a, red[0][w]), bb = min(bb, red[1][w]), c = max(c, red[2][w]), d = max(d, red[3][w]);
-    box[0] = a, box[1] = bb, box[2] = c, box[3] = d;
-  }
-  __syncthreads();
-  const int rx0 = box[0], ry0 = box[1];
-  const int rw = box[2] - rx0 + 1, rh = box[3] - ry0 + 1;
-  const bool none = box[2] < rx0;                          // no pixel of the tile has a window inside the image
+  const TileBox rb = block_bbox(lo_x, lo_y, hi_x, hi_y, red, box);
+  const int rx0 = rb.x0, ry0 = rb.y0;
+  const int rw = rb.x1 - rx0 + 1, rh = rb.y1 - ry0 + 1;
+  const bool none = rb.x1 < rx0;                           // no pixel of the tile has a window inside the image
   const bool oversize = !none && (rw > RW || rh > RH);     // workgroup-uniform
   const int nr = (none || oversize) ? 0 : rw * rh;
   // taps of the targets in the box, once per workgroup
@@ -1400,24 +1352,10 @@ __global__ __launch_bounds__(256) void splat_kernel(const float* __restrict__ fl
       lo_x = min(lo_x, t.xi[k]), hi_x = max(hi_x, t.xi[k]);
       lo_y = min(lo_y, t.yi[k]), hi_y = max(hi_y, t.yi[k]);
     }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo_x = min(lo_x, __shfl_xor(lo_x, off, 64));
-    lo_y = min(lo_y, __shfl_xor(lo_y, off, 64));
-    hi_x = max(hi_x, __shfl_xor(hi_x, off, 64));
-    hi_y = max(hi_y, __shfl_xor(hi_y, off, 64));
-  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) red[0][wave] = lo_x, red[1][wave] = lo_y, red[2][wave] = hi_x, red[3][wave] = hi_y;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int a = red[0][0], bb = red[1][0], c = red[2][0], d = red[3][0];
-    for (int w = 1; w < 4; ++w) a = min(a, red[0][w]), bb = min(bb, red[1][w]), c = max(c, red[2][w]), d = max(d, red[3][w]);
-    box[0] = a, box[1] = bb, box[2] = c, box[3] = d;
-  }
-  __syncthreads();
-  const int bx0 = box[0], by0 = box[1], bw = box[2] - bx0 + 1, bh = box[3] - by0 + 1;
-  if (box[2] < bx0) return;  // nothing lands inside the image
+  const TileBox bb = block_bbox(lo_x, lo_y, hi_x, hi_y, red, box);
+  const int bx0 = bb.x0, by0 = bb.y0, bw = bb.x1 - bx0 + 1, bh = bb.y1 - by0 + 1;
+  if (bb.x1 < bx0) return;  // nothing lands inside the image
   float* ob = out + (long)b * H * W;
   if (bw > WMAX || bh > HMAX) {
 #pragma unroll
@@ -1488,20 +1426,63 @@ inline dim3 pixel_grid(int B, int H, int W, int bx) { return dim3(af_cdiv(W, bx)
 inline unsigned channel_split(long tiles, int C) { return af_channel_split(tiles, C); }
 inline int pick_bx(int W) { return W >= 192 ? 256 : (W >= 96 ? 128 : 64); }
 
+// the argument contract the four warp entry points share (p0 .. p2: the three pointers each of them requires)
+int warp_check_args(const void* p0, const void* p1, const void* p2, int B, int C, int Hs, int Ws, int H, int W,
+                    long flow_bstride, int pad_mode, int norm_mode) {
+  AF_REQUIRE_PTR(p0);
+  AF_REQUIRE_PTR(p1);
+  AF_REQUIRE_PTR(p2);
+  AF_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && Hs > 0 && Ws > 0, ARFLOW_ESHAPE);
+  AF_REQUIRE(B <= 65535 && H <= 65535, ARFLOW_ESHAPE);
+  AF_REQUIRE(flow_bstride >= 2L * H * W, ARFLOW_ESHAPE);
+  AF_REQUIRE(pad_mode == ARFLOW_PAD_ZEROS || pad_mode == ARFLOW_PAD_BORDER, ARFLOW_EPARAM);
+  AF_REQUIRE(norm_mode >= ARFLOW_NORM_ARFLOW && norm_mode <= ARFLOW_NORM_UFLOW_ABS, ARFLOW_EPARAM);
+  return ARFLOW_OK;
+}
+
+// Both gradients of the warp (either may be null); TS = the storage type of src.  add1 / add2: see flow_grad::total
+template <typename TS>
+int warp_bwd_launch(const float* gout, const TS* src, const float* flow, float* gsrc, float* gflow, int B, int C, int Hs,
+                    int Ws, int H, int W, long flow_bstride, int pad_mode, int align_corners, int norm_mode,
+                    const float* add1, long add1_bs, const float* add2, hipStream_t st) {
+  if (!gsrc && !gflow) return ARFLOW_OK;
+  if (gsrc) {
+    hipError_t e = hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)B * C * Hs * Ws, st);
+    if (e != hipSuccess) return af_hip_status(e);
+  }
+  const long tiles = (long)af_cdiv(W, 32) * af_cdiv(H, 8) * B;
+  const unsigned nsplit = channel_split(tiles, C);
+  const dim3 grid(af_grid_for_tiles(tiles), nsplit);
+  if (gsrc)  // (d/d src never reads src)
+    hipLaunchKernelGGL(lds_scatter::warp_bwd_src_kernel<false>, grid, dim3(256), 0, st, gout, flow, gsrc, B, C, Hs, Ws, H, W,
+                       flow_bstride, pad_mode, align_corners, norm_mode);
+  if (gsrc && gflow) AF_LAUNCH_CHECK();
+  if (gflow) {
+    if (nsplit > 1) {
+      hipError_t e = hipMemsetAsync(gflow, 0, sizeof(float) * (size_t)B * 2 * H * W, st);
+      if (e != hipSuccess) return af_hip_status(e);
+    }
+    if constexpr (std::is_same<TS, float>::value) {
+      if (C <= 3) {  // image warps of the losses: 3 channels per chunk (fp32 storage only: bf16 has the one instantiation)
+        hipLaunchKernelGGL(warp_bwd_flow_kernel<3>, grid, dim3(256), 0, st, gout, src, flow, gflow, B, C, Hs, Ws, H, W,
+                           flow_bstride, pad_mode, align_corners, norm_mode, add1, add1_bs, add2);
+        return af_launch_status();
+      }
+    }
+    hipLaunchKernelGGL((warp_bwd_flow_kernel<2, TS>), grid, dim3(256), 0, st, gout, src, flow, gflow, B, C, Hs, Ws, H, W,
+                       flow_bstride, pad_mode, align_corners, norm_mode, add1, add1_bs, add2);
+  }
+  return af_launch_status();
+}
+
 }  // namespace
 
 extern "C" int arflow_warp_fwd(const float* src, const float* flow, float* out, float* valid, int B, int C,
                                int Hs, int Ws, int H, int W, long flow_bstride, int pad_mode,
                                int align_corners, int norm_mode, arflow_stream_t stream) {
   af_clear_stale_error();
-  AF_REQUIRE_PTR(src);
-  AF_REQUIRE_PTR(flow);
-  AF_REQUIRE_PTR(out);
-  AF_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && Hs > 0 && Ws > 0, ARFLOW_ESHAPE);
-  AF_REQUIRE(B <= 65535 && H <= 65535, ARFLOW_ESHAPE);
-  AF_REQUIRE(flow_bstride >= 2L * H * W, ARFLOW_ESHAPE);
-  AF_REQUIRE(pad_mode == ARFLOW_PAD_ZEROS || pad_mode == ARFLOW_PAD_BORDER, ARFLOW_EPARAM);
-  AF_REQUIRE(norm_mode >= ARFLOW_NORM_ARFLOW && norm_mode <= ARFLOW_NORM_UFLOW_ABS, ARFLOW_EPARAM);
+  const int rc = warp_check_args(src, flow, out, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, norm_mode);
+  if (rc != ARFLOW_OK) return rc;
   const long tiles = (long)af_cdiv(W, 32) * af_cdiv(H, 8) * B;
   if (C <= 3)  // image warps of the losses: 3 channels per chunk (smaller LDS window, more workgroups per CU)
     hipLaunchKernelGGL(warp_fwd_kernel<3>, dim3(af_grid_for_tiles(tiles), 1), dim3(256), 0, (hipStream_t)stream, src, flow,
@@ -1569,34 +1550,12 @@ extern "C" int arflow_level_warp_fwd(const float* x1, const float* x2, const flo
                                   (hipStream_t)stream);
 }
 
-// internal launcher (also used by the level entry points, level.hip); add1 / add2: see warp_bwd_flow_kernel
+// internal launcher (also used by the level entry points, level.hip)
 int af_warp_bwd_launch(const float* gout, const float* src, const float* flow, float* gsrc, float* gflow, int B, int C,
                        int Hs, int Ws, int H, int W, long flow_bstride, int pad_mode, int align_corners, int norm_mode,
                        const float* add1, long add1_bs, const float* add2, hipStream_t st) {
-  if (!gsrc && !gflow) return ARFLOW_OK;
-  if (gsrc) {
-    hipError_t e = hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)B * C * Hs * Ws, st);
-    if (e != hipSuccess) return af_hip_status(e);
-  }
-  const long tiles = (long)af_cdiv(W, 32) * af_cdiv(H, 8) * B;
-  const unsigned nsplit = channel_split(tiles, C);
-  if (gsrc)
-    hipLaunchKernelGGL(lds_scatter::warp_bwd_src_kernel<false>, dim3(af_grid_for_tiles(tiles), nsplit), dim3(256), 0, st, gout,
-                       flow, gsrc, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, align_corners, norm_mode);
-  if (gsrc && gflow) AF_LAUNCH_CHECK();
-  if (gflow) {
-    if (nsplit > 1) {
-      hipError_t e = hipMemsetAsync(gflow, 0, sizeof(float) * (size_t)B * 2 * H * W, st);
-      if (e != hipSuccess) return af_hip_status(e);
-    }
-    if (C <= 3)
-      hipLaunchKernelGGL(warp_bwd_flow_kernel<3>, dim3(af_grid_for_tiles(tiles), nsplit), dim3(256), 0, st, gout, src, flow,
-                         gflow, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, align_corners, norm_mode, add1, add1_bs, add2);
-    else
-      hipLaunchKernelGGL(warp_bwd_flow_kernel<2>, dim3(af_grid_for_tiles(tiles), nsplit), dim3(256), 0, st, gout, src, flow,
-                         gflow, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, align_corners, norm_mode, add1, add1_bs, add2);
-  }
-  return af_launch_status();
+  return warp_bwd_launch<float>(gout, src, flow, gsrc, gflow, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, align_corners,
+                                norm_mode, add1, add1_bs, add2, st);
 }
 
 // level backward, warp part: the normalisation's backward folded into both warp-gradient kernels (no apply pass, the
@@ -1675,14 +1634,8 @@ extern "C" int arflow_warp_bwd(const float* gout, const float* src, const float*
                                float* gflow, int B, int C, int Hs, int Ws, int H, int W, long flow_bstride,
                                int pad_mode, int align_corners, int norm_mode, arflow_stream_t stream) {
   af_clear_stale_error();
-  AF_REQUIRE_PTR(gout);
-  AF_REQUIRE_PTR(src);
-  AF_REQUIRE_PTR(flow);
-  AF_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && Hs > 0 && Ws > 0, ARFLOW_ESHAPE);
-  AF_REQUIRE(B <= 65535 && H <= 65535, ARFLOW_ESHAPE);
-  AF_REQUIRE(flow_bstride >= 2L * H * W, ARFLOW_ESHAPE);
-  AF_REQUIRE(pad_mode == ARFLOW_PAD_ZEROS || pad_mode == ARFLOW_PAD_BORDER, ARFLOW_EPARAM);
-  AF_REQUIRE(norm_mode >= ARFLOW_NORM_ARFLOW && norm_mode <= ARFLOW_NORM_UFLOW_ABS, ARFLOW_EPARAM);
+  const int rc = warp_check_args(gout, src, flow, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, norm_mode);
+  if (rc != ARFLOW_OK) return rc;
   return af_warp_bwd_launch(gout, src, flow, gsrc, gflow, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, align_corners,
                             norm_mode, nullptr, 0, nullptr, (hipStream_t)stream);
 }
@@ -1766,14 +1719,8 @@ extern "C" int arflow_warp_fwd_bf16(const unsigned short* src, const float* flow
                                     int Hs, int Ws, int H, int W, long flow_bstride, int pad_mode, int align_corners,
                                     int norm_mode, arflow_stream_t stream) {
   af_clear_stale_error();
-  AF_REQUIRE_PTR(src);
-  AF_REQUIRE_PTR(flow);
-  AF_REQUIRE_PTR(out);
-  AF_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && Hs > 0 && Ws > 0, ARFLOW_ESHAPE);
-  AF_REQUIRE(B <= 65535 && H <= 65535, ARFLOW_ESHAPE);
-  AF_REQUIRE(flow_bstride >= 2L * H * W, ARFLOW_ESHAPE);
-  AF_REQUIRE(pad_mode == ARFLOW_PAD_ZEROS || pad_mode == ARFLOW_PAD_BORDER, ARFLOW_EPARAM);
-  AF_REQUIRE(norm_mode >= ARFLOW_NORM_ARFLOW && norm_mode <= ARFLOW_NORM_UFLOW_ABS, ARFLOW_EPARAM);
+  const int rc = warp_check_args(src, flow, out, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, norm_mode);
+  if (rc != ARFLOW_OK) return rc;
   const long tiles = (long)af_cdiv(W, 32) * af_cdiv(H, 8) * B;
   hipLaunchKernelGGL((warp_fwd_kernel<2, bf16_t>), dim3(af_grid_for_tiles(tiles), channel_split(tiles, C)), dim3(256), 0,
                      (hipStream_t)stream, src, flow, out, valid, B, C, Hs, Ws, H, W, flow_bstride, pad_mode,
@@ -1785,33 +1732,8 @@ extern "C" int arflow_warp_bwd_bf16(const float* gout, const unsigned short* src
                                     float* gflow, int B, int C, int Hs, int Ws, int H, int W, long flow_bstride,
                                     int pad_mode, int align_corners, int norm_mode, arflow_stream_t stream) {
   af_clear_stale_error();
-  AF_REQUIRE_PTR(gout);
-  AF_REQUIRE_PTR(src);
-  AF_REQUIRE_PTR(flow);
-  AF_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && Hs > 0 && Ws > 0, ARFLOW_ESHAPE);
-  AF_REQUIRE(B <= 65535 && H <= 65535, ARFLOW_ESHAPE);
-  AF_REQUIRE(flow_bstride >= 2L * H * W, ARFLOW_ESHAPE);
-  AF_REQUIRE(pad_mode == ARFLOW_PAD_ZEROS || pad_mode == ARFLOW_PAD_BORDER, ARFLOW_EPARAM);
-  AF_REQUIRE(norm_mode >= ARFLOW_NORM_ARFLOW && norm_mode <= ARFLOW_NORM_UFLOW_ABS, ARFLOW_EPARAM);
-  if (!gsrc && !gflow) return ARFLOW_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (gsrc) {
-    hipError_t e = hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)B * C * Hs * Ws, st);
-    if (e != hipSuccess) return af_hip_status(e);
-  }
-  const long tiles = (long)af_cdiv(W, 32) * af_cdiv(H, 8) * B;
-  const unsigned nsplit = channel_split(tiles, C);
-  if (gsrc)
-    hipLaunchKernelGGL(lds_scatter::warp_bwd_src_kernel<false>, dim3(af_grid_for_tiles(tiles), nsplit), dim3(256), 0, st, gout,
-                       flow, gsrc, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, align_corners, norm_mode);
-  if (gsrc && gflow) AF_LAUNCH_CHECK();
-  if (gflow) {
-    if (nsplit > 1) {
-      hipError_t e = hipMemsetAsync(gflow, 0, sizeof(float) * (size_t)B * 2 * H * W, st);
-      if (e != hipSuccess) return af_hip_status(e);
-    }
-    hipLaunchKernelGGL((warp_bwd_flow_kernel<2, bf16_t>), dim3(af_grid_for_tiles(tiles), nsplit), dim3(256), 0, st, gout,
-                       src, flow, gflow, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, align_corners, norm_mode);
-  }
-  return af_launch_status();
+  const int rc = warp_check_args(gout, src, flow, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, norm_mode);
+  if (rc != ARFLOW_OK) return rc;
+  return warp_bwd_launch<bf16_t>(gout, src, flow, gsrc, gflow, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, align_corners,
+                                 norm_mode, nullptr, 0, nullptr, (hipStream_t)stream);
 }

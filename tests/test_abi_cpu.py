@@ -60,6 +60,19 @@ def test_argument_errors_without_gpu(lib):
     assert lib.arflow_corr_sign_planes(32, 160, 4) == 3 and lib.arflow_corr_sign_planes(32, 10, 4) == 0
     assert lib.arflow_warp_fwd(one, one, one, None, 1, 1, 4, 4, 4, 4, 32, 7, 1, 0, None) == -1003
     assert lib.arflow_warp_fwd(one, one, one, None, 1, 1, 4, 4, 4, 4, 3, 0, 1, 0, None) == -1002
+    # the four warp entry points share one argument contract: the same fault gets the same code from each of them
+    good = dict(p0=one, p1=one, p2=one, B=1, C=1, Hs=4, Ws=4, H=4, W=4, fbs=32, pad=0, align=1, norm=0)
+    faults = [(dict(p0=None), -1001), (dict(p1=None), -1001), (dict(p2=None), -1001),  # null pointer
+              (dict(B=0), -1002), (dict(fbs=2 * 4 * 4 - 1), -1002),                    # B = 0, flow_bstride < 2*H*W
+              (dict(pad=7), -1003), (dict(norm=9), -1003)]                             # pad mode 7, norm mode 9
+    for change, want in faults:
+        a = dict(good, **change)
+        tail = (a['B'], a['C'], a['Hs'], a['Ws'], a['H'], a['W'], a['fbs'], a['pad'], a['align'], a['norm'], None)
+        ptrs = (a['p0'], a['p1'], a['p2'])
+        got = {n: getattr(lib, n)(*ptrs, *opt, *tail)  # fwd: (src, flow, out, valid); bwd: (gout, src, flow, gsrc, gflow)
+               for n, opt in (('arflow_warp_fwd', (None,)), ('arflow_warp_fwd_bf16', (None,)),
+                              ('arflow_warp_bwd', (one, one)), ('arflow_warp_bwd_bf16', (one, one)))}
+        assert set(got.values()) == {want}, (change, got)
     assert lib.arflow_census_fwd(one, one, None, one, None, None, 1, 8, 8, 17, None) == -1003  # radius 1..16
     assert lib.arflow_down4(one, one, 1, 6, 8, None) == -1002
     assert b'NULL' in lib.arflow_strerror(-1001)
