@@ -19,6 +19,10 @@ c_f = ctypes.c_float
 PROTOTYPES = {
     'arflow_abi_version': [],
     'arflow_take_stale_error': [],
+    'arflow_set_deterministic': [c_i],
+    'arflow_get_deterministic': [],
+    'arflow_flow_up_fwd': [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_flow_up_bwd': [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_profile_marker': [c_i, c_fp],
     'arflow_sums_rows': [c_i, c_i, c_i],
     'arflow_corr_fwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_fp],

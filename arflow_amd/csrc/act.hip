@@ -90,6 +90,47 @@ __global__ __launch_bounds__(NT) void bias_act_bwd_kernel(const float* gout, con
     if (threadIdx.x == 0) atomicAdd(gbias + c, s[0]);
   }
 }
+
+// Deterministic mode: gbias[c] = sum_{b,hw} gout * (y > 0 ? 1 : slope) by ONE workgroup of 1024 threads per channel.
+// Thread t adds, plane after plane (sample-major), the elements (float4 groups when VEC) t, t + 1024, ... in double, and the
+// 1024 partials meet in a fixed tree (lanes by shuffle, then the 16 waves in order): the order is a function of the indices
+// alone.  No scratch and no zero-fill; it re-reads gout and y (the elementwise pass has run with gbias = NULL) -- the
+// mode's price here.  (256 threads and one scalar load pair per trip took 8 ms per step over the feature extractor's layers.)
+constexpr int NTD = 1024;
+template <bool VEC>
+__global__ __launch_bounds__(NTD) void bias_grad_det_kernel(const float* __restrict__ gout, const float* __restrict__ y,
+                                                            float* __restrict__ gbias, int B, int C, long HW, float slope) {
+  __shared__ double red[NTD / 64];
+  const int c = blockIdx.x;
+  double s = 0.0;
+  auto term = [&](float g, float v) { return (double)(v > 0.f ? g : g * slope); };
+  for (int b = 0; b < B; ++b) {
+    const long base = ((long)b * C + c) * HW;
+    if (VEC) {
+      const float4* g4 = reinterpret_cast<const float4*>(gout + base);
+      const float4* y4 = reinterpret_cast<const float4*>(y + base);
+      const long n4 = HW / 4;
+      for (long i = threadIdx.x; i < n4; i += 2 * NTD) {  // two groups in flight
+        const long j = i + NTD;
+        const float4 ga = g4[i], va = y4[i];
+        const float4 gb = j < n4 ? g4[j] : make_float4(0.f, 0.f, 0.f, 0.f), vb = j < n4 ? y4[j] : make_float4(1.f, 1.f, 1.f, 1.f);
+        s += (term(ga.x, va.x) + term(ga.y, va.y)) + (term(ga.z, va.z) + term(ga.w, va.w));
+        s += (term(gb.x, vb.x) + term(gb.y, vb.y)) + (term(gb.z, vb.z) + term(gb.w, vb.w));
+      }
+    } else {
+      for (long i = threadIdx.x; i < HW; i += NTD) s += term(gout[base + i], y[base + i]);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < NTD / 64; ++w) t += red[w];
+    gbias[c] = (float)t;
+  }
+}
 }  // namespace
 
 extern "C" int arflow_bias_act_fwd(const float* x, const float* bias, float* y, int B, int C, long HW,
@@ -126,6 +167,16 @@ extern "C" int arflow_bias_act_bwd(const float* gout, const float* y, float* gin
   AF_REQUIRE_PTR(gin);
   AF_REQUIRE(B > 0 && C > 0 && HW > 0 && B <= 65535 && C <= 65535, ARFLOW_ESHAPE);
   hipStream_t st = (hipStream_t)stream;
+  if (gbias && af_deterministic()) {  // elementwise pass alone, then the fixed-order bias gradient
+    hipLaunchKernelGGL(bias_act_bwd_kernel, dim3(af_cdiv(HW, NT * EPT), C, B), dim3(NT), 0, st, gout, y, gin, (float*)nullptr, C,
+                       HW, negative_slope);
+    AF_LAUNCH_CHECK();
+    if ((HW & 3) == 0 && (((size_t)gout | (size_t)y) & 15) == 0)
+      hipLaunchKernelGGL(bias_grad_det_kernel<true>, dim3(C), dim3(NTD), 0, st, gout, y, gbias, B, C, HW, negative_slope);
+    else
+      hipLaunchKernelGGL(bias_grad_det_kernel<false>, dim3(C), dim3(NTD), 0, st, gout, y, gbias, B, C, HW, negative_slope);
+    return af_launch_status();
+  }
   if (gbias) {
     hipError_t e = hipMemsetAsync(gbias, 0, sizeof(float) * (size_t)C, st);
     if (e != hipSuccess) return af_hip_status(e);

@@ -2,6 +2,7 @@
 
 #include <atomic>
 #include <cstdio>
+#include <cstdlib>
 
 extern "C" int arflow_abi_version(void) { return 10; }
 
@@ -22,6 +23,27 @@ void af_record_stale_error(int code) {
 
 extern "C" int arflow_take_stale_error(void) { return g_stale_code.exchange(0); }
 
+// Deterministic mode: one process-wide switch, read by the launchers when they choose kernels -- never
+// inside a kernel.  -1 = not yet initialised from ARFLOW_DETERMINISTIC.
+static std::atomic<int> g_deterministic{-1};
+int af_deterministic() {
+  int v = g_deterministic.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("ARFLOW_DETERMINISTIC");
+    int want = (e && e[0] == '1' && e[1] == '\0') ? 1 : 0;
+    int expected = -1;
+    g_deterministic.compare_exchange_strong(expected, want);  // a set() that raced ahead wins
+    v = g_deterministic.load(std::memory_order_relaxed);
+  }
+  return v;
+}
+extern "C" int arflow_get_deterministic(void) { return af_deterministic(); }
+extern "C" int arflow_set_deterministic(int on) {
+  const int prev = af_deterministic();
+  g_deterministic.store(on ? 1 : 0, std::memory_order_relaxed);
+  return prev;
+}
+
 // Profiling aid (tools/kbench.py): a one-wave no-op kernel whose NAME delimits the dispatches of consecutive C-ABI calls
 // in a rocprofv3 kernel / counter trace, so that counters can be summed per CALL (an entry point may launch several kernels).
 __global__ void af_marker_kernel(int tag) { (void)tag; }
@@ -36,6 +58,7 @@ extern "C" const char* arflow_strerror(int code) {
     case ARFLOW_ENULL: return "required pointer is NULL";
     case ARFLOW_ESHAPE: return "non-positive, inconsistent or too large dimension";
     case ARFLOW_EPARAM: return "unsupported mode or parameter value";
+    case ARFLOW_ENONDET: return "this operation has no deterministic form (deterministic mode is on)";
     default: break;
   }
   if (code <= ARFLOW_ELAUNCH_BASE) return hipGetErrorString((hipError_t)(ARFLOW_ELAUNCH_BASE - code));

@@ -39,6 +39,12 @@ static inline int af_launch_status() {
 static inline int af_hip_status(hipError_t e) {
   return e == hipSuccess ? ARFLOW_OK : (ARFLOW_ELAUNCH_BASE - (int)e);
 }
+// Deterministic mode (arflow_set_deterministic / ARFLOW_DETERMINISTIC=1): sampled by the LAUNCHERS, which then pick the
+// fixed-order kernels (det_scatter.hip and friends); no kernel branches on it.  api.hip
+int af_deterministic();
+// in front of the first launch of an entry point that only has an atomic form
+#define AF_REQUIRE_NONDET_OK() AF_REQUIRE(!af_deterministic(), ARFLOW_ENONDET)
+
 static inline int af_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Launch-shape helpers shared by translation units (the level entry points size one accumulator for either producer).

@@ -411,6 +411,7 @@ extern "C" int arflow_warp_nearest_bwd(const float* gout, const float* flow, flo
   AF_REQUIRE(flow_bstride >= 2L * H * W, ARFLOW_ESHAPE);
   AF_REQUIRE(pad_mode == ARFLOW_PAD_ZEROS || pad_mode == ARFLOW_PAD_BORDER, ARFLOW_EPARAM);
   AF_REQUIRE(norm_mode >= ARFLOW_NORM_ARFLOW && norm_mode <= ARFLOW_NORM_UFLOW_ABS, ARFLOW_EPARAM);
+  AF_REQUIRE_NONDET_OK();  // float atomics only
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)B * C * Hs * Ws, st);
   if (e != hipSuccess) return af_hip_status(e);
@@ -447,6 +448,7 @@ extern "C" int arflow_warp_bicubic_bwd(const float* gout, const float* src, cons
   AF_REQUIRE(pad_mode == ARFLOW_PAD_ZEROS || pad_mode == ARFLOW_PAD_BORDER, ARFLOW_EPARAM);
   AF_REQUIRE(norm_mode >= ARFLOW_NORM_ARFLOW && norm_mode <= ARFLOW_NORM_UFLOW_ABS, ARFLOW_EPARAM);
   if (!gsrc && !gflow) return ARFLOW_OK;
+  if (gsrc) AF_REQUIRE_NONDET_OK();  // the source gradient is a float-atomic scatter
   hipStream_t st = (hipStream_t)stream;
   if (gsrc) {
     hipError_t e = hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)B * C * Hs * Ws, st);
@@ -551,6 +553,7 @@ extern "C" int arflow_corr_general_bwd(const float* gout, const float* x1, const
   CorrGen g;
   const int rc = corr_general_cfg(g, C, H, W, pad_size, kernel_size, max_disp, stride1, stride2);
   if (rc) return rc;
+  AF_REQUIRE_NONDET_OK();  // outside the set of ops the mode vouches for bit for bit: refused rather than promised
   const long total = (long)B * C * H * W;
   const unsigned blocks = (unsigned)((total + 255) / 256 > 65535 * 16 ? 65535 * 16 : (total + 255) / 256);
   hipLaunchKernelGGL(corr_general_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, gout, x1, x2, gx1, gx2, g,

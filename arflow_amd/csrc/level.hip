@@ -20,8 +20,9 @@ namespace {
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 constexpr int SLAB_CAP = 768;  // cells per tile slab: windows up to e.g. 16 x 48 (a smooth flow gives ~10 x 36)
 struct BwdWs {
-  size_t g1, g2, gfl, acc, slab, meta, ovf, qinfo, total;
+  size_t g1, g2, gfl, acc, slab, meta, ovf, qinfo, graw, total;
   int slab_cap;
+  bool det;     // deterministic mode: the unfused chain of arflow_level_bwd, with the raw warped map's gradient at `graw`
   bool gather;  // fine level: d/d src of the warp as a gather over the inverse-flow window (warp.hip inv_gather)
 };
 inline BwdWs bwd_layout(int B, int C, int H, int W) {
@@ -34,11 +35,12 @@ inline BwdWs bwd_layout(int B, int C, int H, int W) {
   w.slab = w.acc + align256(sizeof(double) * (size_t)ARFLOW_FEATNORM_ACC_DOUBLES(B));
   // two-pass source gradient of the warp at the fine level: one slab of SLAB_CAP cells per tile and channel
   const size_t tiles = (size_t)((W + 31) / 32) * ((H + 7) / 8) * B;
+  w.det = af_deterministic() != 0;
   static const bool slab_on = [] {
     const char* e = getenv("ARFLOW_WARP_SLAB");
     return e && e[0] == '1';
   }();
-  w.slab_cap = (slab_on && tiles >= 768 && tiles / B <= 1024) ? SLAB_CAP : 0;
+  w.slab_cap = (slab_on && !w.det && tiles >= 768 && tiles / B <= 1024) ? SLAB_CAP : 0;
   w.meta = w.slab + align256(sizeof(float) * tiles * C * (size_t)w.slab_cap);
   w.ovf = w.meta + align256(16 * tiles);
   w.qinfo = w.ovf + align256(sizeof(int) * (size_t)B);
@@ -54,8 +56,9 @@ inline BwdWs bwd_layout(int B, int C, int H, int W) {
   }();
   // (below ~768 tiles the two gradient roles share one launch and the atomics are not the bound: the gather form would add
   // a launch)
-  w.gather = gather_on && !w.slab_cap && tiles >= 768 && H <= 4095 && W <= 4095;
-  w.total = w.qinfo + (w.gather ? align256(sizeof(int) * (size_t)B * H * W) : 0);
+  w.gather = gather_on && !w.det && !w.slab_cap && tiles >= 768 && H <= 4095 && W <= 4095;
+  w.graw = w.qinfo + (w.gather ? align256(sizeof(int) * (size_t)B * H * W) : 0);
+  w.total = w.graw + (w.det ? n : 0);
   return w;
 }
 }  // namespace
@@ -187,6 +190,24 @@ extern "C" int arflow_level_bwd(const float* gout, long gout_bstride, const unsi
     AF_REQUIRE(gflow_a == nullptr || gflow_a_bstride >= 2L * H * W, ARFLOW_ESHAPE);
   }
   const float* second = has_flow ? x2w : x2;
+  if (ws.det && has_flow) {
+    // Deterministic mode: the level's backward as its unfused chain, every link in a fixed order --
+    //   correlation backward (a gather) -> the normalisation's backward WITH its apply pass (the raw warped map's gradient
+    //   is written once, to the workspace) -> the warp's two gradients (source: det_scatter.hip; flow: no channel split,
+    //   the concatenation's / residual's flow gradients added on the way out) -> the gather adjoint of the x2 upsample.
+    // Two launches and one pass over a [B,C,H,W] buffer more than the fused form; no float atomic anywhere.
+    float* graw = (float*)(base + ws.graw);
+    int rc = af_level_corr_bwd_launch(gout, gout_bstride, sign_bits, x1n, x1n_bstride, second, stats, g1, g2, B, C, H, W,
+                                      negative_slope, st, nullptr, nullptr, nullptr, nullptr);
+    if (rc != ARFLOW_OK) return rc;
+    rc = af_featnorm_bwd_launch(g1, gx1n_direct, gx1n_direct_bstride, g2, x1, x2w, stats, acc, gx1, graw, B, (long)C * H * W,
+                                norm_mode, st);
+    if (rc != ARFLOW_OK) return rc;
+    rc = af_warp_bwd_launch(graw, x2, flow_full, gx2, flow_is_coarse ? gfl : gflow, B, C, H, W, H, W, flow_bstride, pad_mode,
+                            align_corners, coord_norm, gflow_a, gflow_a_bstride, gflow_b, st);
+    if (rc != ARFLOW_OK || !flow_is_coarse) return rc;
+    return af_up2_bwd_launch(gfl, gflow, B * 2, H, W, up_align_corners, st);
+  }
   // (the upsample's adjoint through float atomics inside the warp launch was tried for the coarse levels: the channel-split
   // workgroups of a tile all add into the same few coarse cells -- 24x40 backward 48 -> 77 us; the gather kernel stays)
   const bool up_atomic = false;

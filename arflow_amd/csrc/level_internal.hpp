@@ -24,6 +24,10 @@ int af_level_warp_bwd_launch(const float* g2n, const float* x2, const float* x2w
                              float* slab, void* slab_meta, int* slab_ovf, int slab_cap, int* qinfo, hipStream_t st);
 int af_featnorm_bwd_sums_launch(const float* g1, const float* g1b, long g1b_bs, const float* g2, const float* x1,
                                 const float* x2, const float* stats, double* acc, int* nrows, int B, long n, hipStream_t st);
+// deterministic mode (det_scatter.hip): the fixed-order forms of the warp's source gradient and of the forward splat
+int af_det_warp_src_launch(const float* gout, const float* flow, float* gsrc, int B, int C, int Hs, int Ws, int H, int W,
+                           long flow_bstride, int pad_mode, int align_corners, int norm_mode, hipStream_t st);
+int af_det_splat_launch(const float* flow, float* out, int B, int H, int W, long flow_bstride, int variant, hipStream_t st);
 int af_up2_bwd_launch(const float* gfine, float* gcoarse, int planes, int H, int W, int up_align, hipStream_t st);
 int af_level_corr_fwd_launch(const float* x1, const float* x2w, const double* acc, int acc_rows, int norm_mode, float* out,
                              long out_bstride, float* x1n, long x1n_bstride, unsigned* sign_bits, float* stats, int B, int C,

@@ -102,6 +102,44 @@ __device__ __forceinline__ void up2_source(int d, int n_in, int n_out, bool alig
   l0 = 1.f - l1;
 }
 
+// The four target cells and weights of a forward splat at position (cx, cy) (splat_kernel, warp.hip, and its fixed-order
+// form in det_scatter.hip): variant 0 = compute_range_map, 1 = get_corresponding_map (clamped indices, weight dropped when a
+// tap left the image).
+struct SplatTaps {
+  int xi[4], yi[4];
+  float w[4];
+  bool ok[4];
+};
+__device__ __forceinline__ SplatTaps splat_taps(float cx, float cy, int H, int W, int variant) {
+  SplatTaps t;
+  const float fx = floorf(cx), fy = floorf(cy);
+  if ((variant & 1) == 0) {
+    const float ox = cx - fx, oy = cy - fy;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int di = k >> 1, dj = k & 1;
+      const float yi = fy + di, xj = fx + dj;
+      t.ok[k] = yi >= 0.f && yi < (float)H && xj >= 0.f && xj < (float)W;
+      t.w[k] = (di ? oy : 1.f - oy) * (dj ? ox : 1.f - ox);
+      t.yi[k] = t.ok[k] ? (int)yi : 0;
+      t.xi[k] = t.ok[k] ? (int)xj : 0;
+    }
+  } else {
+    const float xw = (float)(W - 1), yh = (float)(H - 1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int di = k >> 1, dj = k & 1;
+      const float yr = fy + di, xr = fx + dj;
+      const float yc = fminf(fmaxf(yr, 0.f), yh), xc = fminf(fmaxf(xr, 0.f), xw);
+      t.ok[k] = yc == yr && xc == xr;
+      t.w[k] = (1.f - fabsf(cx - xc)) * (1.f - fabsf(cy - yc));
+      t.yi[k] = t.ok[k] ? (int)yc : 0;
+      t.xi[k] = t.ok[k] ? (int)xc : 0;
+    }
+  }
+  return t;
+}
+
 __device__ __forceinline__ Taps no_taps() {
   Taps t;
   t.vx0 = t.vx1 = t.vy0 = t.vy1 = false;

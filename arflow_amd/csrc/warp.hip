@@ -13,6 +13,7 @@
 #include "taps.hpp"
 #include "featnorm_stats.hpp"
 #include "smooth_dev.hpp"
+#include "level_internal.hpp"
 
 namespace {
 
@@ -1273,41 +1274,7 @@ __global__ __launch_bounds__(NT) void gather_kernel(const float* __restrict__ g2
 // atomics per pixel, with same-address collisions inside a wave wherever the flow compresses -- took
 // 128 us for 8 x 384 x 640.  Weight quantisation error <= 1.2e-7 per tap.  Windows larger than
 // 128 x 64 fall back to direct atomics.
-struct SplatTaps {
-  int xi[4], yi[4];
-  float w[4];
-  bool ok[4];
-};
-__device__ __forceinline__ SplatTaps splat_taps(float cx, float cy, int H, int W, int variant) {
-  SplatTaps t;
-  const float fx = floorf(cx), fy = floorf(cy);
-  if ((variant & 1) == 0) {
-    const float ox = cx - fx, oy = cy - fy;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int di = k >> 1, dj = k & 1;
-      const float yi = fy + di, xj = fx + dj;
-      t.ok[k] = yi >= 0.f && yi < (float)H && xj >= 0.f && xj < (float)W;
-      t.w[k] = (di ? oy : 1.f - oy) * (dj ? ox : 1.f - ox);
-      t.yi[k] = t.ok[k] ? (int)yi : 0;
-      t.xi[k] = t.ok[k] ? (int)xj : 0;
-    }
-  } else {
-    const float xw = (float)(W - 1), yh = (float)(H - 1);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int di = k >> 1, dj = k & 1;
-      const float yr = fy + di, xr = fx + dj;
-      const float yc = fminf(fmaxf(yr, 0.f), yh), xc = fminf(fmaxf(xr, 0.f), xw);
-      t.ok[k] = yc == yr && xc == xr;
-      t.w[k] = (1.f - fabsf(cx - xc)) * (1.f - fabsf(cy - yc));
-      t.yi[k] = t.ok[k] ? (int)yc : 0;
-      t.xi[k] = t.ok[k] ? (int)xc : 0;
-    }
-  }
-  return t;
-}
-
+// (the four targets of a pixel: splat_taps, taps.hpp -- shared with the fixed-order form in det_scatter.hip)
 // SM: the same launch also takes the edge-aware smoothness partial sums of its tile's pixels (smooth_fwd_kernel's
 // arithmetic, smooth_dev.hpp) -- UFlowLoss needs the range map AND the smoothness term of the same level-2 flows
 // (losses/uflow_loss.py:43,62-102): one launch instead of two at a size where a launch costs more than either.
@@ -1446,17 +1413,25 @@ int warp_bwd_launch(const float* gout, const TS* src, const float* flow, float* 
                     int Ws, int H, int W, long flow_bstride, int pad_mode, int align_corners, int norm_mode,
                     const float* add1, long add1_bs, const float* add2, hipStream_t st) {
   if (!gsrc && !gflow) return ARFLOW_OK;
-  if (gsrc) {
+  // deterministic mode: d/d src through the fixed-order scatter (det_scatter.hip: every element written, no zero-fill) and
+  // the flow gradient without the channel split, whose partial sums meet in float atomics (flow_grad::store)
+  const bool det = af_deterministic() != 0;
+  if (gsrc && !det) {
     hipError_t e = hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)B * C * Hs * Ws, st);
     if (e != hipSuccess) return af_hip_status(e);
   }
   const long tiles = (long)af_cdiv(W, 32) * af_cdiv(H, 8) * B;
-  const unsigned nsplit = channel_split(tiles, C);
+  const unsigned nsplit = det ? 1u : channel_split(tiles, C);
   const dim3 grid(af_grid_for_tiles(tiles), nsplit);
-  if (gsrc)  // (d/d src never reads src)
+  if (gsrc && det) {
+    const int rc = af_det_warp_src_launch(gout, flow, gsrc, B, C, Hs, Ws, H, W, flow_bstride, pad_mode, align_corners,
+                                          norm_mode, st);
+    if (rc != ARFLOW_OK || !gflow) return rc;
+  } else if (gsrc) {  // (d/d src never reads src)
     hipLaunchKernelGGL(lds_scatter::warp_bwd_src_kernel<false>, grid, dim3(256), 0, st, gout, flow, gsrc, B, C, Hs, Ws, H, W,
                        flow_bstride, pad_mode, align_corners, norm_mode);
-  if (gsrc && gflow) AF_LAUNCH_CHECK();
+    if (gflow) AF_LAUNCH_CHECK();
+  }
   if (gflow) {
     if (nsplit > 1) {
       hipError_t e = hipMemsetAsync(gflow, 0, sizeof(float) * (size_t)B * 2 * H * W, st);
@@ -1649,6 +1624,7 @@ extern "C" int arflow_splat_map(const float* flow, float* out, int B, int H, int
   AF_REQUIRE(flow_bstride >= 2L * H * W, ARFLOW_ESHAPE);
   AF_REQUIRE(variant >= 0 && variant <= 3, ARFLOW_EPARAM);
   hipStream_t st = (hipStream_t)stream;
+  if (af_deterministic()) return af_det_splat_launch(flow, out, B, H, W, flow_bstride, variant, st);
   hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * H * W, st);
   if (e != hipSuccess) return af_hip_status(e);
   const long tiles = (long)af_cdiv(W, 32) * af_cdiv(H, 8) * B;
@@ -1673,6 +1649,11 @@ extern "C" int arflow_splat_smooth_fwd(const float* flow, const float* img, floa
   AF_REQUIRE(wmode == 0 || wmode == 1, ARFLOW_EPARAM);
   AF_REQUIRE(penalty == 0 || penalty == 1, ARFLOW_EPARAM);
   hipStream_t st = (hipStream_t)stream;
+  if (af_deterministic()) {  // the fixed-order splat, then the smoothness sums (already fixed-order) as their own launch
+    const int rc = af_det_splat_launch(flow, out, B, H, W, flow_bstride, 0, st);
+    if (rc != ARFLOW_OK) return rc;
+    return arflow_smooth_fwd(flow, img, sums, B, 3, H, W, flow_bstride, flow_scale, alpha, order, wmode, penalty, stream);
+  }
   if (!prezeroed) {
     hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * H * W, st);
     if (e != hipSuccess) return af_hip_status(e);

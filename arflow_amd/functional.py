@@ -4,6 +4,8 @@ Every op here runs ONLY on CUDA(ROCm) fp32 tensors through the hand-written gfx9
 tensor, a wrong dtype or a missing library raises.  Outputs are allocated with the torch caching
 allocator and kernels are enqueued on ``torch.cuda.current_stream()`` -- no synchronisation.
 """
+import contextlib
+
 import torch
 
 from . import _lib
@@ -103,6 +105,51 @@ def _call(name, *args, key=None):
         rc = getattr(lib, name)(*args)
     _lib.check(rc, name)
     _lib.poll_stale_error(lib, name)
+
+
+# ---- deterministic mode ------------------------------------------------------
+def set_deterministic(on):
+    """Switch the library's process-wide deterministic mode (initial value: ARFLOW_DETERMINISTIC=1); returns the previous
+    value.  While it is on, every op whose default kernels end in float atomics runs fixed-order kernels instead and is
+    bitwise reproducible; ops that only have an atomic form raise ArflowHipError.  ``torch.use_deterministic_algorithms``
+    is NOT consulted: under that flag ATen raises inside the models' own F.interpolate backward."""
+    return bool(_lib.load().arflow_set_deterministic(int(bool(on))))
+
+
+def is_deterministic():
+    return bool(_lib.load().arflow_get_deterministic())
+
+
+@contextlib.contextmanager
+def deterministic(on=True):
+    """``with AF.deterministic():`` -- the mode for the duration of the block; the previous value is restored on exit,
+    also when the block raises."""
+    prev = set_deterministic(on)
+    try:
+        yield
+    finally:
+        set_deterministic(prev)
+
+
+def _samples_mode(cls):
+    """Class decorator for the autograd nodes whose backward depends on the mode: the node samples it ONCE, in its
+    forward, and its backward runs under that value whatever the process-wide switch says by then (and puts the switch
+    back), so flipping the mode between forward and backward is safe."""
+    fwd, bwd = cls.forward, cls.backward
+
+    def forward(ctx, *args):
+        ctx.det_mode = is_deterministic()
+        return fwd(ctx, *args)
+
+    def backward(ctx, *grads):
+        if ctx.det_mode == is_deterministic():
+            return bwd(ctx, *grads)
+        with deterministic(ctx.det_mode):
+            return bwd(ctx, *grads)
+
+    forward.__doc__, backward.__doc__ = fwd.__doc__, bwd.__doc__
+    cls.forward, cls.backward = staticmethod(forward), staticmethod(backward)
+    return cls
 
 
 # ------------------------------------------------------------------------------------------------
@@ -206,6 +253,7 @@ class CorrelationBF16Function(torch.autograd.Function):
         return g1, g2, None, None
 
 
+@_samples_mode
 class CorrelationGeneralFunction(torch.autograd.Function):
     """Correlation with the CUDA extension's full parameter set (correlation_cuda.cc:10-16: pad_size, kernel_size,
     max_displacement, stride1, stride2); the configuration every model uses goes through CorrelationFunction."""
@@ -411,6 +459,7 @@ def level_supported(x1, flow, flow_is_coarse, max_displacement=4):
 _LEVEL_FUSED = __import__('os').environ.get('ARFLOW_LEVEL_FUSED', '1') != '0'  # A/B switch for tools/ and tests
 
 
+@_samples_mode
 class LevelFunction(torch.autograd.Function):
     """One pyramid level in front of its flow estimator (models/pwclite_uflow.py:203-222,
     models/uflow_model.py:160-198):
@@ -541,6 +590,7 @@ def level(x1, x2, flow, cfg, *members, x1_rows=None, x2_rows=None):
 
 
 # ------------------------------------------------------------------------------------------------
+@_samples_mode
 class BiasLeakyReLUFunction(torch.autograd.Function):
     """y = leaky_relu(x + bias[None, :, None, None], slope), IN PLACE on x (the bias-free output of a
     convolution, which autograd does not need again); backward = LeakyReLU derivative and bias gradient in
@@ -816,6 +866,7 @@ def dense_estimator(x, slope, params):
     return DenseEstimatorFunction.apply(x, slope, *params)
 
 
+@_samples_mode
 class BiasLeakyReLUMomentsFunction(torch.autograd.Function):
     """bias_leaky_relu that also returns the partial moments (sum y, sum y^2) of its output as rows of 2 doubles
     ([B, rows, 2], arflow_bias_act_fwd_mom): normalize_features' moments taken where the feature map is produced."""
@@ -858,6 +909,7 @@ def bias_leaky_relu_moments(x, bias, slope=0.1):
 
 
 # ------------------------------------------------------------------------------------------------
+@_samples_mode
 class WarpFunction(torch.autograd.Function):
     """out = bilinear(src, grid + flow); with ``want_valid`` also the in-image mask of the sampling
     positions (mask_invalid(flow_to_warp(flow)), utils/uflow_utils.py:35-50) from the same launch."""
@@ -898,6 +950,7 @@ class WarpFunction(torch.autograd.Function):
         return gsrc, gflow, None, None, None, None
 
 
+@_samples_mode
 class WarpUp2Function(torch.autograd.Function):
     """The front of a PWC pyramid level as the ARFlow model writes it (models/pwclite.py:178-180):
 
@@ -962,6 +1015,7 @@ def warp_up2_supported(src, flow_coarse):
             and flow_coarse.shape[1] == 2)
 
 
+@_samples_mode
 class WarpBF16Function(torch.autograd.Function):
     """Bilinear warp with the SOURCE stored as bf16 (opt-in): sampling arithmetic, output and
     both gradients fp32; the source is rounded to bf16 once and kept as such for the backward."""
@@ -997,6 +1051,7 @@ class WarpBF16Function(torch.autograd.Function):
         return gsrc, gflow, None, None, None
 
 
+@_samples_mode
 class WarpNearestFunction(torch.autograd.Function):
     """flow_warp(mode='nearest') (utils/warp_utils.py:83-90): gradient w.r.t. the source only, like grid_sample."""
 
@@ -1036,6 +1091,7 @@ def warp_nearest(src, flow, pad='zeros', align_corners=True, norm=NORM_ARFLOW):
     return WarpNearestFunction.apply(src, flow, PAD[pad], align_corners, norm)
 
 
+@_samples_mode
 class WarpBicubicFunction(torch.autograd.Function):
     """flow_warp(mode='bicubic') (utils/warp_utils.py:83-90 -> grid_sample bicubic): both gradients."""
 
@@ -1071,6 +1127,47 @@ class WarpBicubicFunction(torch.autograd.Function):
 
 def warp_bicubic(src, flow, pad='zeros', align_corners=True, norm=NORM_ARFLOW):
     return WarpBicubicFunction.apply(src, flow, PAD[pad], align_corners, norm)
+
+
+class FlowUpsampleFunction(torch.autograd.Function):
+    """F.interpolate(flow * factor, scale_factor=factor, mode='bilinear', align_corners) in one launch, with a GATHER
+    adjoint (arflow_flow_up_bwd): ATen's backward of that call scatters with float atomics, this one adds in a fixed
+    order.  Does not depend on the mode: it is what the models call while the mode is on."""
+
+    @staticmethod
+    def forward(ctx, flow, factor, align_corners):
+        _need_gpu(flow)
+        if flow.dim() != 4 or flow.shape[1] != 2:
+            raise ValueError('flow_upsample expects a [B,2,h,w] flow')
+        flow = flow.contiguous()
+        B, _, h, w = flow.shape
+        factor = int(factor)
+        out = torch.empty(B, 2, h * factor, w * factor, device=flow.device, dtype=torch.float32)
+        with torch.cuda.device_of(flow):
+            _call('arflow_flow_up_fwd', _p(flow), _p(out), B, h, w, factor, int(bool(align_corners)), _stream())
+        ctx.cfg = (B, h, w, factor, int(bool(align_corners)))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        B, h, w, factor, ac = ctx.cfg
+        gout = gout.contiguous()
+        gin = torch.empty(B, 2, h, w, device=gout.device, dtype=torch.float32)
+        with torch.cuda.device_of(gout):
+            _call('arflow_flow_up_bwd', _p(gout), _p(gin), B, h, w, factor, ac, _stream())
+        return gin, None, None
+
+
+def flow_upsample(flow, factor=2, align_corners=True):
+    """flow [B,2,h,w] -> F.interpolate(flow * factor, scale_factor=factor, mode='bilinear', align_corners) for factor 2, 4."""
+    return FlowUpsampleFunction.apply(flow, factor, align_corners)
+
+
+def interpolate_flow(flow, factor, align_corners):
+    """The models' flow upsample: ATen's F.interpolate in default mode (unchanged), flow_upsample in deterministic mode."""
+    if flow.is_cuda and flow.dtype == torch.float32 and is_deterministic():
+        return flow_upsample(flow, factor, align_corners)
+    return torch.nn.functional.interpolate(flow * factor, scale_factor=factor, mode='bilinear', align_corners=align_corners)
 
 
 def warp(src, flow, pad='zeros', align_corners=True, norm=NORM_ARFLOW, storage=None):

@@ -2,7 +2,6 @@
 state_dict layout as models/pwclite.py:109-283; correlation and warp are the HIP autograd ops."""
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from .. import functional as AF
 from ..correlation import Correlation
@@ -51,7 +50,7 @@ class PWCLite(nn.Module):
                 # flow x2 upsample (models/pwclite.py:178-179) folded into the warp launch
                 x2_warp, flow = AF.warp_up2(x2, flow, up_align=True)
             else:
-                flow = F.interpolate(flow * 2, scale_factor=2, mode='bilinear', align_corners=True)
+                flow = AF.interpolate_flow(flow, 2, True)
                 x2_warp = flow_warp(x2, flow)
             x1_1by1 = self.conv_1x1[l](x1)
             # corr + LeakyReLU(0.1) in one kernel, written straight into the estimator's concatenated input
@@ -63,7 +62,7 @@ class PWCLite(nn.Module):
                 break
         if self.upsample:
             # only the finest flow is upsampled (models/pwclite.py:200-203) -> 6 outputs
-            flows.append(F.interpolate(flow * 4, scale_factor=4, mode='bilinear', align_corners=True))
+            flows.append(AF.interpolate_flow(flow, 4, True))
         return flows[::-1]
 
     def forward_3_frames(self, x0_pyramid, x1_pyramid, x2_pyramid):
@@ -89,7 +88,7 @@ class PWCLite(nn.Module):
             elif AF.warp_up2_supported(neighbours, flow):
                 neighbours, flow = AF.warp_up2(neighbours, flow, up_align=True)
             else:
-                flow = F.interpolate(flow * 2, scale_factor=2, mode='bilinear', align_corners=True)
+                flow = AF.interpolate_flow(flow, 2, True)
                 neighbours = flow_warp(neighbours, flow)
             cost = self.corr(centre, neighbours, negative_slope=0.1)
             squeezed = self.conv_1x1[l](x1)
@@ -101,7 +100,7 @@ class PWCLite(nn.Module):
             if l == self.output_level:
                 break
         if self.upsample:
-            flows = [F.interpolate(f * 4, scale_factor=4, mode='bilinear', align_corners=True) for f in flows]
+            flows = [AF.interpolate_flow(f, 4, True) for f in flows]
         return [f[:B] for f in flows[::-1]], [f[B:] for f in flows[::-1]]
 
     def forward(self, x, with_bk=False):

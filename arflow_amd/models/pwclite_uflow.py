@@ -1,7 +1,6 @@
 """PWCLiteUflow host model on the gfx950 ops; contract of models/pwclite_uflow.py:126-267."""
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from .. import functional as AF
 from ..correlation import Correlation
@@ -101,7 +100,7 @@ class PWCLiteUflow(nn.Module):
                 if l == 0:
                     x2_warp = x2
                 else:
-                    flow = F.interpolate(flow * 2, scale_factor=2, mode='bilinear', align_corners=self.align_corners)
+                    flow = AF.interpolate_flow(flow, 2, self.align_corners)
                     x2_warp = flow_warp(x2, flow, align_corners=self.align_corners, pad=self.warp_pad,
                                         **({'storage_dtype': self.feature_storage} if self.feature_storage is not None else {}))
                 if self.feature_norm:
@@ -121,7 +120,7 @@ class PWCLiteUflow(nn.Module):
         flow = flow + flow_fine
         flows[-1] = flow
         for _ in range(2):
-            flow = F.interpolate(flow * 2, scale_factor=2, mode='bilinear', align_corners=self.align_corners)
+            flow = AF.interpolate_flow(flow, 2, self.align_corners)
             flows.append(flow)
         return flows[::-1]
 

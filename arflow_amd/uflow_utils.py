@@ -39,7 +39,11 @@ def compute_range_map(flow):
 
 
 def upsample(img, is_flow, scale_factor=2.0):
-    """utils/uflow_utils.py:163-182 (plain ATen resize: not a hot-path kernel)."""
+    """utils/uflow_utils.py:163-182 (plain ATen resize: not a hot-path kernel).  In deterministic mode a flow goes through
+    AF.flow_upsample instead: ATen's backward of this resize is an atomic scatter."""
+    if is_flow and scale_factor in (2, 4) and img.is_cuda and img.dtype == torch.float32 and img.shape[1] == 2 \
+            and AF.is_deterministic():
+        return AF.flow_upsample(img, int(scale_factor), False)
     out = torch.nn.functional.interpolate(img, scale_factor=scale_factor, mode='bilinear', align_corners=False)
     return out * scale_factor if is_flow else out
 

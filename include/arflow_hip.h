@@ -39,6 +39,7 @@ typedef void* arflow_stream_t; /* hipStream_t */
 #define ARFLOW_ENULL (-1001)   /* required pointer is NULL */
 #define ARFLOW_ESHAPE (-1002)  /* non-positive or inconsistent dimension */
 #define ARFLOW_EPARAM (-1003)  /* unsupported mode / parameter value */
+#define ARFLOW_ENONDET (-1004) /* deterministic mode is on and this operation only has an atomic form */
 #define ARFLOW_ELAUNCH_BASE (-2000)
 
 #define ARFLOW_PAD_ZEROS 0
@@ -62,6 +63,30 @@ int arflow_sums_rows(int B, int H, int W);
 
 int arflow_abi_version(void);
 const char* arflow_strerror(int code);
+
+/* ---- deterministic mode ------------------------------------------------------------------------
+ * One process-wide switch (initial value: environment variable ARFLOW_DETERMINISTIC=1, else off).  While it is on, every
+ * entry point whose default kernels end in floating-point atomics -- the source gradient of arflow_warp_bwd[_bf16] and of
+ * arflow_level_bwd, their channel-split flow gradient, arflow_splat_map / arflow_splat_smooth_fwd, the bias gradient of
+ * arflow_bias_act_bwd -- launches fixed-order kernels instead: each output element is the sum of its terms in ascending
+ * (target pixel, tap) order, a function of the data indices alone, so two calls on the same inputs agree bit for bit.
+ * The switch selects kernels at launch; default-mode kernels and results are untouched.  Entry points that only have
+ * an atomic form (arflow_corr_general_bwd, arflow_warp_nearest_bwd, arflow_warp_bicubic_bwd with gsrc) return
+ * ARFLOW_ENONDET while it is on.  arflow_level_bwd_ws_bytes honours the mode: size the workspace under the mode the call
+ * will run in.  set returns the previous value.  [No reference counterpart.] */
+int arflow_set_deterministic(int on);
+int arflow_get_deterministic(void);
+
+/* out[b,c] = factor * upsample_bilinear2d(flow[b,c], scale_factor = factor) in ATen's arithmetic, i.e.
+ * F.interpolate(flow * factor, scale_factor=factor, mode='bilinear', align_corners) of models/pwclite.py:54,66,92,104,
+ * models/pwclite_uflow.py:104,124 and utils/uflow_utils.py:163-180 upsample(is_flow) in one launch; factor 2 or 4 (else
+ * ARFLOW_EPARAM).  flow: [B,2,h,w] contiguous -> out: [B,2,factor*h,factor*w].  arflow_flow_up_bwd is its adjoint as a GATHER:
+ * one thread per coarse cell adds the fine pixels that read it, rows then columns ascending -- every element of gcoarse
+ * [B,2,h,w] written, no atomics, bitwise reproducible (ATen's backward scatters with atomics). */
+int arflow_flow_up_fwd(const float* flow, float* out, int B, int h, int w, int factor, int align_corners,
+                       arflow_stream_t stream);
+int arflow_flow_up_bwd(const float* gfine, float* gcoarse, int B, int h, int w, int factor, int align_corners,
+                       arflow_stream_t stream);
 /* HIP keeps ONE "last error" per host thread.  If a code was already pending when an entry point is entered
  * (left by the host framework or an unchecked earlier call) it is not attributed to this library's launch and
  * not dropped either: the first such hipError_t is kept (and reported once on stderr) until the host reads it
@@ -205,7 +230,8 @@ int arflow_level_corr_bwd(const float* gout, long gout_bstride, const unsigned* 
  * y = lrelu(x + bias[c]) for x, y: [B, C, HW] (x == y allowed; bias nullable): the bias add and
  * LeakyReLU(0.1) that follow every convolution of the reference models (models/pwclite.py:10-23,
  * models/uflow_model.py:271-287) in one pass.  Backward: gin = gout * (y > 0 ? 1 : negative_slope) and
- * gbias[c] = sum_{b,hw} gin (gbias nullable, zero-filled here; fp32 atomics). */
+ * gbias[c] = sum_{b,hw} gin (gbias nullable, zero-filled here; fp32 atomics -- in deterministic mode one workgroup per
+ * channel sums in a fixed order instead). */
 int arflow_bias_act_fwd(const float* x, const float* bias, float* y, int B, int C, long HW,
                         float negative_slope, arflow_stream_t stream);
 /* As arflow_bias_act_fwd; additionally every workgroup leaves (sum y, sum y^2) of its slice: mom holds
@@ -276,7 +302,8 @@ int arflow_warp_fwd(const float* src, const float* flow, float* out, float* vali
                     int norm_mode, arflow_stream_t stream);
 
 /* gsrc (nullable, zero-filled here, 4-tap atomic scatter) and gflow (nullable, [B,2,H,W]
- * contiguous). */
+ * contiguous).  Deterministic mode: gsrc through the fixed-order scatter of csrc/det_scatter.hip (every element
+ * written, no atomics), gflow without the channel split (plain stores). */
 int arflow_warp_bwd(const float* gout, const float* src, const float* flow, float* gsrc, float* gflow,
                     int B, int C, int Hs, int Ws, int H, int W, long flow_bstride, int pad_mode,
                     int align_corners, int norm_mode, arflow_stream_t stream);
@@ -285,7 +312,8 @@ int arflow_warp_bwd(const float* gout, const float* src, const float* flow, floa
  * variant 0: compute_range_map (utils/uflow_utils.py:80-160, utils/warp_utils.py:158-239)
  * variant 1: get_corresponding_map(grid+flow) (utils/warp_utils.py:26-80) -- clamped indices,
  *            weight zeroed when a tap left the image.
- * out [B,1,H,W] is zero-filled here. */
+ * out [B,1,H,W] is zero-filled here.  Deterministic mode: the fixed-order scatter of csrc/det_scatter.hip (fp32 sums in
+ * ascending source-pixel order instead of 2^-22 fixed point + float atomics; every cell written). */
 int arflow_splat_map(const float* flow, float* out, int B, int H, int W, long flow_bstride,
                      int variant, arflow_stream_t stream);
 
