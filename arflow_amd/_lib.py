@@ -95,6 +95,8 @@ PROTOTYPES = {
     'arflow_smooth_bwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_l, c_f, c_f, c_i, c_i, c_i, c_fp],
     'arflow_down4': [c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'arflow_up4_clamp_mul': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'arflow_flow_eval_rows': [c_i, c_i],
+    'arflow_flow_eval': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
 }
 
 ABI_VERSION = 10

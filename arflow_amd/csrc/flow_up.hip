@@ -3,28 +3,12 @@
 // 54,66,92,104; models/pwclite_uflow.py:104,124; utils/uflow_utils.py:163-180 upsample(is_flow)).  ATen's backward of that
 // call scatters with float atomics; here the adjoint is a gather with a fixed order of additions, so the models' flow path
 // is reproducible in deterministic mode.  (The x2 case inside the fused level keeps its own kernels: up2_source /
-// up2_bwd_kernel, warp.hip -- this file is their generalisation to a factor argument.)
+// up2_bwd_kernel, warp.hip -- this file is their generalisation to a factor argument; the index arithmetic is shared.)
 #include "common.hpp"
+#include "taps.hpp"
 
 namespace {
-// Source rows / weights of output index d of the bilinear upsample n_in -> n_out = factor * n_in: ATen/native/UpSample.h
-// area_pixel_compute_source_index and the index / lambda arithmetic of upsample_bilinear2d; rs = 1 / factor (exact).
-__device__ __forceinline__ void up_source(int d, int n_in, int n_out, float rs, bool align, int& i0, int& i1, float& l0,
-                                          float& l1) {
-  float src;
-  if (align) {
-    const float scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
-    src = scale * (float)d;
-  } else {
-    src = rs * ((float)d + 0.5f) - 0.5f;  // scale_factor given: scale = 1 / factor
-    src = src < 0.f ? 0.f : src;
-  }
-  i0 = min((int)src, n_in - 1);
-  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.f - l1;
-}
-
+// Source rows / weights: up_source (taps.hpp) with rs = 1 / factor (exact) -- the same device code as the level's x2 case.
 // one thread per fine pixel; planes = 2 B
 __global__ __launch_bounds__(256) void flow_up_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, int planes,
                                                           int h, int w, int factor, int align) {
@@ -41,7 +25,7 @@ __global__ __launch_bounds__(256) void flow_up_fwd_kernel(const float* __restric
   const float* s = in + pl * h * w;
   const float a00 = s[ya * w + xa], a01 = s[ya * w + xb], a10 = s[yb * w + xa], a11 = s[yb * w + xb];
   // interpolate(f * v) = f * interpolate(v) exactly in fp32: a power-of-two scale commutes with every rounding
-  out[idx] = f * (wy0 * (wx0 * a00 + wx1 * a01) + wy1 * (wx0 * a10 + wx1 * a11));
+  out[idx] = f * up_blend(wx0, wx1, wy0, wy1, a00, a01, a10, a11);
 }
 
 // Adjoint: one thread per coarse cell (i, j).  The fine rows that read coarse row i are those whose source index i0 is i or

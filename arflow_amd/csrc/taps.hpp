@@ -84,22 +84,34 @@ __device__ __forceinline__ void tap_corner_grad(const Taps& t, const float (&v)[
   sy = (v[2] - v[0]) * t.wx0 + (v[3] - v[1]) * t.wx1;
 }
 
-// Source rows / weights of output index d of the x2 bilinear upsample n_in -> n_out = 2 n_in:
-// ATen/native/UpSample.h area_pixel_compute_source_index + the index / lambda arithmetic of upsample_bilinear2d.
-__device__ __forceinline__ void up2_source(int d, int n_in, int n_out, bool align, int& i0, int& i1, float& l0,
-                                           float& l1) {
+// Source rows / weights of output index d of the bilinear resize n_in -> n_out: ATen/native/UpSample.h
+// area_pixel_compute_source_index + the index / lambda arithmetic of upsample_bilinear2d.  rs is the half-pixel scale of
+// the align_corners=False map: 1 / scale_factor where the caller of F.interpolate gave one (flow_up.hip, the level's x2),
+// (float)n_in / n_out where it gave a size (flow_eval.hip; cv2.INTER_LINEAR is the same map).  Both taps are clamped.
+__device__ __forceinline__ void up_source(int d, int n_in, int n_out, float rs, bool align, int& i0, int& i1, float& l0,
+                                          float& l1) {
   float src;
   if (align) {
     const float scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
     src = scale * (float)d;
   } else {
-    src = 0.5f * ((float)d + 0.5f) - 0.5f;  // scale_factor = 2 given: scale = 1 / 2
+    src = rs * ((float)d + 0.5f) - 0.5f;
     src = src < 0.f ? 0.f : src;
   }
   i0 = min((int)src, n_in - 1);
   i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
   l1 = src - (float)i0;
   l0 = 1.f - l1;
+}
+// ... the x2 case n_out = 2 n_in of the fused level (scale_factor = 2 given: scale = 1 / 2)
+__device__ __forceinline__ void up2_source(int d, int n_in, int n_out, bool align, int& i0, int& i1, float& l0,
+                                           float& l1) {
+  up_source(d, n_in, n_out, 0.5f, align, i0, i1, l0, l1);
+}
+// ... and the blend of the four taps in ATen's order (rows of the x blend, then y); no contraction (-ffp-contract=off)
+__device__ __forceinline__ float up_blend(float wx0, float wx1, float wy0, float wy1, float a00, float a01, float a10,
+                                          float a11) {
+  return wy0 * (wx0 * a00 + wx1 * a01) + wy1 * (wx0 * a10 + wx1 * a11);
 }
 
 // The four target cells and weights of a forward splat at position (cx, cy) (splat_kernel, warp.hip, and its fixed-order

@@ -1823,3 +1823,36 @@ def area_pyramid(frames, sizes):
             out.append(buf[off:off + B * C * h * w].view(B, C, h, w))
             off += B * C * h * w
     return out
+
+
+# ---- ground-truth flow metrics -------------------------------------------------
+EVAL_COLS = 8  # doubles per row of arflow_flow_eval
+
+
+def flow_eval_sums(pred, gt, move=None, want_map=False):
+    """The per-sample sums behind evaluate_flow (utils/flow_utils.py:121-183) in one launch: pred [B,2,h,w] is scaled,
+    resized to the ground truth's size and compared with gt [B,C,H,W] (C = 2 dense, C = 4 with the valid and non-occluded
+    masks in channels 2, 3); move: [B,1,H,W] moving mask or None.  -> sums [B,8] float64 on the device (columns: include/
+    arflow_hip.h; arflow_amd.metrics.metrics_from_sums turns them into the reference's metrics), and the end-point-error
+    map [B,1,H,W] as well if want_map.  No autograd, no synchronisation."""
+    _need_gpu(pred, gt, move)
+    if pred.dim() != 4 or pred.shape[1] != 2 or gt.dim() != 4 or gt.shape[0] != pred.shape[0]:
+        raise ValueError('flow_eval_sums expects pred [B,2,h,w] and gt [B,C,H,W]')
+    B, C, H, W = gt.shape
+    if move is not None and tuple(move.shape) != (B, 1, H, W):
+        raise ValueError('flow_eval_sums expects move [B,1,H,W]')
+    h, w = pred.shape[2:]
+    lib = _lib.load()
+    nrows = lib.arflow_flow_eval_rows(int(H), int(W))
+    if nrows <= 0:
+        _lib.check(nrows, 'arflow_flow_eval_rows')
+    with torch.no_grad():
+        pred, gt = pred.detach().contiguous(), gt.detach().contiguous()
+        move = None if move is None else move.detach().contiguous()
+        rows = torch.empty(B, nrows, EVAL_COLS, device=gt.device, dtype=torch.float64)
+        epe_map = torch.empty(B, 1, H, W, device=gt.device, dtype=torch.float32) if want_map else None
+        with torch.cuda.device_of(gt):
+            _call('arflow_flow_eval', _p(pred), _p(gt), _p(move), _p(rows), _p(epe_map), B, h, w, C, H, W, _stream(),
+                  key=(B, h, w, C, H, W))
+        sums = rows.sum(1)  # fixed order: reproducible
+    return (sums, epe_map) if want_map else sums

@@ -493,6 +493,27 @@ int arflow_down4(const float* in, float* out, int planes, int H, int W, arflow_s
 int arflow_up4_clamp_mul(const float* in, const float* valid, float* out, int B, int h, int w,
                          arflow_stream_t stream);
 
+/* ---- ground-truth flow metrics -----------------------------------------------------------------------
+ * The sums behind evaluate_flow (utils/flow_utils.py:121-183; trainer/uflow_trainer.py:94-170 validates with it after every
+ * epoch) in ONE launch, without bringing the flow to the host.  Per ground-truth pixel, fp32, in the reference's order:
+ *   u = (pred_u / w) * W, v = (pred_v / h) * H                                             (flow_utils.py:139-140)
+ *   bilinear resize to H x W, half-pixel rule (cv2.resize INTER_LINEAR, :143 = ATen upsample_bilinear2d(align_corners=False))
+ *   epe = sqrt(du^2 + dv^2) against gt[:, 0:2]                                             (:145-146)
+ *   valid = gt[:, 2], noc = gt[:, 3] (C = 4, read as [..., 2] and [..., -1], :151-152; both 1 for C = 2)
+ *   bad = (e > 3) && (e / max(|gt|, 1e-10) > 0.05), e = epe * valid                        (:123-128)
+ * rows: [B][arflow_flow_eval_rows(H, W)][8] doubles, need not be initialised: every row is stored by the call (one row per
+ * workgroup -- the `sums` conventions above; no zero-fill launch, no atomics: bitwise reproducible in either mode).  A
+ * sample's quantity k is the sum of column k over its rows:
+ *   0 sum epe*valid   1 sum valid   2 sum epe*noc   3 sum noc   4 sum bad   5 sum epe*valid*move   6 sum valid*move   7 zero
+ * (move NULL: columns 5, 6 are 0).  The occluded and the static sums follow on the host: (0) - (2), (1) - (3) and
+ * (0) - (5), (1) - (6).  Partials are fp32 per thread over 8 pixels and double from the wave reduction on.
+ * pred: [B,2,h,w]; gt: [B,C,H,W], C = 2 or 4 (else ARFLOW_EPARAM); move: [B,1,H,W] or NULL (needs C = 4, else
+ * ARFLOW_EPARAM); epe_map: [B,1,H,W] or NULL.  Any h, w, H, W >= 1 (float4 rows when W % 4 == 0 and gt / move / epe_map
+ * are 16-byte aligned).  arflow_flow_eval_rows: rows per sample, or ARFLOW_ESHAPE. */
+int arflow_flow_eval_rows(int H, int W);
+int arflow_flow_eval(const float* pred, const float* gt, const float* move, double* rows, float* epe_map, int B, int h,
+                     int w, int C, int H, int W, arflow_stream_t stream);
+
 /* ---- the rest of the reference's parameter space (no shipped config uses these values; plain kernels) ----------
  * flow_warp(mode='nearest') (utils/warp_utils.py:83-90 -> grid_sample nearest: border clips the coordinate, index =
  * nearbyint, out of range reads 0).  No gradient w.r.t. the flow (grid_sample's nearest mode has none). */
