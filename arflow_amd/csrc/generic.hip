@@ -6,6 +6,7 @@
 //   * SSIM(md != 1)                                              losses/loss_blocks.py:65-84
 //   * Correlation(kernel_size, stride1, stride2, pad_size != d)  models/correlation_package/correlation_cuda_kernel.cu:41-114
 #include "common.hpp"
+#include "ssim_dev.hpp"  // SSIM_C1 / SSIM_C2, Win, ssim_terms
 
 namespace {
 
@@ -246,14 +247,14 @@ __global__ __launch_bounds__(256) void census_any_bwd_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ SSIM, any window
-constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
-struct WinStats {
-  float mx, my, sx, sy, sxy;
-};
+// The constants, the window statistics and the four factors are those of ssim_dev.hpp; the divisions here are IEEE ones
+// (any k, nothing measured), and the backward passes the gradient on the OPEN interval 0 < dist < 1 where the tiled
+// kernels (ssim_dist_grad) use the closed one: they differ only where dist is exactly 0 or 1.
+//
 // un-padded k x k window anchored at (wy, wx): the reference pools x, y and the rounded products x*x, y*y, x*y
 // (losses/loss_blocks.py:70-78), sum in row-major order, then divides by k^2
-__device__ __forceinline__ WinStats window_stats(const float* __restrict__ X, const float* __restrict__ Y, int W, int wy,
-                                                 int wx, int k) {
+__device__ __forceinline__ Win window_stats_any(const float* __restrict__ X, const float* __restrict__ Y, int W, int wy,
+                                                int wx, int k) {
   float sa = 0.f, sb = 0.f, saa = 0.f, sbb = 0.f, sab = 0.f;
   for (int i = 0; i < k; ++i)
     for (int j = 0; j < k; ++j) {
@@ -261,7 +262,7 @@ __device__ __forceinline__ WinStats window_stats(const float* __restrict__ X, co
       sa += a, sb += b, saa += a * a, sbb += b * b, sab += a * b;
     }
   const float n = (float)(k * k);
-  WinStats w;
+  Win w;
   w.mx = sa / n, w.my = sb / n;
   w.sx = saa / n - w.mx * w.mx, w.sy = sbb / n - w.my * w.my, w.sxy = sab / n - w.mx * w.my;
   return w;
@@ -273,10 +274,8 @@ __global__ __launch_bounds__(256) void ssim_any_fwd_kernel(const float* __restri
   const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
   const long plane = blockIdx.z;  // b * C + c
   if (ox >= Wo) return;
-  const WinStats w = window_stats(x + plane * H * W, y + plane * H * W, W, oy, ox, k);
-  const float n = (2.f * w.mx * w.my + SSIM_C1) * (2.f * w.sxy + SSIM_C2);
-  const float d = (w.mx * w.mx + w.my * w.my + SSIM_C1) * (w.sx + w.sy + SSIM_C2);
-  out[(plane * Ho + oy) * Wo + ox] = fminf(fmaxf((1.f - n / d) / 2.f, 0.f), 1.f);
+  const SsimTerms t = ssim_terms(window_stats_any(x + plane * H * W, y + plane * H * W, W, oy, ox, k));
+  out[(plane * Ho + oy) * Wo + ox] = fminf(fmaxf((1.f - (t.n1 * t.n2) / (t.d1 * t.d2)) / 2.f, 0.f), 1.f);
 }
 
 // d / d x of sum_w gmap[w] * dist[w]; with S = A1 A2 / (B1 B2) over a window of N pixels,
@@ -297,9 +296,9 @@ __global__ __launch_bounds__(256) void ssim_any_bwd_kernel(const float* __restri
   for (int wy = max(0, py - k + 1); wy <= min(py, Ho - 1); ++wy)
     for (int wx = max(0, px - k + 1); wx <= min(px, Wo - 1); ++wx) {
       const float g = gmap[(plane * Ho + wy) * Wo + wx];
-      const WinStats w = window_stats(X, Y, W, wy, wx, k);
-      const float A1 = 2.f * w.mx * w.my + SSIM_C1, A2 = 2.f * w.sxy + SSIM_C2;
-      const float B1 = w.mx * w.mx + w.my * w.my + SSIM_C1, B2 = w.sx + w.sy + SSIM_C2;
+      const Win w = window_stats_any(X, Y, W, wy, wx, k);
+      const SsimTerms t = ssim_terms(w);
+      const float A1 = t.n1, A2 = t.n2, B1 = t.d1, B2 = t.d2;
       const float S = (A1 * A2) / (B1 * B2);
       const float dist = (1.f - S) / 2.f;
       if (!(dist > 0.f && dist < 1.f)) continue;  // clamp inactive only strictly inside (torch.clamp's gradient)

@@ -7,7 +7,8 @@
 // kernels of the composed path are gone.
 //
 // Per-pixel arithmetic is that of warp_fwd_kernel / warp_bwd_flow_kernel (taps.hpp) and of photo4::fwd_kernel /
-// bwd_kernel (ssim_dev.hpp): only the order of the final summation differs from the composed path.
+// bwd_kernel, whose window, coefficient and gather stages (ssim_dev.hpp) run here unchanged: only the order of the
+// final summation differs from the composed path.
 //
 // Tiling: 16 x 64 pixels / 256 threads as photo4.  Every slot of the tile + halo (1 px forward, 2 px backward) warps
 // its own pixel straight from global memory (3-channel images: the four taps of neighbouring pixels share cache lines;
@@ -21,7 +22,10 @@
 namespace {
 
 namespace pw {
-constexpr int TXW = 64, TYH = 16, NT = 256, P = 72, CMAX = 3;
+using photo4::NT;
+using photo4::TXW;
+using photo4::TYH;
+constexpr int P = 72, CMAX = 3;
 
 struct Args {
   const float* tgt;
@@ -121,17 +125,8 @@ __global__ __launch_bounds__(NT) void fwd_kernel(Args a, float* __restrict__ mas
   const int xg = threadIdx.x & 15, ly = threadIdx.x >> 4;
   const int x0 = tx0 + 4 * xg, y = ty0 + ly;
   if (y < a.H - 2 && x0 < a.W - 2) {
-    for (int c = 0; c < a.C; ++c) {
-      float wa[3][6], wb[3][6];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        photo4::read6(&X[c][(ly + i) * P + 4 * xg], wa[i]);
-        photo4::read6(&Y[c][(ly + i) * P + 4 * xg], wb[i]);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (x0 + e < a.W - 2) part[1] += ssim_dist(photo4::stats6(wa, wb, e));
-    }
+    for (int c = 0; c < a.C; ++c)
+      photo4::fwd_windows<P>(X[c], Y[c], ly, xg, x0, a.W, [&](int, float dist) { part[1] += dist; });
   }
   af_block_sum<3>(part, red);
   if (threadIdx.x == 0) {
@@ -193,65 +188,22 @@ __global__ __launch_bounds__(NT) void bwd_kernel(Args a, const float* __restrict
     px[e] = pixel(a, fl, mk, in[e] ? y : 0, in[e] ? x0 + e : 0);
   }
   float gix[4] = {0.f, 0.f, 0.f, 0.f}, giy[4] = {0.f, 0.f, 0.f, 0.f};
-  constexpr int NG = TXW / 4 + 1, NTASK = (TYH + 2) * NG;  // 18 anchor rows x 17 groups of 4 anchors
   for (int c = 0; c < a.C; ++c) {
     __syncthreads();  // X / Y staged (c = 0); the previous channel's WA / WB / WC consumed (c > 0)
-    // per-window coefficients: d dist_w / d x_r = A + B x_r + C y_r
-    for (int t = threadIdx.x; t < NTASK; t += NT) {
-      const int r = t / NG, gq = t - r * NG;
-      float wa[3][6], wb[3][6];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        photo4::read6(&X[c][(r + i) * P + 4 * gq], wa[i]);
-        photo4::read6(&Y[c][(r + i) * P + 4 * gq], wb[i]);
-      }
-      const int wy = ty0 - 2 + r;
-      float A[4], Bc[4], Cc[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int wx = tx0 - 4 + 4 * gq + e;
-        A[e] = Bc[e] = Cc[e] = 0.f;
-        if (wy >= 0 && wy < a.H - 2 && wx >= 0 && wx < a.W - 2) ssim_dist_grad(photo4::stats6(wa, wb, e), c_ss, A[e], Bc[e], Cc[e]);
-      }
-      *reinterpret_cast<float4*>(WA + r * P + 4 * gq) = make_float4(A[0], A[1], A[2], A[3]);
-      *reinterpret_cast<float4*>(WB + r * P + 4 * gq) = make_float4(Bc[0], Bc[1], Bc[2], Bc[3]);
-      *reinterpret_cast<float4*>(WC + r * P + 4 * gq) = make_float4(Cc[0], Cc[1], Cc[2], Cc[3]);
-    }
+    photo4::coef_pass<P>(X[c], Y[c], WA, WB, WC, ty0, tx0, a.H, a.W, [&](int, int) { return c_ss; });
     __syncthreads();
-    // pixel (y, x0+e) = tile (ly+2, 4xg+4+e); the window anchored at (y-i, x-j) sits at tile (ly+2-i, 4xg+4+e-j)
-    float ca[3][8], cb[3][8], cc[3][8], xc[8], yc[8];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      photo4::read8(WA + (ly + i) * P + 4 * xg, ca[i]);
-      photo4::read8(WB + (ly + i) * P + 4 * xg, cb[i]);
-      photo4::read8(WC + (ly + i) * P + 4 * xg, cc[i]);
-    }
-    photo4::read8(&X[c][(ly + 2) * P + 4 * xg], xc);
-    photo4::read8(&Y[c][(ly + 2) * P + 4 * xg], yc);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float sa = 0.f, sb = 0.f, sc = 0.f;
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          sa += ca[2 - i][4 + e - j];
-          sb += cb[2 - i][4 + e - j];
-          sc += cc[2 - i][4 + e - j];
-        }
+    photo4::gather4<P>(X[c], Y[c], WA, WB, WC, ly, xg, [&](int e, const Coef& s, float xv, float yv) {
       float v[4];
       taps4(sr + c * cs, px[e].p, v);
       const float rec = tap_blend(px[e].p, v);
       const float iv = tg[c * cs + (in[e] ? (long)y * a.W + x0 + e : 0)];
-      const float diff = rec - iv;
-      const float sg = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
       // photo4::bwd_kernel's d / d rec, fed into warp_bwd_flow_kernel's d rec / d coordinate
-      const float gr = px[e].m * (c_l1 * sg + sa + sb * xc[4 + e] + sc * yc[4 + e]);
+      const float gr = rec_grad(px[e].m, c_l1, rec, iv, s, xv, yv);
       float sx, sy;
       tap_corner_grad(px[e].t, v, sx, sy);
       gix[e] = fmaf(gr, sx, gix[e]);
       giy[e] = fmaf(gr, sy, giy[e]);
-    }
+    });
   }
   float* gf = gflow + b * gflow_bs + g * gflow_half + (long)y * a.W + x0;
 #pragma unroll
@@ -355,7 +307,7 @@ int pw_args(pw::Args& a, const float* tgt, long tgt_bs, long tgt_half, const flo
 
 extern "C" int arflow_photo_warp_rows(int N, int H, int W) {
   if (N <= 0 || H < 3 || W < 3) return ARFLOW_ESHAPE;
-  const long t = (long)af_cdiv(W, pw::TXW) * af_cdiv(H, pw::TYH) * N;
+  const long t = photo4::tiles(N, H, W);
   return t > (1L << 30) ? ARFLOW_ESHAPE : (int)t;
 }
 
@@ -370,8 +322,8 @@ extern "C" int arflow_photo_warp_fwd(const float* tgt, long tgt_bs, long tgt_hal
   const int rc = pw_args(a, tgt, tgt_bs, tgt_half, src, src_bs, src_half, flow, flow_bs, flow_half, mask, mask_bs, mask_half,
                          mask_mode, mask_invert, mask_h, mask_w, B, G, C, H, W, pad_mode);
   if (rc != ARFLOW_OK) return rc;
-  const long tiles = (long)af_cdiv(W, pw::TXW) * af_cdiv(H, pw::TYH) * B * G;
-  hipLaunchKernelGGL(pw::fwd_kernel, dim3(af_grid_for_tiles(tiles)), dim3(pw::NT), 0, (hipStream_t)stream, a, mask_out, rows);
+  hipLaunchKernelGGL(pw::fwd_kernel, dim3(af_grid_for_tiles(photo4::tiles((long)B * G, H, W))), dim3(pw::NT), 0,
+                     (hipStream_t)stream, a, mask_out, rows);
   return af_launch_status();
 }
 
@@ -387,9 +339,8 @@ extern "C" int arflow_photo_warp_bwd(const float* tgt, long tgt_bs, long tgt_hal
   const int rc = pw_args(a, tgt, tgt_bs, tgt_half, src, src_bs, src_half, flow, flow_bs, flow_half, mask, mask_bs, mask_half,
                          mask_mode, mask_invert, mask_h, mask_w, B, G, C, H, W, pad_mode);
   if (rc != ARFLOW_OK) return rc;
-  const long tiles = (long)af_cdiv(W, pw::TXW) * af_cdiv(H, pw::TYH) * B * G;
-  hipLaunchKernelGGL(pw::bwd_kernel, dim3(af_grid_for_tiles(tiles)), dim3(pw::NT), 0, (hipStream_t)stream, a, coef, gflow,
-                     gflow_bs, gflow_half);
+  hipLaunchKernelGGL(pw::bwd_kernel, dim3(af_grid_for_tiles(photo4::tiles((long)B * G, H, W))), dim3(pw::NT), 0,
+                     (hipStream_t)stream, a, coef, gflow, gflow_bs, gflow_half);
   return af_launch_status();
 }
 

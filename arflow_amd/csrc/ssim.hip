@@ -3,8 +3,11 @@
 // want different compiler settings: these kernels are built WITHOUT the SLP vectoriser (Makefile: its v_pk_* pairing
 // costs more v_mov than it saves here: forward 28.4 -> 23.5 us, backward 53.3 -> 45.6 us at 8x3x384x640), the census
 // kernels with it (backward 59 -> 69 us without).
+//
+// The kernels here are staging (global -> LDS tiles, the block sums, the stores) plus calls: every piece of SSIM
+// arithmetic, and the stages the 16 x 64 tiling shares with photo_warp.hip, are in ssim_dev.hpp.
 #include "common.hpp"
-#include "ssim_dev.hpp"  // Win, div9, fdiv_pos, frcp_pos, photo4::read6 / read8 / stats6
+#include "ssim_dev.hpp"
 
 namespace {
 
@@ -13,32 +16,6 @@ constexpr int TX = 32, TY = 8;  // pixel tile = 256 threads, lanes run along x
 // ------------------------------------------------------------------------------------------------
 // SSIM (3x3, un-padded) + L1
 // ------------------------------------------------------------------------------------------------
-template <int PITCH>
-__device__ __forceinline__ Win window_stats(const float (*tx)[PITCH], const float (*ty)[PITCH], int r, int c) {
-  float sxv = 0.f, syv = 0.f, sxx = 0.f, syy = 0.f, sxyv = 0.f;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float a = tx[r + i][c + j], b = ty[r + i][c + j];
-      // the reference pools the already-rounded products x*x, y*y, x*y (AvgPool2d of a product
-      // tensor, loss_blocks.py:76-78): round each product, add in row-major order, divide by 9.
-      // sigma = E[x^2]-mu^2 cancels catastrophically, so the operation order is kept.
-      sxv += a;
-      syv += b;
-      sxx += a * a;
-      syy += b * b;
-      sxyv += a * b;
-    }
-  Win w;
-  w.mx = div9(sxv);
-  w.my = div9(syv);
-  w.sx = div9(sxx) - w.mx * w.mx;
-  w.sy = div9(syy) - w.my * w.my;
-  w.sxy = div9(sxyv) - w.mx * w.my;
-  return w;
-}
-
 __global__ __launch_bounds__(TX* TY) void photo_fwd_kernel(const float* __restrict__ im,
                                                            const float* __restrict__ rec,
                                                            const float* __restrict__ mask,
@@ -79,10 +56,7 @@ __global__ __launch_bounds__(TX* TY) void photo_fwd_kernel(const float* __restri
     }
     __syncthreads();
     if (x < W - 2 && y < H - 2) {
-      const Win w = window_stats<TX + 3>(tx, ty, ly, lx);
-      const float n = (2.f * w.mx * w.my + SSIM_C1) * (2.f * w.sxy + SSIM_C2);
-      const float d = (w.mx * w.mx + w.my * w.my + SSIM_C1) * (w.sx + w.sy + SSIM_C2);
-      const float dist = fminf(fmaxf((1.f - fdiv_pos(n, d)) / 2.f, 0.f), 1.f);
+      const float dist = ssim_dist(window_stats<TX + 3>(tx, ty, ly, lx));
       part[1] += dist;
       if (ssim_map) ssim_map[(((long)b * C + c) * (H - 2) + y) * (W - 2) + x] = dist;
     }
@@ -134,43 +108,25 @@ __global__ __launch_bounds__(TX* TY) void photo_bwd_kernel(const float* __restri
       const int r = idx / (TX + 2), cc = idx - r * (TX + 2);
       const int wy = ty0 + r - 2, wx = tx0 + cc - 2;  // window anchor
       float A = 0.f, Bc = 0.f, Cc = 0.f;
-      if (wy >= 0 && wy < H - 2 && wx >= 0 && wx < W - 2) {
-        const Win w = window_stats<TX + 5>(dx_, dy_, r, cc);
-        const float n1 = 2.f * w.mx * w.my + SSIM_C1, n2 = 2.f * w.sxy + SSIM_C2;
-        const float d1 = w.mx * w.mx + w.my * w.my + SSIM_C1, d2 = w.sx + w.sy + SSIM_C2;
-        const float n = n1 * n2, d = d1 * d2;
-        const float v = (1.f - fdiv_pos(n, d)) / 2.f;
-        if (v >= 0.f && v <= 1.f) {  // torch.clamp passes the gradient on the closed interval
-          const float up = gmap ? gmap[(((long)b * C + c) * (H - 2) + wy) * (W - 2) + wx] : c_ss;
-          const float k = -0.5f * up * (2.f / 9.f);
-          const float id = frcp_pos(d), nd2 = n * id * id;
-          Cc = k * n1 * id;                                                     // * y_r
-          Bc = -k * nd2 * d1;                                                   // * x_r
-          A = k * ((w.my * n2 - n1 * w.my) * id - nd2 * (w.mx * d2 - d1 * w.mx));  // constant
-        }
-      }
+      if (wy >= 0 && wy < H - 2 && wx >= 0 && wx < W - 2)
+        ssim_dist_grad(
+            window_stats<TX + 5>(dx_, dy_, r, cc),
+            [&] { return gmap ? gmap[(((long)b * C + c) * (H - 2) + wy) * (W - 2) + wx] : c_ss; }, A, Bc, Cc);
       wa[r][cc] = A;
       wb[r][cc] = Bc;
       wc[r][cc] = Cc;
     }
     __syncthreads();
     if (x < W && y < H) {
-      float sa = 0.f, sb = 0.f, sc = 0.f;
+      Coef s;
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          // window anchored at (y-i, x-j) = tile slot (ly+2-i, lx+2-j)
-          sa += wa[ly + 2 - i][lx + 2 - j];
-          sb += wb[ly + 2 - i][lx + 2 - j];
-          sc += wc[ly + 2 - i][lx + 2 - j];
-        }
+        for (int j = 0; j < 3; ++j)  // window anchored at (y-i, x-j) = tile slot (ly+2-i, lx+2-j)
+          s.add(wa[ly + 2 - i][lx + 2 - j], wb[ly + 2 - i][lx + 2 - j], wc[ly + 2 - i][lx + 2 - j]);
       const long o = (long)y * W + x;
       const float m = mask ? mask[(long)b * cs + o] : 1.f;
-      const float xv = dx_[ly + 2][lx + 2], yv = dy_[ly + 2][lx + 2];
-      const float diff = rc[o] - imc[o];
-      const float sg = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-      g_rec[((long)b * C + c) * cs + o] = m * (c_l1 * sg + sa + sb * xv + sc * yv);
+      g_rec[((long)b * C + c) * cs + o] = rec_grad(m, c_l1, rc[o], imc[o], s, dx_[ly + 2][lx + 2], dy_[ly + 2][lx + 2]);
     }
   }
 }
@@ -183,7 +139,7 @@ __global__ __launch_bounds__(TX* TY) void photo_bwd_kernel(const float* __restri
 // the same order, as the 1-px kernels (which remain for unaligned widths).
 // ------------------------------------------------------------------------------------------------
 namespace photo4 {
-constexpr int TXW = 64, TYH = 16, NT = 256, P = 128;
+constexpr int P = 128;
 // masked tiles x = recons*mask, y = im*mask: `rows` x `nq` float4 starting at image (gy0, gx0) (gx0 % 4 == 0)
 template <int ROWS, int NQ, bool L1>
 __device__ __forceinline__ float stage(float* __restrict__ X, float* __restrict__ Y, const float* __restrict__ imc,
@@ -252,25 +208,11 @@ __global__ __launch_bounds__(NT) void fwd_kernel(const float* __restrict__ im, c
     part[0] += stage<TYH + 2, TXW / 4 + 1, true>(X, Y, im + ((long)b * C + c) * cs, rec + ((long)b * C + c) * cs, mb, H,
                                                   W, ty0, tx0, 0, 0);
     __syncthreads();
-    if (y < H - 2) {
-      float a[3][6], bb[3][6];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        read6(X + (ly + i) * P + 4 * xg, a[i]);
-        read6(Y + (ly + i) * P + 4 * xg, bb[i]);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (x0 + e < W - 2) {
-          const Win w = stats6(a, bb, e);
-          const float n = (2.f * w.mx * w.my + SSIM_C1) * (2.f * w.sxy + SSIM_C2);
-          const float d = (w.mx * w.mx + w.my * w.my + SSIM_C1) * (w.sx + w.sy + SSIM_C2);
-          const float dist = fminf(fmaxf((1.f - fdiv_pos(n, d)) / 2.f, 0.f), 1.f);
-          part[1] += dist;
-          if (ssim_map) ssim_map[(((long)b * C + c) * (H - 2) + y) * (W - 2) + x0 + e] = dist;
-        }
-      }
-    }
+    if (y < H - 2)
+      fwd_windows<P>(X, Y, ly, xg, x0, W, [&](int e, float dist) {
+        part[1] += dist;
+        if (ssim_map) ssim_map[(((long)b * C + c) * (H - 2) + y) * (W - 2) + x0 + e] = dist;
+      });
   }
   af_block_sum<3>(part, red);
   if (threadIdx.x == 0) af_store_partial(sums, nrows, part[0], part[1], part[2]);
@@ -295,106 +237,56 @@ __global__ __launch_bounds__(NT) void bwd_kernel(const float* __restrict__ im, c
   const int x0 = tx0 + 4 * xg, y = ty0 + ly;
   const float* mb = mask ? mask + (long)b * cs : nullptr;
   const float c_l1 = coef[0], c_ss = coef[1];
-  constexpr int NG = TXW / 4 + 1, NTASK = (TYH + 2) * NG;  // 18 anchor rows x 17 groups of 4 anchors
   for (int c = 0; c < C; ++c) {
     const float* imc = im + ((long)b * C + c) * cs;
     const float* rc = rec + ((long)b * C + c) * cs;
     if (c) __syncthreads();
     stage<TYH + 4, TXW / 4 + 2, false>(X, Y, imc, rc, mb, H, W, ty0 - 2, tx0 - 4, 0, 0);
     __syncthreads();
-    // per-window coefficients: d dist_w / d x_r = -(1/2)(A + B x_r + C y_r)  (see photo_bwd_kernel)
-    for (int t = threadIdx.x; t < NTASK; t += NT) {
-      const int r = t / NG, g = t - r * NG;
-      float a[3][6], bb[3][6];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        read6(X + (r + i) * P + 4 * g, a[i]);
-        read6(Y + (r + i) * P + 4 * g, bb[i]);
-      }
-      const int wy = ty0 - 2 + r;
-      float A[4], Bc[4], Cc[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int wx = tx0 - 4 + 4 * g + e;
-        A[e] = Bc[e] = Cc[e] = 0.f;
-        if (wy >= 0 && wy < H - 2 && wx >= 0 && wx < W - 2) {
-          const Win w = stats6(a, bb, e);
-          const float n1 = 2.f * w.mx * w.my + SSIM_C1, n2 = 2.f * w.sxy + SSIM_C2;
-          const float d1 = w.mx * w.mx + w.my * w.my + SSIM_C1, d2 = w.sx + w.sy + SSIM_C2;
-          const float n = n1 * n2, d = d1 * d2;
-          const float v = (1.f - fdiv_pos(n, d)) / 2.f;
-          if (v >= 0.f && v <= 1.f) {  // torch.clamp passes the gradient on the closed interval
-            const float up = gmap ? gmap[(((long)b * C + c) * (H - 2) + wy) * (W - 2) + wx] : c_ss;
-            const float k = -0.5f * up * (2.f / 9.f);
-            const float id = frcp_pos(d), nd2 = n * id * id;
-            Cc[e] = k * n1 * id;                                                        // * y_r
-            Bc[e] = -k * nd2 * d1;                                                      // * x_r
-            A[e] = k * ((w.my * n2 - n1 * w.my) * id - nd2 * (w.mx * d2 - d1 * w.mx));  // constant
-          }
-        }
-      }
-      *reinterpret_cast<float4*>(WA + r * P + 4 * g) = make_float4(A[0], A[1], A[2], A[3]);
-      *reinterpret_cast<float4*>(WB + r * P + 4 * g) = make_float4(Bc[0], Bc[1], Bc[2], Bc[3]);
-      *reinterpret_cast<float4*>(WC + r * P + 4 * g) = make_float4(Cc[0], Cc[1], Cc[2], Cc[3]);
-    }
+    coef_pass<P>(X, Y, WA, WB, WC, ty0, tx0, H, W, [&](int wy, int wx) {
+      return gmap ? gmap[(((long)b * C + c) * (H - 2) + wy) * (W - 2) + wx] : c_ss;
+    });
     __syncthreads();
     if (y < H && x0 < W) {
-      // pixel (y, x0+e) = tile (ly+2, 4xg+4+e); the window anchored at (y-i, x-j) sits at tile (ly+2-i, 4xg+4+e-j)
-      float ca[3][8], cb[3][8], cc[3][8], xc[8], yc[8];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        read8(WA + (ly + i) * P + 4 * xg, ca[i]);
-        read8(WB + (ly + i) * P + 4 * xg, cb[i]);
-        read8(WC + (ly + i) * P + 4 * xg, cc[i]);
-      }
-      read8(X + (ly + 2) * P + 4 * xg, xc);
-      read8(Y + (ly + 2) * P + 4 * xg, yc);
       const long o = (long)y * W + x0;
       const float4 i4 = *reinterpret_cast<const float4*>(imc + o), r4 = *reinterpret_cast<const float4*>(rc + o);
       const float4 m4 = mb ? *reinterpret_cast<const float4*>(mb + o) : make_float4(1.f, 1.f, 1.f, 1.f);
       const float iv[4] = {i4.x, i4.y, i4.z, i4.w}, rv[4] = {r4.x, r4.y, r4.z, r4.w}, mv[4] = {m4.x, m4.y, m4.z, m4.w};
       float out[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float sa = 0.f, sb = 0.f, sc = 0.f;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j) {
-            sa += ca[2 - i][4 + e - j];
-            sb += cb[2 - i][4 + e - j];
-            sc += cc[2 - i][4 + e - j];
-          }
-        const float diff = rv[e] - iv[e];
-        const float sg = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-        out[e] = mv[e] * (c_l1 * sg + sa + sb * xc[4 + e] + sc * yc[4 + e]);
-      }
+      gather4<P>(X, Y, WA, WB, WC, ly, xg, [&](int e, const Coef& s, float xv, float yv) {
+        out[e] = rec_grad(mv[e], c_l1, rv[e], iv[e], s, xv, yv);
+      });
       *reinterpret_cast<float4*>(g_rec + ((long)b * C + c) * cs + o) = make_float4(out[0], out[1], out[2], out[3]);
     }
   }
 }
 }  // namespace photo4
 
-
 }  // namespace
+
+// 16 x 64 tiles and 4 pixels per lane where the rows are 16-byte aligned, else 8 x 32 tiles and 1 pixel per lane;
+// 256 threads either way
+static_assert(TX * TY == photo4::NT, "both tilings launch photo4::NT threads");
+static bool photo_four(int W) { return (W & 3) == 0; }
+static dim3 grid1(int B, int H, int W) { return dim3(af_grid_for_tiles((long)af_cdiv(W, TX) * af_cdiv(H, TY) * B)); }
+static dim3 grid4(int B, int H, int W) { return dim3(af_grid_for_tiles(photo4::tiles(B, H, W))); }
+static int photo_check(const float* im, const float* recons, int B, int C, int H, int W) {
+  AF_REQUIRE_PTR(im);
+  AF_REQUIRE_PTR(recons);
+  AF_REQUIRE(B > 0 && C > 0 && H >= 3 && W >= 3 && B <= 65535, ARFLOW_ESHAPE);
+  return ARFLOW_OK;
+}
 
 extern "C" int arflow_photo_fwd(const float* im, const float* recons, const float* mask, float* ssim_map,
                                 float* sums, int B, int C, int H, int W, arflow_stream_t stream) {
   af_clear_stale_error();
-  AF_REQUIRE_PTR(im);
-  AF_REQUIRE_PTR(recons);
   AF_REQUIRE_PTR(sums);
-  AF_REQUIRE(B > 0 && C > 0 && H >= 3 && W >= 3 && B <= 65535, ARFLOW_ESHAPE);
-  hipStream_t st = (hipStream_t)stream;
+  const int rc = photo_check(im, recons, B, C, H, W);
+  if (rc != ARFLOW_OK) return rc;
   const int nrows = af_sums_rows(B, H, W);
-  if ((W & 3) == 0) {
-    namespace p4 = photo4;
-    dim3 g4(af_grid_for_tiles((long)af_cdiv(W, p4::TXW) * af_cdiv(H, p4::TYH) * B));
-    hipLaunchKernelGGL(p4::fwd_kernel, g4, dim3(p4::NT), 0, st, im, recons, mask, ssim_map, sums, nrows, B, C, H, W);
-    return af_launch_status();
-  }
-  dim3 grid(af_grid_for_tiles((long)af_cdiv(W, TX) * af_cdiv(H, TY) * B));
-  hipLaunchKernelGGL(photo_fwd_kernel, grid, dim3(TX * TY), 0, st, im, recons, mask, ssim_map, sums, nrows, B, C, H, W);
+  const bool four = photo_four(W);
+  hipLaunchKernelGGL(four ? photo4::fwd_kernel : photo_fwd_kernel, four ? grid4(B, H, W) : grid1(B, H, W), dim3(photo4::NT),
+                     0, (hipStream_t)stream, im, recons, mask, ssim_map, sums, nrows, B, C, H, W);
   return af_launch_status();
 }
 
@@ -402,20 +294,12 @@ extern "C" int arflow_photo_bwd(const float* im, const float* recons, const floa
                                 const float* coef, float* g_recons, int B, int C, int H, int W,
                                 arflow_stream_t stream) {
   af_clear_stale_error();
-  AF_REQUIRE_PTR(im);
-  AF_REQUIRE_PTR(recons);
   AF_REQUIRE_PTR(coef);
   AF_REQUIRE_PTR(g_recons);
-  AF_REQUIRE(B > 0 && C > 0 && H >= 3 && W >= 3 && B <= 65535, ARFLOW_ESHAPE);
-  if ((W & 3) == 0) {
-    namespace p4 = photo4;
-    dim3 g4(af_grid_for_tiles((long)af_cdiv(W, p4::TXW) * af_cdiv(H, p4::TYH) * B));
-    hipLaunchKernelGGL(p4::bwd_kernel, g4, dim3(p4::NT), 0, (hipStream_t)stream, im, recons, mask, gmap, coef, g_recons, B,
-                       C, H, W);
-    return af_launch_status();
-  }
-  dim3 grid(af_grid_for_tiles((long)af_cdiv(W, TX) * af_cdiv(H, TY) * B));
-  hipLaunchKernelGGL(photo_bwd_kernel, grid, dim3(TX * TY), 0, (hipStream_t)stream, im, recons, mask, gmap,
-                     coef, g_recons, B, C, H, W);
+  const int rc = photo_check(im, recons, B, C, H, W);
+  if (rc != ARFLOW_OK) return rc;
+  const bool four = photo_four(W);
+  hipLaunchKernelGGL(four ? photo4::bwd_kernel : photo_bwd_kernel, four ? grid4(B, H, W) : grid1(B, H, W), dim3(photo4::NT),
+                     0, (hipStream_t)stream, im, recons, mask, gmap, coef, g_recons, B, C, H, W);
   return af_launch_status();
 }
