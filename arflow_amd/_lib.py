@@ -97,6 +97,9 @@ PROTOTYPES = {
     'arflow_up4_clamp_mul': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'arflow_flow_eval_rows': [c_i, c_i],
     'arflow_flow_eval': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_triag_solve': [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_triag_solve_bwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_triag_inverse_diagonal': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
 }
 
 ABI_VERSION = 10

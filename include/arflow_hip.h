@@ -514,6 +514,34 @@ int arflow_flow_eval_rows(int H, int W);
 int arflow_flow_eval(const float* pred, const float* gt, const float* move, double* rows, float* epe_map, int B, int h,
                      int w, int C, int H, int W, arflow_stream_t stream);
 
+/* ---- sparse triangular solves on the pixel grid -----------------------------------------------------------
+ * forward_substitution / backward_substitution / inverse_diagonal of utils/triag_solve.py:76-115 and utils/triag_solve/
+ * triag_solve_cuda.cu:72-139: the sparse Cholesky factor of the precision of losses/uflow_elbo_loss.py:149-157, a pixel
+ * coupled to three neighbours.  P = K * L planes, fp32, contiguous: A [P,M,N], B [P,M,N-1], C [P,M-1,N], D [P,M-1,N-1].
+ *   lower (upper = 0): A[i,j] y[i,j] + B[i,j-1] y[i,j-1] + C[i-1,j] y[i-1,j] + D[i-1,j-1] y[i-1,j-1] = x[i,j]   (:84-92)
+ *   upper (upper = 1): A[i,j] y[i,j] + B[i,j] y[i,j+1] + C[i,j] y[i+1,j] + D[i,j] y[i+1,j+1] = x[i,j]           (:105-113)
+ * One wave per plane, one lane per row, rows skewed by one column each so that the wave walks the anti-diagonals; rows
+ * beyond 64 in further strips of the same wave: ceil(M / 64) * (N + 63) dependent steps, not M * N.
+ * Per element the rounded C, B and D products are subtracted in the reference's order and the result is divided by A
+ * (IEEE): the bits of the reference's fp32 CPU run, on every run and in either mode (no atomics).
+ * arflow_triag_solve: Y = J^-1 X.  D may be NULL (zero); B, C, D may be NULL where they have no elements (N == 1, M == 1).
+ * arflow_triag_solve_bwd: the whole backward of ForwardSubst (upper = 0) / BackwardSubst (upper = 1) of :163-202 in one
+ *   launch.  Y: the forward's result.  gX = the solve of the transposed system (the opposite triangle, the same arrays) on
+ *   gY; gA = -gX * Y, and gB, gC, gD the products of :178-180 / :199-201, stored as the sweep produces gX: every element
+ *   of all five is stored.  gD is NULL exactly when D is (ARFLOW_ENULL / ARFLOW_EPARAM otherwise); gB, gC as B, C.
+ * arflow_triag_inverse_diagonal: H[p,k,l] = |J^-1 e_(k,l)|^2 for the lower form without D = the diagonal of (J J^T)^-1
+ *   (marginal_variances, :205-218).  One wave per source pixel on the rows >= k and columns >= l its solution can reach;
+ *   the squares are summed in registers -- no scratch tensor.
+ * Limits (ARFLOW_ESHAPE beyond them): M <= 16384, N <= 8192 (a strip's last row is kept in LDS), and for
+ * arflow_triag_inverse_diagonal P * M * N < 2^31.  X and Y (gY and gX) must not overlap. */
+int arflow_triag_solve(const float* A, const float* B, const float* C, const float* D, const float* X, float* Y, int P,
+                       int M, int N, int upper, arflow_stream_t stream);
+int arflow_triag_solve_bwd(const float* A, const float* B, const float* C, const float* D, const float* Y, const float* gY,
+                           float* gX, float* gA, float* gB, float* gC, float* gD, int P, int M, int N, int upper,
+                           arflow_stream_t stream);
+int arflow_triag_inverse_diagonal(const float* A, const float* B, const float* C, float* H, int P, int M, int N,
+                                  arflow_stream_t stream);
+
 /* ---- the rest of the reference's parameter space (no shipped config uses these values; plain kernels) ----------
  * flow_warp(mode='nearest') (utils/warp_utils.py:83-90 -> grid_sample nearest: border clips the coordinate, index =
  * nearbyint, out of range reads 0).  No gradient w.r.t. the flow (grid_sample's nearest mode has none). */

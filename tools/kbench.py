@@ -291,6 +291,27 @@ def main():
         rec('arflow_down4', (B * 3, H0, W0), timeit(lambda: lib.arflow_down4(p(im1), p(sm), B * 3, H0, W0, s), args.iters))
     if want('up4'):
         rec('arflow_up4_clamp_mul', (B, H0 // 4, W0 // 4), timeit(lambda: lib.arflow_up4_clamp_mul(p(sm), p(mask), p(dham), B, H0 // 4, W0 // 4, s), args.iters))
+    if want('triag'):  # the sparse triangular solves (csrc/triag.hip) at the 1/4-resolution grid of the flagship: 2 * batch * nsamples planes
+        for P, M, N in ((16, H0 // 4, W0 // 4), (64, H0 // 4, W0 // 4), (16, H0 // 16, W0 // 16), (64, H0 // 16, W0 // 16)):
+            A = torch.exp(0.4 * torch.randn(1, P, M, N, device=dev, generator=g))
+            Bc, Cc, Dc = [0.6 * torch.rand(1, P, M - i, N - j, device=dev, generator=g) - 0.3 for i, j in ((0, 1), (1, 0), (1, 1))]
+            X = torch.randn(1, P, M, N, device=dev, generator=g)
+            Y, gX, gA, gB, gC, gD = [torch.empty_like(t) for t in (X, X, A, Bc, Cc, Dc)]
+            steps = -(-M // 64) * (N + 63)  # the dependent chain
+
+            def trec(name, us, floats):
+                MANIFEST[-1].update(name=name, shape=[P, M, N], us=us)
+                gbs = 4 * floats / us / 1e3
+                print('%-22s %-26s %9.1f us %9.1f GB/s  %5.1f%% of HBM peak  (%d dependent steps, %.0f ns each)' % (
+                    name, [P, M, N], us, gbs, 100 * gbs / HBM_PEAK_GBS, steps, 1e3 * us / steps), flush=True)
+            if (M, N) == (H0 // 4, W0 // 4):  # the solves at the small grid are launch-bound: not timed
+                for upper in (0, 1):
+                    trec('arflow_triag_solve' + ('/upper' if upper else ''), timeit(lambda: lib.arflow_triag_solve(
+                        p(A), p(Bc), p(Cc), p(Dc), p(X), p(Y), P, M, N, upper, s), args.iters), 6 * P * M * N)
+                trec('arflow_triag_solve_bwd', timeit(lambda: lib.arflow_triag_solve_bwd(
+                    p(A), p(Bc), p(Cc), p(Dc), p(Y), p(X), p(gX), p(gA), p(gB), p(gC), p(gD), P, M, N, 0, s), args.iters), 11 * P * M * N)
+            trec('arflow_triag_inverse_diagonal', timeit(lambda: lib.arflow_triag_inverse_diagonal(
+                p(A), p(Bc), p(Cc), p(gA), P, M, N, s), max(3, args.iters // 10)), 4 * P * M * N)
     if args.manifest:
         json.dump(MANIFEST, open(args.manifest, 'w'), indent=1)
     if not rows:  # only ops that keep their own byte model (the head convolutions) were selected
