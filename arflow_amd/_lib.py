@@ -65,6 +65,9 @@ PROTOTYPES = {
     'arflow_headconv_bwd_data': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
     'arflow_headconv_bwd_weight_ws_bytes': [c_i, c_i, c_i, c_i],
     'arflow_headconv_bwd_weight': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_splitconv_pack_bytes': [c_i, c_i],
+    'arflow_splitconv_pack': [c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'arflow_splitconv_fwd': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_dense_cat_fwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_l, c_f, c_fp],
     'arflow_dense_gbias_rows': [c_i, c_l],
     'arflow_dense_grad_gather': [c_fp, c_i, c_fp, c_l, c_fp, c_fp, c_i, c_i, c_l, c_f, c_fp],
@@ -127,7 +130,7 @@ def load():
     for name, argtypes in PROTOTYPES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
-        fn.restype = c_l if name.endswith('_ws_bytes') else c_i
+        fn.restype = c_l if name.endswith(('_ws_bytes', '_pack_bytes')) else c_i
     lib.arflow_strerror.argtypes = [c_i]
     lib.arflow_strerror.restype = ctypes.c_char_p
     if lib.arflow_abi_version() != ABI_VERSION:

@@ -1,0 +1,299 @@
+// 3x3 convolution (stride 1, zero padding 1, dilation 1) of the WIDE layers on the bf16 matrix cores at fp32 accuracy, for
+// gfx950: the dense flow estimators' 147..563 -> 128..32 layers and the context network's 597 -> 128, forward and -- with
+// the roles of the channel axes swapped and the taps flipped by the packer -- data gradient.
+//
+// Arithmetic.  An fp32 number splits EXACTLY into three bf16 numbers, b0 = bf16(x), b1 = bf16(x - b0), b2 = bf16(x - b0 - b1)
+// (round to nearest even; both subtractions are exact, b0 + b1 + b2 == x bit for bit).  A product x * w is then nine bf16
+// products, each exact in the MFMA's fp32 accumulator; the three smallest (b1 w2, b2 w1, b2 w2) are below 2^-24 of the
+// product and dropped, the other six are accumulated: (w2,x0) (w1,x1) (w0,x2) (w1,x0) (w0,x1) and (w0,x0).
+// Six v_mfma_f32_32x32x16_bf16 per 32x32x16 block of fp32-accurate products: 1/6 of the bf16 rate, 2.7x the fp32 MFMA's.
+//
+// GEMM view: D[k][pixel] = sum over (tap, c) of A[k][(tap, c)] * B[(tap, c)][pixel].  A = weights, packed once per call by
+// arflow_splitconv_pack into the three bf16 planes IN FRAGMENT ORDER (a wave's A fragment is 1 KiB contiguous, read straight
+// from L2); B = the input: per block of 32 input channels a workgroup loads its halo tile from NCHW, splits every value in
+// registers and stores the planes to LDS as [pixel][plane][channel], so that a lane's B fragment (8 consecutive channels of
+// one pixel) is one ds_read_b128 and a tap is a pixel offset, not a re-load.  The pixel stride is 3 * 64 + 16 bytes = 13
+// 16-byte slots: odd, so the 16 lanes ds_read_b128 serves together fall on 16 different slots of the 256-byte bank row.
+//
+// A workgroup of 4 waves owns 8 pixel tiles (32 pixels each: PW columns x 32 / PW rows, stacked vertically) and KT <= 2
+// tiles of 32 output channels; a wave holds 2 pixel tiles x KT channel tiles, twice: the accumulators of the current block
+// and the running totals, up to 128 registers.  Two workgroups share a CU (2 x 70 KB of LDS, 256 registers per lane): one
+// stages its next block while the other multiplies.  More than 64 output channels go over gridDim.y in chunks of equal
+// size (+-1 tile: no tile of zeros is multiplied).
+//
+// Summation order is fixed.  Within a block of 32 input channels one MFMA accumulator chain starts from zero and takes, over
+// taps row-major and 16-channel steps ascending, FIRST the five small products of every step -- (w2,x0) (w1,x1) (w0,x2)
+// (w1,x0) (w0,x1), together 2^-8 of the block's sum, so that their 90 roundings are negligible -- and THEN the 18 (w0,x0)
+// products; the blocks' sums are added to the running total in ascending order with plain fp32 adds.  (An MFMA rounds at
+// the accumulator's magnitude whatever it adds: one chain over all blocks with the six products interleaved has six full
+// roundings per 16 terms where an fp32 kernel has one.  Emulated at 597 x 9 all-positive terms: 27 u of sum |a b| for
+// that, 13 u for fp32 partial sums of 16, 4.7 u with the per-block restart, and with the small products first as well
+// the figure in tests/test_splitconv_cpu.py.)  No atomics, no split of the reduction: two calls are bitwise equal, in
+// every mode.
+#include <climits>
+#include <cstdint>
+
+#include "common.hpp"
+
+namespace {
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int NT = 256;                       // 4 waves
+constexpr int CB = 32;                        // input channels per LDS block (two MFMA k-steps)
+constexpr int PLANE_BYTES = CB * 2;           // one pixel's channels of one plane
+constexpr int PIX_BYTES = 3 * PLANE_BYTES + 16;  // 208: see the header
+constexpr int FRAG = 64 * 8;                  // bf16 per wave fragment (32 rows x 16 k)
+constexpr int MAX_KT = 2;                     // output-channel tiles per workgroup (template KT: 1 or 2)
+
+template <int PW>
+struct Geo {
+  static constexpr int PR = 32 / PW;    // rows of a pixel tile
+  static constexpr int TH = 8 * PR;     // rows of the workgroup's tile
+  static constexpr int HW = PW + 2;     // halo tile
+  static constexpr int HH = TH + 2;
+  static constexpr int NPIX = HH * HW;  // 340 / 324 / 340 for PW = 32 / 16 / 8
+  static constexpr int LDS_BYTES = NPIX * PIX_BYTES;
+};
+
+struct Split {
+  __bf16 p[3];
+  __device__ __forceinline__ explicit Split(float v) {
+    p[0] = (__bf16)v;
+    const float r1 = v - (float)p[0];
+    p[1] = (__bf16)r1;
+    p[2] = (__bf16)(r1 - (float)p[1]);
+  }
+};
+
+// packed: [plane 3][tap 9][nkt = ceil(K / 32)][ncs = 2 ceil(C / 32)][lane 64][8], element j of lane (r = lane & 31, h = lane >> 5)
+// = plane of W[k = 32 kt + r][c = 16 cs + 8 h + j][tap], zero where k >= K or c >= C.  transpose_flip: W = w'[c][k][8 - tap].
+__global__ __launch_bounds__(NT) void splitconv_pack_kernel(const float* __restrict__ w, bf16x8* __restrict__ packed, int wK, int wC,
+                                                            int Kout, int Cin, int nkt, int ncs, int transpose_flip) {
+  const int nfrag = 9 * nkt * ncs * 64;
+  const int f = blockIdx.x * NT + threadIdx.x;
+  if (f >= nfrag) return;
+  const int lane = f & 63, cs = (f >> 6) % ncs, kt = ((f >> 6) / ncs) % nkt, tap = (f >> 6) / (ncs * nkt);
+  const int k = 32 * kt + (lane & 31), c0 = 16 * cs + 8 * (lane >> 5);
+  bf16x8 o[3];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = c0 + j;
+    float v = 0.f;
+    if (k < Kout && c < Cin) v = transpose_flip ? w[((long)c * wC + k) * 9 + (8 - tap)] : w[((long)k * wC + c) * 9 + tap];
+    const Split s(v);
+    o[0][j] = s.p[0], o[1][j] = s.p[1], o[2][j] = s.p[2];
+  }
+#pragma unroll
+  for (int p = 0; p < 3; ++p) packed[(long)p * nfrag + f] = o[p];
+}
+
+template <int KT, int PW>
+__global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restrict__ x, const bf16x8* __restrict__ packed,
+                                                          float* __restrict__ y, int C, int K, int H, int W, int nkt, int ncs,
+                                                          int kt_first, int tiles_x, int tiles_y) {
+  using G = Geo<PW>;
+  extern __shared__ __align__(16) unsigned char lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, hh = lane >> 5;
+  const int t = blockIdx.x;
+  const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, n = t / (tiles_x * tiles_y);
+  const int h0 = ty * G::TH, w0 = tx * PW;
+  const int kt0 = kt_first + blockIdx.y * KT;
+  const long plane_frags = (long)9 * nkt * ncs * 64;  // fragments (of 8 bf16) per plane
+
+  f32x16 tot[2][KT];  // running totals; every block of 32 input channels is summed in fresh accumulators first
+#pragma unroll
+  for (int pt = 0; pt < 2; ++pt)
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) tot[pt][kt][i] = 0.f;
+
+  // the lane's pixel in each of the wave's two pixel tiles: halo-tile byte offset of tap (0, 0), plus its k half
+  int pbase[2], prow[2], pcol;
+  pcol = r % PW;
+#pragma unroll
+  for (int pt = 0; pt < 2; ++pt) {
+    prow[pt] = (2 * wv + pt) * G::PR + r / PW;
+    pbase[pt] = (prow[pt] * G::HW + pcol) * PIX_BYTES + hh * 16;
+  }
+  const float* xn = x + (long)n * C * H * W;
+  const long HWl = (long)H * W;
+
+  for (int cb = 0; cb < C; cb += CB) {
+    if (cb) __syncthreads();  // every wave is done with the previous block's planes
+    // ---- stage: 8 channels of one halo pixel per item, split, one 16-byte store per plane
+#pragma unroll 3  // 24 loads of a lane in flight together (all 48: spills at KT = 2)
+    for (int it = 0; it < (4 * G::NPIX + NT - 1) / NT; ++it) {
+      const int i = tid + it * NT;
+      if (i >= 4 * G::NPIX) break;
+      const int g = i / G::NPIX, pix = i - g * G::NPIX;
+      const int row = pix / G::HW, col = pix - row * G::HW;
+      const int gh = h0 - 1 + row, gw = w0 - 1 + col;
+      const bool inb = gh >= 0 && gh < H && gw >= 0 && gw < W;
+      const int c0 = cb + 8 * g;
+      const float* src = xn + (long)c0 * HWl + (inb ? gh * W + gw : 0);
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (inb && c0 + e < C) ? src[e * HWl] : 0.f;
+      bf16x8 o[3];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const Split s(v[e]);
+        o[0][e] = s.p[0], o[1][e] = s.p[1], o[2][e] = s.p[2];
+      }
+      unsigned char* dst = lds + pix * PIX_BYTES + g * 16;
+#pragma unroll
+      for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(dst + p * PLANE_BYTES) = o[p];
+    }
+    __syncthreads();
+    // ---- multiply: two passes of 9 taps x 2 k-steps; weight fragments from L2, pixel fragments from LDS, 12 KT MFMAs per step
+    const bf16x8* wblk = packed + ((long)kt0 * ncs + cb / 16) * 64 + lane;
+    f32x16 acc[2][KT];
+#pragma unroll
+    for (int pt = 0; pt < 2; ++pt)
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[pt][kt][i] = 0.f;
+    // pass 0: the five small products of every tap and step, while the accumulator is small (their roundings are 2^-8 of the
+    // block's sum); pass 1: the (w0, x0) products on top -- 18 roundings at the block's magnitude instead of 108
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+      constexpr int NP[2] = {3, 1}, Q0[2] = {0, 5}, Q1[2] = {5, 6};
+#pragma unroll 1  // a row of taps per trip: unrolled further, the scheduler hoists pass 1's loads until registers spill
+      for (int trow = 0; trow < 3; ++trow)
+#pragma unroll
+      for (int tcol = 0; tcol < 3; ++tcol) {
+        const int tap = 3 * trow + tcol;
+        const int toff = (trow * G::HW + tcol) * PIX_BYTES;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          bf16x8 a[KT][3], b[2][3];
+#pragma unroll
+          for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+            for (int p = 0; p < NP[pass]; ++p) a[kt][p] = wblk[p * plane_frags + ((long)(tap * nkt + kt) * ncs + s) * 64];
+#pragma unroll
+          for (int pt = 0; pt < 2; ++pt)
+#pragma unroll
+            for (int p = 0; p < NP[pass]; ++p)
+              b[pt][p] = *reinterpret_cast<const bf16x8*>(lds + pbase[pt] + toff + p * PLANE_BYTES + s * 32);
+#pragma unroll
+          for (int q = Q0[pass]; q < Q1[pass]; ++q) {  // (weight plane, input plane), smallest product first
+            constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+#pragma unroll
+            for (int pt = 0; pt < 2; ++pt)
+#pragma unroll
+              for (int kt = 0; kt < KT; ++kt)
+                acc[pt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kt][PA[q]], b[pt][PB[q]], acc[pt][kt], 0, 0, 0);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int pt = 0; pt < 2; ++pt)
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt) tot[pt][kt] = tot[pt][kt] + acc[pt][kt];
+  }
+  // ---- store: accumulator register i of lane (r, hh) is output channel (i & 3) + 8 (i >> 2) + 4 hh of its tile, pixel r
+  float* yn = y + (long)n * K * HWl;
+  const int gw = w0 + pcol;
+#pragma unroll
+  for (int pt = 0; pt < 2; ++pt) {
+    const int gh = h0 + prow[pt];
+    if (gh >= H || gw >= W) continue;
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int k = 32 * (kt0 + kt) + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        if (k < K) yn[(long)k * HWl + gh * W + gw] = tot[pt][kt][i];
+      }
+  }
+}
+
+inline int tiles32(int n) { return (n + 31) / 32; }
+inline bool pack_shape_ok(int K, int C) {
+  return K > 0 && C > 0 && (long)K * C * 9 <= INT_MAX && (long)9 * tiles32(K) * 2 * tiles32(C) * 64 <= INT_MAX / 8;
+}
+
+template <int KT, int PW>
+int launch(const float* x, const bf16x8* packed, float* y, int N, int C, int K, int H, int W, int kt_first, int chunks,
+           hipStream_t st) {
+  using G = Geo<PW>;
+  static bool attr_set = false;  // more than 64 KB of dynamic LDS has to be asked for once per kernel
+  if (!attr_set) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&splitconv_kernel<KT, PW>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+    if (e != hipSuccess) return af_hip_status(e);
+    attr_set = true;
+  }
+  const int tx = (W + PW - 1) / PW, ty = (H + G::TH - 1) / G::TH;
+  const dim3 grid((unsigned)((long)N * tx * ty), (unsigned)chunks);
+  hipLaunchKernelGGL((splitconv_kernel<KT, PW>), grid, dim3(NT), G::LDS_BYTES, st, x, packed, y, C, K, H, W, tiles32(K),
+                     2 * tiles32(C), kt_first, tx, ty);
+  return af_launch_status();
+}
+
+template <int PW>
+int launch_kt(int KT, const float* x, const bf16x8* packed, float* y, int N, int C, int K, int H, int W, int kt_first, int chunks,
+              hipStream_t st) {
+  return KT == 1 ? launch<1, PW>(x, packed, y, N, C, K, H, W, kt_first, chunks, st)
+                 : launch<2, PW>(x, packed, y, N, C, K, H, W, kt_first, chunks, st);
+}
+}  // namespace
+
+extern "C" long arflow_splitconv_pack_bytes(int K, int C) {
+  if (!pack_shape_ok(K, C)) return ARFLOW_ESHAPE;
+  return (long)3 * 9 * tiles32(K) * 2 * tiles32(C) * FRAG * 2;
+}
+
+extern "C" int arflow_splitconv_pack(const float* w, void* packed, int K, int C, int transpose_flip, arflow_stream_t stream) {
+  af_clear_stale_error();
+  AF_REQUIRE_PTR(w);
+  AF_REQUIRE_PTR(packed);
+  AF_REQUIRE(pack_shape_ok(K, C), ARFLOW_ESHAPE);
+  AF_REQUIRE(transpose_flip == 0 || transpose_flip == 1, ARFLOW_EPARAM);
+  AF_REQUIRE(((uintptr_t)packed & 15) == 0, ARFLOW_EPARAM);
+  const int Kout = transpose_flip ? C : K, Cin = transpose_flip ? K : C;
+  const int nkt = tiles32(Kout), ncs = 2 * tiles32(Cin);
+  const int nfrag = 9 * nkt * ncs * 64;
+  hipLaunchKernelGGL(splitconv_pack_kernel, dim3((unsigned)af_cdiv(nfrag, NT)), dim3(NT), 0, (hipStream_t)stream, w,
+                     (bf16x8*)packed, K, C, Kout, Cin, nkt, ncs, transpose_flip);
+  return af_launch_status();
+}
+
+extern "C" int arflow_splitconv_fwd(const float* x, const void* packed, float* y, int N, int C, int K, int H, int W,
+                                    arflow_stream_t stream) {
+  af_clear_stale_error();
+  AF_REQUIRE_PTR(x);
+  AF_REQUIRE_PTR(packed);
+  AF_REQUIRE_PTR(y);
+  AF_REQUIRE(N > 0 && C > 0 && K > 0 && H > 0 && W > 0, ARFLOW_ESHAPE);
+  AF_REQUIRE((long)N * C * H * W <= INT_MAX && (long)N * K * H * W <= INT_MAX && pack_shape_ok(K, C), ARFLOW_ESHAPE);
+  AF_REQUIRE(((uintptr_t)packed & 15) == 0, ARFLOW_EPARAM);
+  // pixel tile: 32 x 1 where the rows are long enough, else 16 x 2 or 8 x 4 (fewer columns of padding at W = 80, 40, 20)
+  const auto waste = [&](int pw) {
+    const int th = 8 * (32 / pw);
+    return (long)((W + pw - 1) / pw * pw) * ((H + th - 1) / th * th);
+  };
+  int PW = 32;
+  if (waste(16) < waste(PW)) PW = 16;
+  if (waste(8) < waste(PW)) PW = 8;
+  // output-channel tiles in chunks of at most MAX_KT: `extra` chunks of base + 1 tiles, then the rest of base tiles
+  const int nkt = tiles32(K), chunks = (nkt + MAX_KT - 1) / MAX_KT, base = nkt / chunks, extra = nkt % chunks;
+  const bf16x8* pk = (const bf16x8*)packed;
+  hipStream_t st = (hipStream_t)stream;
+  for (int part = 0; part < 2; ++part) {
+    const int kt = part == 0 ? base + 1 : base, cnt = part == 0 ? extra : chunks - extra, first = part == 0 ? 0 : extra * (base + 1);
+    if (cnt == 0) continue;
+    int rc;
+    if (PW == 32) rc = launch_kt<32>(kt, x, pk, y, N, C, K, H, W, first, cnt, st);
+    else if (PW == 16) rc = launch_kt<16>(kt, x, pk, y, N, C, K, H, W, first, cnt, st);
+    else rc = launch_kt<8>(kt, x, pk, y, N, C, K, H, W, first, cnt, st);
+    if (rc != ARFLOW_OK) return rc;
+  }
+  return ARFLOW_OK;
+}

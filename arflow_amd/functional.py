@@ -688,6 +688,102 @@ def head_conv_enabled():
 
 
 # ------------------------------------------------------------------------------------------------
+# Wide 3x3 convolutions on the bf16 matrix cores at fp32 accuracy (csrc/splitconv.hip)
+_SPLITCONV = __import__('os').environ.get('ARFLOW_SPLITCONV', '1') != '0'  # A/B switch for tools/ and tests: 0 = MIOpen
+
+
+def splitconv_enabled():
+    return _SPLITCONV
+
+
+def splitconv_takes(N, C, K, H, W):
+    """Whether ONE convolution call -- x: [N,C,H,W] -> y: [N,K,H,W], 3x3, stride 1, padding 1 -- goes to the split-bf16 kernel.
+    A layer's forward asks with its own (C, K), its data gradient with the two swapped: that is the call the kernel sees.
+    The rule is read off profiles/splitconv_kbench.log: the kernel is taken only where it beat
+    MIOpen's best solver by more than the spread of both."""
+    if not _SPLITCONV:
+        return False
+    return _splitconv_rule(int(N), int(C), int(K), int(H), int(W))
+
+
+def _splitconv_rule(N, C, K, H, W):
+    # measured at N = 16, channels 32 .. 597: faster on every call at 96x160 (1.13x .. 1.45x); at 48x80 on the calls with 128
+    # output channels or at most 128 input channels (1.16x .. 1.50x; 403->96, 499->64, 563->32 forward and 64<->32 are not);
+    # at 24x40 and 12x20 on none (the tiles do not fill the chip)
+    if min(C, K) < 32 or not 64 <= max(C, K) <= 640:
+        return False
+    if H * W >= 96 * 160 and N * H * W >= 16 * 96 * 160:
+        return True
+    if H * W >= 48 * 80 and N * H * W >= 16 * 48 * 80:
+        return max(C, K) >= 128 and (K >= 128 or C <= 128)
+    return False
+
+
+def splitconv(x, w, transpose_flip=False):
+    """conv2d(x, w, padding=1) through arflow_splitconv_pack + arflow_splitconv_fwd (no autograd); transpose_flip: the data
+    gradient of that convolution for x = dy, i.e. conv2d(x, w.transpose(0, 1).flip(2, 3), padding=1)."""
+    _need_gpu(x, w)
+    if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or x.shape[1] != w.shape[0 if transpose_flip else 1]:
+        raise ValueError('splitconv expects x [N,C,H,W] and w [K,C,3,3] (transpose_flip: x [N,K,H,W])')
+    x, w = x.contiguous(), w.contiguous()
+    N, C, H, W = x.shape
+    K = int(w.shape[1 if transpose_flip else 0])
+    nbytes = _lib.load().arflow_splitconv_pack_bytes(K, C)
+    if nbytes < 0:
+        _lib.check(int(nbytes), 'arflow_splitconv_pack_bytes')
+    packed = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    y = torch.empty(N, K, H, W, device=x.device, dtype=torch.float32)
+    with torch.cuda.device_of(x):
+        _call('arflow_splitconv_pack', _p(w), _p(packed), int(w.shape[0]), int(w.shape[1]), int(bool(transpose_flip)), _stream())
+        _call('arflow_splitconv_fwd', _p(x), _p(packed), _p(y), N, C, K, H, W, _stream())
+    return y
+
+
+def _conv_args():
+    return [1, 1], [1, 1], [1, 1], False, [0, 0], 1  # stride, padding, dilation, transposed, output_padding, groups
+
+
+class Conv3x3Function(torch.autograd.Function):
+    """y = conv2d(x, w, None, 1, 1) for a 3x3 kernel as one autograd node.  `fwd` / `dgrad` say which of the forward and the
+    data gradient run the split-bf16 kernel; the other one, and always the weight gradient, are the calls F.conv2d and its
+    autograd make (aten.convolution / aten.convolution_backward: the same MIOpen problem keys as before)."""
+
+    @staticmethod
+    def forward(ctx, x, w, fwd, dgrad):
+        if fwd:
+            y = splitconv(x, w)
+        else:
+            y = torch.ops.aten.convolution(x, w, None, *_conv_args())
+        ctx.save_for_backward(x, w)
+        ctx.dgrad = bool(dgrad)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = gy.contiguous()
+        want_dx, want_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dx = dw = None
+        if ctx.dgrad and want_dx:
+            dx = splitconv(gy, w, transpose_flip=True)
+            want_dx = False
+        if want_dx or want_dw:
+            dx_m, dw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, *_conv_args(), [want_dx, want_dw, False])
+            if want_dx:
+                dx = dx_m
+            if not want_dw:
+                dw = None
+        return dx, dw, None, None
+
+
+def conv3x3(x, w, fwd=True, dgrad=True):
+    """conv2d(x, w, padding=1), 3x3: forward and data gradient on the split-bf16 kernel (each can be left to MIOpen), weight
+    gradient MIOpen's."""
+    return Conv3x3Function.apply(x, w, bool(fwd), bool(dgrad))
+
+
+# ------------------------------------------------------------------------------------------------
 # The dense flow estimator as one autograd node (csrc/dense.hip)
 _DENSE_BLOCK = __import__('os').environ.get('ARFLOW_DENSE_BLOCK', '1') != '0'  # A/B switch for tools/ and tests: 0 = composed path
 DENSE_MAX_SRC = 8  # ARFLOW_DENSE_MAX_SRC of include/arflow_hip.h
@@ -779,7 +875,8 @@ class DenseEstimatorFunction(torch.autograd.Function):
         for k in 1..5:  x_{k+1} = cat([leaky_relu(conv2d(x_k, w_k) + b_k), x_k], 1)
         flow = conv2d(x_6, w_head) + b_head                         -> (x_6, flow)
 
-    The convolutions stay MIOpen's (bias-free F.conv2d forward, aten.convolution_backward backward: the calls autograd makes);
+    The convolutions are the calls the composed path makes (bias-free F.conv2d forward, aten.convolution_backward backward, or
+    the split-bf16 kernel where splitconv_takes routes ConvAct's forward / data gradient to it);
     arflow_dense_cat_fwd writes activation and input into their slots of the next tensor, and backward the gradient of layer
     m's activation is gathered by ONE launch from every tensor that holds a slice of it -- the gradient of x_6, the head's
     data gradient and the data gradients of the layers above -- in the nesting autograd's accumulation has, so the values
@@ -796,8 +893,12 @@ class DenseEstimatorFunction(torch.autograd.Function):
         w_head, b_head = params[10], params[11]
         xs = [x.contiguous()]
         for w, b in zip(ws, bs):
-            y = torch.nn.functional.conv2d(xs[-1], w, None, 1, 1)
-            xs.append(dense_cat(y, b, xs[-1], slope))
+            xk = xs[-1]
+            if splitconv_takes(xk.shape[0], xk.shape[1], w.shape[0], xk.shape[2], xk.shape[3]):  # ConvAct's routing, same kernel
+                y = splitconv(xk, w)
+            else:
+                y = torch.nn.functional.conv2d(xk, w, None, 1, 1)
+            xs.append(dense_cat(y, b, xk, slope))
         x6 = xs[-1]
         B, C6, H, W = x6.shape
         w_head = w_head.contiguous()
@@ -849,9 +950,14 @@ class DenseEstimatorFunction(torch.autograd.Function):
             gy, gb = dense_grad_gather(srcs, ocs[m - 1], act=xs[m], slope=ctx.slope, want_bias=need[2 * m + 1])
             want_dx = m > lowest
             dx = dw = None
-            if want_dx or need[2 * m]:  # (a layer of which only the bias is trained needs neither)
-                dx, dw, _ = torch.ops.aten.convolution_backward(gy, xs[m - 1], ws[m - 1], None, [1, 1], [1, 1], [1, 1], False,
-                                                                [0, 0], 1, [want_dx, bool(need[2 * m]), False])
+            xm = xs[m - 1]
+            if want_dx and splitconv_takes(B, ocs[m - 1], xm.shape[1], H, W):  # as Conv3x3Function.backward: dx here, dw MIOpen's
+                dx = splitconv(gy, ws[m - 1], transpose_flip=True)
+                if need[2 * m]:
+                    dw = torch.ops.aten.convolution_backward(gy, xm, ws[m - 1], None, *_conv_args(), [False, True, False])[1]
+            elif want_dx or need[2 * m]:  # (a layer of which only the bias is trained needs neither)
+                dx, dw, _ = torch.ops.aten.convolution_backward(gy, xm, ws[m - 1], None, *_conv_args(),
+                                                                [want_dx, bool(need[2 * m]), False])
             grads[2 * m], grads[2 * m + 1] = (dw if need[2 * m] else None), gb
             if want_dx:
                 dxs.append((dx, m))

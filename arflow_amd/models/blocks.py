@@ -18,9 +18,25 @@ class ConvAct(nn.Sequential):
     want_moments = False  # set on the conv that OUTPUTS a pyramid level: its epilogue also leaves that map's moments
     last_moments = None
 
+    def split_route(self, x):
+        """(forward, data gradient) on the split-bf16 kernel (AF.conv3x3): a CUDA fp32 4-D input of a 3x3 / stride 1 / padding 1 /
+        dilation 1 layer under the package's own bias_act -- the conditions HeadConv.native spells out -- at a shape
+        AF.splitconv_takes routes; the data gradient asks with the channel counts swapped, which is the call the kernel sees."""
+        c = self[0]
+        if not (AF.splitconv_enabled() and bias_act is AF.bias_leaky_relu and x.is_cuda and x.dtype == torch.float32 and
+                x.dim() == 4 and c.weight.dtype == torch.float32 and c.kernel_size == (3, 3) and c.stride == (1, 1) and
+                c.padding == (1, 1) and c.dilation == (1, 1) and c.groups == 1 and c.padding_mode == 'zeros'):
+            return False, False
+        N, C, H, W = x.shape
+        return AF.splitconv_takes(N, C, c.out_channels, H, W), AF.splitconv_takes(N, c.out_channels, C, H, W)
+
     def forward(self, x):
         c, act = self[0], self[1]
-        y = F.conv2d(x, c.weight, None, c.stride, c.padding, c.dilation, c.groups)
+        fwd, dgrad = self.split_route(x)
+        if fwd or dgrad:
+            y = AF.conv3x3(x, c.weight, fwd, dgrad)
+        else:
+            y = F.conv2d(x, c.weight, None, c.stride, c.padding, c.dilation, c.groups)
         if self.want_moments and y.is_cuda and bias_act is AF.bias_leaky_relu:
             y, self.last_moments = AF.bias_leaky_relu_moments(y, c.bias, act.negative_slope)
             return y

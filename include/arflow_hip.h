@@ -261,6 +261,26 @@ long arflow_headconv_bwd_weight_ws_bytes(int B, int C, int H, int W);
 int arflow_headconv_bwd_weight(const float* x, const float* dy, float* dw, float* dbias, void* ws, int B, int C, int H,
                                int W, arflow_stream_t stream);
 
+/* ---- wide 3x3 convolution on the bf16 matrix cores at fp32 accuracy -----------------------------
+ * y[n,k] = sum_c x[n,c] * w[k,c] (cross-correlation as conv2d), 3x3, stride 1, zero padding 1, dilation 1, groups 1, no
+ * bias; x: [N,C,H,W], y: [N,K,H,W], packed fp32.  Every fp32 operand is split exactly into three bf16 numbers and six of
+ * the nine bf16 products are accumulated, smallest first, in the MFMA's fp32 accumulator: the accuracy of an fp32 FMA chain
+ * at 1/6 of the bf16 matrix rate.  The summation order is fixed (no atomics, no split of the reduction): two calls are
+ * bitwise equal.
+ *
+ * arflow_splitconv_pack turns the fp32 weights w: [K,C,3,3] into the three bf16 planes in MFMA fragment order,
+ *     packed[plane][tap][K' / 32][C' / 16][lane 64][8],   K' = K padded to 32, C' = C padded to 32, zero in the padding,
+ * element j of lane l = W[32 kt + (l & 31)][16 cs + 8 (l >> 5) + j][tap].  transpose_flip = 0 packs W = w;
+ * transpose_flip = 1 packs W[c][k][r][s] = w[k][c][2-r][2-s], which makes the data gradient the same convolution:
+ * dx = arflow_splitconv_fwd(dy, packed, N, C = K, K = C).  `packed` is 16-byte aligned and holds
+ * arflow_splitconv_pack_bytes(K, C) bytes, K and C being the OUTPUT and INPUT channels of the convolution that will read
+ * it (for transpose_flip = 1: the weights' C and K); < 0 = ARFLOW_ESHAPE.  Weights change every step: pack per call.
+ * ARFLOW_ESHAPE also where N*C*H*W or N*K*H*W exceeds INT_MAX. */
+long arflow_splitconv_pack_bytes(int K, int C);
+int arflow_splitconv_pack(const float* w, void* packed, int K, int C, int transpose_flip, arflow_stream_t stream);
+int arflow_splitconv_fwd(const float* x, const void* packed, float* y, int N, int C, int K, int H, int W,
+                         arflow_stream_t stream);
+
 /* ---- dense flow estimator: concatenating epilogue and gradient gather ---------------------------
  * FlowEstimatorDense (models/pwclite.py:48-66) runs five times x = cat([lrelu(conv(x) + bias), x], 1).
  *

@@ -165,6 +165,64 @@ def main():
             hrec('arflow_headconv_bwd_data', timeit(lambda: lib.arflow_headconv_bwd_data(p(dy), p(wt), p(dx), B2, C, h, w, s), args.iters))
             hrec('arflow_headconv_bwd_weight', timeit(lambda: lib.arflow_headconv_bwd_weight(p(x), p(dy), p(dw), p(db), p(ws), B2, C, h, w, s), args.iters))
             del x, dx, ws
+    if want('splitconv'):  # the wide 3x3 layers on the split-bf16 kernel (csrc/splitconv.hip) next to MIOpen's call, same buffers
+        import torch.nn.functional as F
+        conv_args = ([1, 1], [1, 1], [1, 1], False, [0, 0], 1)
+        layers = ((147, 128), (275, 128), (403, 96), (499, 64), (563, 32), (597, 128), (64, 32))
+        U = 2.0 ** -24
+
+        def sc_call(x, wt, packed, y, tf):
+            N, C, h, w = x.shape
+            K = y.shape[1]
+            lib.arflow_splitconv_pack(p(wt), p(packed), wt.shape[0], wt.shape[1], tf, s)
+            return lib.arflow_splitconv_fwd(p(x), p(packed), p(y), N, C, K, h, w, s)
+
+        def spread(fn):  # three rounds of --iters: (median, min, max) in us
+            ts = sorted(timeit(fn, args.iters) for _ in range(3))
+            MANIFEST[-1].update(name='splitconv', shape=[], us=ts[1])
+            return ts[1], ts[0], ts[2]
+
+        def err_vs_float64(Cl, Kl, h, w):
+            """e = max |err| / S against float64 on the CPU, S the same operation on absolute values; inputs mean 3, std 1; one
+            sample at this resolution (the chain length is set by the channels).  -> (fwd kernel, fwd MIOpen, dgrad kernel, dgrad MIOpen)"""
+            gc = torch.Generator().manual_seed(Cl * 1000 + Kl)
+            x, wt, gy = (3.0 + torch.randn(*sh, generator=gc) for sh in ((1, Cl, h, w), (Kl, Cl, 3, 3), (1, Kl, h, w)))
+            ref_y = F.conv2d(x.double(), wt.double(), None, 1, 1)
+            s_y = F.conv2d(x.double().abs(), wt.double().abs(), None, 1, 1)
+            wT = wt.transpose(0, 1).flip(2, 3).double()
+            ref_dx, s_dx = F.conv2d(gy.double(), wT, None, 1, 1), F.conv2d(gy.double().abs(), wT.abs(), None, 1, 1)
+            xd, wd, gd = x.to(dev), wt.to(dev), gy.to(dev)
+            pk = torch.empty(lib.arflow_splitconv_pack_bytes(max(Cl, Kl), max(Cl, Kl)), device=dev, dtype=torch.uint8)
+            y, dx = torch.empty(1, Kl, h, w, device=dev), torch.empty(1, Cl, h, w, device=dev)
+            assert sc_call(xd, wd, pk, y, 0) == 0 and sc_call(gd, wd, pk, dx, 1) == 0
+            ym = F.conv2d(xd, wd, None, 1, 1)
+            dxm = torch.ops.aten.convolution_backward(gd, xd, wd, None, *conv_args, [True, False, False])[0]
+            e = lambda got, ref, sc: float(((got.double().cpu() - ref).abs() / sc).max()) / U
+            return e(y, ref_y, s_y), e(ym, ref_y, s_y), e(dx, ref_dx, s_dx), e(dxm, ref_dx, s_dx)
+
+        print('splitconv: time in us as median (min .. max) of 3 x %d calls; kernel = pack + forward; TF = fp32-equivalent TFLOP/s of the kernel' % args.iters)
+        for _, h, w in levels[::-1]:
+            for Cl, Kl in layers:
+                x = torch.randn(B2, Cl, h, w, device=dev, generator=g)
+                gy = torch.randn(B2, Kl, h, w, device=dev, generator=g)
+                wt = 0.05 * torch.randn(Kl, Cl, 3, 3, device=dev, generator=g)
+                y, dx = torch.empty_like(gy), torch.empty_like(x)
+                pk = torch.empty(lib.arflow_splitconv_pack_bytes(max(Cl, Kl), max(Cl, Kl)), device=dev, dtype=torch.uint8)
+                assert sc_call(x, wt, pk, y, 0) == 0 and sc_call(gy, wt, pk, dx, 1) == 0
+                flop = 2.0 * B2 * h * w * Cl * Kl * 9
+                for what, mine, theirs in (
+                        ('fwd  ', lambda: sc_call(x, wt, pk, y, 0), lambda: F.conv2d(x, wt, None, 1, 1)),
+                        ('dgrad', lambda: sc_call(gy, wt, pk, dx, 1),
+                         lambda: torch.ops.aten.convolution_backward(gy, x, wt, None, *conv_args, [True, False, False]))):
+                    a, b = spread(mine), spread(theirs)
+                    cin, cout = (Cl, Kl) if what == 'fwd  ' else (Kl, Cl)
+                    print('splitconv %s %-22s kernel %8.1f (%8.1f .. %8.1f)  MIOpen %8.1f (%8.1f .. %8.1f)  %5.2fx  %6.1f TF' % (
+                        what, [B2, cin, cout, h, w], a[0], a[1], a[2], b[0], b[1], b[2], b[0] / a[0], flop / a[0] / 1e6), flush=True)
+                del x, gy, y, dx
+        h, w = levels[0][1], levels[0][2]
+        for Cl, Kl in layers:
+            print('splitconv error %4d->%-4d at 1x%dx%d: fwd %6.2f / %6.2f u   dgrad %6.2f / %6.2f u   (kernel / MIOpen, u = 2^-24)' % (
+                (Cl, Kl, h, w) + err_vs_float64(Cl, Kl, h, w)), flush=True)
     if want('dense'):  # the dense estimator's concatenating epilogue and gradient gather (csrc/dense.hip), five layers x four levels
         import ctypes
         from arflow_amd.functional import _DenseSrc
