@@ -1962,3 +1962,112 @@ def flow_eval_sums(pred, gt, move=None, want_map=False):
                   key=(B, h, w, C, H, W))
         sums = rows.sum(1)  # fixed order: reproducible
     return (sums, epe_map) if want_map else sums
+
+
+# ---- uncertainty metrics ---------------------------------------------------------
+PREP_COLS = 8       # doubles per row of arflow_uncert_prep: min / max of ent_map, min / max of epe_map, sum valid, 0, 0, 0
+SPARSIFY_MAX_K = 32
+CALIB_MAX_EDGES = 128
+
+
+def _valid_plane(gt, B, H, W):
+    """gt (contiguous, or None) -> (pointer of the validity plane of sample 0 or None, batch stride in floats).  A ground
+    truth [B,4,H,W] keeps the mask in channel 2 and it is read where it lies; [B,2,H,W] has none (all ones); [B,1,H,W] is
+    a mask on its own."""
+    if gt is None or (gt.dim() == 4 and gt.shape[1] == 2):
+        return None, 0
+    if gt.dim() != 4 or gt.shape[1] not in (1, 4) or (gt.shape[0], gt.shape[2], gt.shape[3]) != (B, H, W):
+        raise ValueError('expected a ground truth [B,2|4,H,W] or a mask [B,1,H,W] of the maps\' size, got %s'
+                         % (tuple(gt.shape),))
+    C = gt.shape[1]
+    return gt.data_ptr() + (2 * H * W * 4 if C == 4 else 0), C * H * W
+
+
+def _uncert_rows(H, W, which='arflow_uncert_rows'):
+    n = getattr(_lib.load(), which)(int(H), int(W))
+    if n <= 0:
+        _lib.check(n, which)
+    return n
+
+
+def uncert_prep(ent, epe_map, gt=None):
+    """Steps 2-4 of evaluate_uncertainty (utils/flow_utils.py:296-307) in one launch: ent [B,2,h,w] is shifted by
+    -2 log w + 2 log W (channel 0) and -2 log h + 2 log H (channel 1), resized to epe_map's size [B,1,H,W] by the half-pixel
+    bilinear rule and summed over its channels, all in fp32 and in the reference's order.  gt: the ground truth [B,2|4,H,W]
+    whose channel 2 is the validity mask, or None.  -> ent_map [B,1,H,W] fp32, stats [B,5] float64 on the device: min and
+    max of ent_map, min and max of epe_map (over all pixels, masked or not: the bracket of sp_plot, :193-194), sum valid.
+    No autograd, no synchronisation."""
+    import math
+    import numpy as np
+    _need_gpu(ent, epe_map, gt)
+    if ent.dim() != 4 or ent.shape[1] != 2 or epe_map.dim() != 4 or epe_map.shape[:2] != (ent.shape[0], 1):
+        raise ValueError('uncert_prep expects ent [B,2,h,w] and epe_map [B,1,H,W]')
+    B, _, H, W = epe_map.shape
+    h, w = ent.shape[2:]
+    nrows = _uncert_rows(H, W)
+    # a float32 array minus, then plus, a Python float: numpy rounds the scalar to float32 first
+    off = [float(np.float32(2 * math.log(v))) for v in (w, W, h, H)]
+    with torch.no_grad():
+        ent, epe_map = ent.detach().contiguous(), epe_map.detach().contiguous()
+        gt = None if gt is None else gt.detach().contiguous()
+        vp, vs = _valid_plane(gt, B, H, W)
+        rows = torch.empty(B, nrows, PREP_COLS, device=ent.device, dtype=torch.float64)
+        ent_map = torch.empty(B, 1, H, W, device=ent.device, dtype=torch.float32)
+        with torch.cuda.device_of(ent):
+            _call('arflow_uncert_prep', _p(ent), _p(epe_map), vp, vs, _p(ent_map), _p(rows), *off, B, h, w, H, W, _stream(),
+                  key=(B, h, w, H, W))
+        stats = torch.stack([rows[:, :, 0].amin(1), rows[:, :, 1].amax(1), rows[:, :, 2].amin(1), rows[:, :, 3].amax(1),
+                             rows[:, :, 4].sum(1)], 1)
+    return ent_map, stats
+
+
+def sparsify_sums(err, field0, field1, gt, thr, alpha):
+    """The sums of sp_mask and splot (utils/flow_utils.py:187-190, :222) for a whole batch, F fields and K thresholds in one
+    launch: err, field0, field1 (or None: F = 1) [B,1,H,W] fp32; gt as in uncert_prep, or a mask [B,1,H,W]; thr [B,F,K] float64 on the device,
+    K <= 32.  -> [B,F,K,3] float64 on the device: sum (1-m) g, sum m g, sum err m g with m = expit(alpha (thr - field)).
+    No autograd, no synchronisation."""
+    _need_gpu(err, field0, field1, gt)
+    B, one, H, W = err.shape
+    F = 1 if field1 is None else 2
+    if one != 1 or field0.shape != err.shape or (field1 is not None and field1.shape != err.shape):
+        raise ValueError('sparsify_sums expects err, field0, field1 [B,1,H,W]')
+    if thr.dim() != 3 or thr.shape[:2] != (B, F) or thr.dtype != torch.float64 or thr.device != err.device:
+        raise ValueError('sparsify_sums expects thr [B,%d,K] float64 on %s' % (F, err.device))
+    K = thr.shape[2]
+    nrows = _uncert_rows(H, W)
+    with torch.no_grad():
+        err, field0 = err.detach().contiguous(), field0.detach().contiguous()
+        field1 = None if field1 is None else field1.detach().contiguous()
+        gt = None if gt is None else gt.detach().contiguous()
+        thr = thr.detach().contiguous()
+        vp, vs = _valid_plane(gt, B, H, W)
+        rows = torch.empty(B, nrows, F, K, 3, device=err.device, dtype=torch.float64)
+        with torch.cuda.device_of(err):
+            _call('arflow_sparsify_sums', _p(err), _p(field0), _p(field1), vp, vs, _p(thr), float(alpha), _p(rows), B, H, W, K,
+                  _stream(), key=(B, H, W, F, K))
+        return rows.sum(1)  # fixed order: reproducible
+
+
+def calib_hist_sums(pred, gt, ent, edges):
+    """The pooled bins of CalibrationCurve.__call__ (utils/flow_utils.py:237-254) in one launch: pred, ent [B,2,H,W] and
+    gt [B,2|4,H,W] of one size, edges [nb] ascending float64 on the device, nb <= 128.  -> [nb+1,3] float64 on the device:
+    per np.digitize bin of exp(ent) the count, the sum and the sum of squares of |scaled pred - gt| over both channels of all
+    samples (the validity mask is not applied, as in the reference).  No autograd, no synchronisation."""
+    _need_gpu(pred, gt, ent)
+    if pred.dim() != 4 or pred.shape[1] != 2 or gt.dim() != 4 or ent.shape != pred.shape:
+        raise ValueError('calib_hist_sums expects pred, ent [B,2,H,W] and gt [B,C,H,W]')
+    B, C, H, W = gt.shape
+    if tuple(pred.shape) != (B, 2, H, W):
+        raise ValueError('calib_hist_sums: the prediction %s must have the ground truth\'s size %s (the reference indexes '
+                         'the error with the entropy\'s bins)' % (tuple(pred.shape[2:]), (H, W)))
+    if edges.dim() != 1 or edges.dtype != torch.float64 or edges.device != pred.device:
+        raise ValueError('calib_hist_sums expects edges [nb] float64 on %s' % pred.device)
+    nb = edges.shape[0]
+    nrows = _uncert_rows(H, W, 'arflow_calib_rows')
+    with torch.no_grad():
+        pred, gt, ent, edges = (t.detach().contiguous() for t in (pred, gt, ent, edges))
+        rows = torch.empty(B, nrows, nb + 1, 3, device=pred.device, dtype=torch.float64)
+        with torch.cuda.device_of(pred):
+            _call('arflow_calib_hist', _p(pred), _p(gt), _p(ent), _p(edges), _p(rows), B, C, H, W, nb, _stream(),
+                  key=(B, C, H, W, nb))
+        return rows.sum((0, 1))  # fixed order: reproducible

@@ -562,6 +562,37 @@ int arflow_triag_solve_bwd(const float* A, const float* B, const float* C, const
 int arflow_triag_inverse_diagonal(const float* A, const float* B, const float* C, float* H, int P, int M, int N,
                                   arflow_stream_t stream);
 
+/* ---- uncertainty metrics: sparsification curves and the calibration histogram -----------------------------------
+ * The device side of evaluate_uncertainty / sp_plot / CalibrationCurve of utils/flow_utils.py:186-320 (DESIGN.md section
+ * 19).  The `rows` conventions of arflow_flow_eval hold for all three: a row buffer need not be initialised, every row is
+ * stored by exactly one workgroup, no atomics and no zero-fill launch, bitwise reproducible in either mode.
+ * arflow_uncert_prep: ent [B,2,h,w] -> ent_map [B,1,H,W] = sum over the two channels of the bilinear resize (half-pixel
+ *   rule, as arflow_flow_eval) of (ent[:,0] - sub_w) + add_W and (ent[:,1] - sub_h) + add_H, every step rounded to fp32 in
+ *   that order (:296-307; the caller passes (float)(2 log w), (float)(2 log W), (float)(2 log h), (float)(2 log H)).
+ *   rows [B][arflow_uncert_rows(H, W)][8]: min ent_map, max ent_map, min epe_map, max epe_map, sum valid, 0, 0, 0 per tile
+ *   -- columns 0..3 fold with min / max, column 4 with a sum.  epe_map [B,1,H,W] (arflow_flow_eval's output); valid: the
+ *   validity plane of sample 0, sample b at valid + b * valid_bstride (gt + 2 H W with stride C H W), or NULL (all ones).
+ * arflow_sparsify_sums: rows [B][arflow_uncert_rows(H, W)][F][K][3], F = 2 if field1 else 1, 1 <= K <= 32 (else
+ *   ARFLOW_EPARAM): per sample, field and threshold thr[b][f][k] (doubles on the device)
+ *     0 sum (1 - m) g     1 sum m g     2 sum err m g,      m = 1 / (1 + expf(-a)), a = alpha * d (fp32),
+ *   d = (float)(thr - (double)field): the difference is formed in double, expf is the accurately rounded one.  Partials
+ *   are fp32 per thread over 8 pixels and double from the wave reduction on.  err, field0, field1: [B,1,H,W].
+ * arflow_calib_hist: pred [B,2,H,W], gt [B,C,H,W] (C = 2 or 4, else ARFLOW_EPARAM), ent [B,2,H,W] of ONE size; per element
+ *   of the two channels e = |(pred / n) * n - gt| (n = W, H: the reference's two roundings) goes into bin = the count of
+ *   edges[0..nb) <= (double)expf(ent) (np.digitize; edges ascending doubles on the device, 1 <= nb <= 128 else
+ *   ARFLOW_EPARAM).  rows [B][arflow_calib_rows(H, W)][nb + 1][3]: count, sum e, sum e^2, in double from the first addition.
+ * arflow_uncert_rows / arflow_calib_rows: rows per sample, or ARFLOW_ESHAPE. */
+int arflow_uncert_rows(int H, int W);
+int arflow_uncert_prep(const float* ent, const float* epe_map, const float* valid, long valid_bstride, float* ent_map,
+                       double* rows, float sub_w, float add_W, float sub_h, float add_H, int B, int h, int w, int H, int W,
+                       arflow_stream_t stream);
+int arflow_sparsify_sums(const float* err, const float* field0, const float* field1, const float* valid,
+                         long valid_bstride, const double* thr, float alpha, double* rows, int B, int H, int W, int K,
+                         arflow_stream_t stream);
+int arflow_calib_rows(int H, int W);
+int arflow_calib_hist(const float* pred, const float* gt, const float* ent, const double* edges, double* rows, int B, int C,
+                      int H, int W, int nb, arflow_stream_t stream);
+
 /* ---- the rest of the reference's parameter space (no shipped config uses these values; plain kernels) ----------
  * flow_warp(mode='nearest') (utils/warp_utils.py:83-90 -> grid_sample nearest: border clips the coordinate, index =
  * nearbyint, out of range reads 0).  No gradient w.r.t. the flow (grid_sample's nearest mode has none). */
