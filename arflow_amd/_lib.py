@@ -103,6 +103,8 @@ PROTOTYPES = {
     'arflow_triag_solve': [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
     'arflow_triag_solve_bwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
     'arflow_triag_inverse_diagonal': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'arflow_band_mv_fwd': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_band_mv_bwd': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_uncert_rows': [c_i, c_i],
     'arflow_uncert_prep': [c_fp, c_fp, c_fp, c_l, c_fp, c_fp, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_sparsify_sums': [c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp],

@@ -1,8 +1,9 @@
-"""losses/get_loss.py:9-24 for the loss types on the hot path (ELBO / MSE research losses are out
-of scope)."""
+"""losses/get_loss.py:9-24 for the loss types on the hot path and the ELBO objective of the probabilistic family (DESIGN.md
+section 21; the MSE research losses are out of scope)."""
 from .flow_loss import unFlowLoss
 from .fullres_loss import FullResLoss
 from .mv_loss import MvLoss
+from .uflow_elbo_loss import UFlowElboLoss
 from .uflow_loss import UFlowLoss
 
 
@@ -13,6 +14,8 @@ def get_loss(cfg):
         return FullResLoss(cfg)
     if cfg.type == 'uflow':
         return UFlowLoss(cfg)
+    if cfg.type == 'uflow_elbo':
+        return UFlowElboLoss(cfg)
     if cfg.type == 'mv':  # build-defined 3-frame objective; not a reference type
         return MvLoss(cfg)
     raise NotImplementedError(cfg.type)

@@ -562,6 +562,34 @@ int arflow_triag_solve_bwd(const float* A, const float* B, const float* C, const
 int arflow_triag_inverse_diagonal(const float* A, const float* B, const float* C, float* H, int P, int M, int N,
                                   arflow_stream_t stream);
 
+/* ---- the banded operator of the sparse-covariance family and its fused sampler (csrc/band.hip) ---------------
+ * matrix_vector_product_general / matrix_vector_product_T_general of utils/triag_solve.py:29-43, :59-73 and the sampler
+ * z = mean + L eps of losses/uflow_elbo_loss.py:142-147.  0 <= k <= 3; tap (i, j), 0 <= i, j <= k, has
+ * index ind = i (k + 1) + j; its coefficient plane for channel c in {0, 1} is channel c of `diag` (ind = 0) or channel
+ * 2 (ind - 1) + c of `off` (ind >= 1; `off` may be NULL when k = 0).  Sample s of batch item b is plane s B + b of X, Y, gY
+ * and gX.  Every tensor is fp32 with contiguous [2 or 2 ((k+1)^2 - 1)][M][N] items and its OWN batch stride in floats (read
+ * only when there is a second item), so channel slices of wider tensors are passed in place.
+ *   transpose = 0:  Y[sB+b,c,y,x] = mean[b,c,y,x] + sum_ind A[b,ind,c,y-i,x-j] X[sB+b,c,y-i,x-j]    (terms on the grid)
+ *   transpose = 1:  Y[sB+b,c,y,x] = mean[b,c,y,x] + sum_ind A[b,ind,c,y,x] X[sB+b,c,y+i,x+j]
+ * mean may be NULL (no addition).  Per element the products are rounded and added in ind order starting from 0, then added
+ * to the mean: the bits of the reference's fp32 CPU run.  The coefficients of a batch item are read once per launch for all
+ * S samples.
+ * arflow_band_mv_bwd, one launch, for the forward of orientation `transpose` with G = gY:
+ *   gX = the product of the OTHER orientation of G (NULL: not wanted);  gmean[b] = sum_s G[sB+b] (NULL: not wanted);
+ *   gA[b,ind,c,y,x] = sum_s X[sB+b,c,y,x] G[sB+b,c,y+i,x+j] (transpose = 0) or sum_s G[sB+b,c,y,x] X[sB+b,c,y+i,x+j]
+ *   (transpose = 1), stored to gdiag / goff in the layout of diag / off.  Every element of every output is stored; sums run
+ *   in a fixed order in one thread (no atomics: the same bits in either mode).
+ * ARFLOW_ENULL: a required pointer is NULL (off / goff only when k > 0); ARFLOW_EPARAM: k outside 0..3 or transpose not 0 / 1;
+ * ARFLOW_ESHAPE: B, S, M or N < 1, a batch stride smaller than its item, M N >= 2^31, B > 32767 or M > 524280.  Outputs
+ * must not overlap inputs. */
+int arflow_band_mv_fwd(const float* mean, long mean_bs, const float* diag, long diag_bs, const float* off, long off_bs,
+                       const float* X, long x_bs, float* Y, long y_bs, int B, int S, int M, int N, int k, int transpose,
+                       arflow_stream_t stream);
+int arflow_band_mv_bwd(const float* diag, long diag_bs, const float* off, long off_bs, const float* X, long x_bs,
+                       const float* gY, long gy_bs, float* gX, long gx_bs, float* gmean, long gmean_bs, float* gdiag,
+                       long gdiag_bs, float* goff, long goff_bs, int B, int S, int M, int N, int k, int transpose,
+                       arflow_stream_t stream);
+
 /* ---- uncertainty metrics: sparsification curves and the calibration histogram -----------------------------------
  * The device side of evaluate_uncertainty / sp_plot / CalibrationCurve of utils/flow_utils.py:186-320 (DESIGN.md section
  * 19).  The `rows` conventions of arflow_flow_eval hold for all three: a row buffer need not be initialised, every row is

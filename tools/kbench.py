@@ -42,6 +42,127 @@ def timeit(fn, iters):
     return e0.elapsed_time(e1) / iters * 1e3  # us
 
 
+def band_bench(dev, g, B=8, S=4, M=96, N=160, launches=30, repeats=5):
+    """z = mean + L eps and its backward at B = 8, S = 4 on the 96 x 160 level, k = 0 and 3 -- the fused
+    kernels (one launch each way, through the autograd node users call) next to the reference's formulation restated in
+    torch ops (repeat the coefficients S times, (k+1)^2 x slice / mul / pad / add, and ATen's autograd of that), which is
+    what a user has without the kernels.  HIP events around `launches` calls after 5 warm-ups, `repeats` times: median and
+    the spread (min .. max) of the repeats; the raw launches through the C ABI are timed next to them.  Then one whole UFlowElboLoss forward + backward at 384 x 640, k = 3."""
+    import statistics
+    import torch.nn.functional as F
+    from arflow_amd import functional as AF, triag_solve as T
+    from arflow_amd.config import AttrDict
+    from arflow_amd.losses.uflow_elbo_loss import UFlowElboLoss
+
+    def torch_formulation(mean, diag, off, eps, k):  # losses/uflow_elbo_loss.py:142-147 + utils/triag_solve.py:29-43
+        A = torch.cat((diag, off), 1).repeat(S, 1, 1, 1)
+        Y = torch.zeros_like(eps)
+        for i in range(k + 1):
+            for j in range(k + 1):
+                ind = i * (k + 1) + j
+                a = A[:, 2 * ind:2 * ind + 2]
+                if i > 0 and j > 0:
+                    Y = Y + F.pad(a[:, :, 0:-i, 0:-j] * eps[:, :, 0:-i, 0:-j], (j, 0, i, 0))
+                elif i > 0:
+                    Y = Y + F.pad(a[:, :, 0:-i, :] * eps[:, :, 0:-i, :], (0, 0, i, 0))
+                elif j > 0:
+                    Y = Y + F.pad(a[:, :, :, 0:-j] * eps[:, :, :, 0:-j], (j, 0, 0, 0))
+                else:
+                    Y = Y + a * eps
+        return mean.repeat(S, 1, 1, 1) + Y
+
+    def spread(fns, settle=100):
+        """{name: fn} -> {name: (median, min, max)} us per call.  These paths are launch-bound, and the host time of one
+        call was seen at two levels in one process, so every function first runs `settle` times and
+        the functions are then timed in alternation, one window each per round: drift hits all of them alike."""
+        for fn in fns.values():
+            for _ in range(settle):
+                fn()
+        torch.cuda.synchronize()
+        t = {name: [] for name in fns}
+        for _ in range(repeats):
+            for name, fn in fns.items():
+                t[name].append(timeit(fn, launches))
+                MANIFEST[-1].update(name='band/' + name, shape=[B, S, M, N])
+        return {name: (statistics.median(v), min(v), max(v)) for name, v in t.items()}
+
+    for k in (0, 3):
+        n2 = 2 * ((k + 1) ** 2 - 1)
+        mean = torch.randn(B, 2, M, N, device=dev, generator=g).requires_grad_(True)
+        diag = torch.exp(-1 + 0.3 * torch.randn(B, 2, M, N, device=dev, generator=g)).requires_grad_(True)
+        off = (0.1 * torch.randn(B, n2, M, N, device=dev, generator=g)).requires_grad_(True)
+        eps = torch.randn(S * B, 2, M, N, device=dev, generator=g)
+        w = torch.randn(S * B, 2, M, N, device=dev, generator=g)
+        leaves = (mean, diag, off) if k else (mean, diag)
+
+        def fused_fwd():
+            with torch.no_grad():
+                T.reparam_triag(mean, diag, off if k else None, k, nsamples=S, eps=eps)
+
+        def torch_fwd():
+            with torch.no_grad():
+                torch_formulation(mean, diag, off, eps, k)
+
+        def fused_both():
+            torch.autograd.grad(T.reparam_triag(mean, diag, off if k else None, k, nsamples=S, eps=eps), leaves, w)
+
+        def torch_both():
+            torch.autograd.grad(torch_formulation(mean, diag, off, eps, k), leaves, w)
+
+        same = torch.equal(T.reparam_triag(mean, diag, off if k else None, k, nsamples=S, eps=eps),
+                           torch_formulation(mean, diag, off, eps, k))
+        # algorithmic bytes: forward = coefficients + mean + eps + z; backward = coefficients + eps + gz in, all gradients out
+        plane = 4 * 2 * M * N
+        fwd_b = plane * (B * (n2 // 2 + 1) + B + 2 * S * B)
+        bwd_b = plane * (B * (n2 // 2 + 1) + 2 * S * B) + plane * (B * (n2 // 2 + 1) + B)
+        # the two launches alone, through the C ABI (no autograd node, no allocation)
+        lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+        d_, m_, o_ = diag.detach(), mean.detach(), (off.detach() if k else None)
+        z, gX, gm, gd = torch.empty_like(eps), torch.empty_like(eps), torch.empty_like(m_), torch.empty_like(d_)
+        go = torch.empty_like(o_) if k else None
+        pl, ob = 2 * M * N, n2 * M * N
+
+        def launch_fwd():
+            lib.arflow_band_mv_fwd(p(m_), pl, p(d_), pl, p(o_), ob, p(eps), pl, p(z), pl, B, S, M, N, k, 0, st)
+
+        def launch_bwd():
+            lib.arflow_band_mv_bwd(p(d_), pl, p(o_), ob, p(eps), pl, p(w), pl, p(gX), pl, p(gm), pl, p(gd), pl, p(go), ob, B, S,
+                                   M, N, k, 0, st)
+
+        res = spread({'launch fwd': launch_fwd, 'launch bwd': launch_bwd, 'fused fwd': fused_fwd, 'torch fwd': torch_fwd,
+                      'fused fwd+bwd': fused_both, 'torch fwd+bwd': torch_both})
+        for name, (med, lo, hi) in res.items():
+            nb = bwd_b if name == 'launch bwd' else fwd_b if name.endswith(' fwd') else fwd_b + bwd_b
+            print('band k=%d %-14s %9.1f us  (min %.1f .. max %.1f)  %8.1f GB/s algorithmic' % (k, name, med, lo, hi, nb / med / 1e3),
+                  flush=True)
+        for what in ('fwd', 'fwd+bwd'):
+            f, t = res['fused ' + what], res['torch ' + what]
+            print('band k=%d %s: fused is %.2fx the torch formulation; ranges %s; same forward bits: %s' % (
+                k, what, t[0] / f[0], 'apart' if f[2] < t[1] else 'OVERLAP', same), flush=True)
+
+    # one whole loss step at the flagship size
+    H, W, k = 384, 640, 3
+    cfg = AttrDict(type='uflow_elbo', edge_constant=150, edge_asymp=0.01, w_smooth=4.0, penalty_smooth='charbonnier',
+                   closed_form_smooth=False, data_loss=['census'], data_weight=[1.0], data_penalty=['abs_robust_loss'],
+                   w_entropy=0.1, w_oof=0.0, w_occ=0.0, with_bk=True, approx='sparse', cov_supp=k, inv_cov=False,
+                   approx_entropy=False, occ_type='sample', n_samples=S, offdiag_reg=0.0, natural_grad=False)
+    loss = UFlowElboLoss(cfg)
+    nets = [torch.cat((1.5 * torch.randn(B, 2, M, N, device=dev, generator=g), -1 + 0.3 * torch.randn(B, 2, M, N, device=dev, generator=g),
+                       0.1 * torch.randn(B, 30, M, N, device=dev, generator=g)), 1).requires_grad_(True) for _ in range(2)]
+    ims = [torch.rand(B, 3, H, W, device=dev, generator=g) for _ in range(2)]
+
+    def step():
+        out = loss({'flows_fw': [None, None, nets[0]], 'flows_bw': [None, None, nets[1]]}, ims[0], ims[1])
+        torch.autograd.grad(out[0], nets)
+
+    med, lo, hi = spread({'loss': step}, settle=20)['loss']
+    AF.start_kernel_timing()
+    step()
+    calls = AF.stop_kernel_timing()
+    print('UFlowElboLoss fwd+bwd B=%d S=%d %dx%d k=%d: %9.1f us  (min %.1f .. max %.1f); %d library launches: %s' % (
+        B, S, H, W, k, med, lo, hi, sum(len(v) for v in calls.values()), sorted({n for n, _ in calls})), flush=True)
+
+
 def main():
     if os.environ.get('ARFLOW_LIB_PATH'):  # an alternative build of the library (A/B timing; tools only)
         _lib.LIB_PATH = os.environ['ARFLOW_LIB_PATH']
@@ -370,6 +491,8 @@ def main():
                     p(A), p(Bc), p(Cc), p(Dc), p(Y), p(X), p(gX), p(gA), p(gB), p(gC), p(gD), P, M, N, 0, s), args.iters), 11 * P * M * N)
             trec('arflow_triag_inverse_diagonal', timeit(lambda: lib.arflow_triag_inverse_diagonal(
                 p(A), p(Bc), p(Cc), p(gA), P, M, N, s), max(3, args.iters // 10)), 4 * P * M * N)
+    if want('band'):  # the fused sparse-covariance sampler (csrc/band.hip) against the reference's formulation in torch ops
+        band_bench(dev, g)
     if args.manifest:
         json.dump(MANIFEST, open(args.manifest, 'w'), indent=1)
     if not rows:  # only ops that keep their own byte model (the head convolutions) were selected
