@@ -23,6 +23,9 @@ PROTOTYPES = {
     'arflow_get_deterministic': [],
     'arflow_flow_up_fwd': [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_flow_up_bwd': [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_out_up2_fwd': [c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_fp],
+    'arflow_out_up2_bwd': [c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_out_tail_fwd': [c_fp, c_l, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_fp],
     'arflow_profile_marker': [c_i, c_fp],
     'arflow_sums_rows': [c_i, c_i, c_i],
     'arflow_corr_fwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_fp],

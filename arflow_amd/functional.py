@@ -1269,6 +1269,115 @@ def flow_upsample(flow, factor=2, align_corners=True):
     return FlowUpsampleFunction.apply(flow, factor, align_corners)
 
 
+# ---- output upsample of the probabilistic PWC model ----------------------------------------------
+_OUT_UP = __import__('os').environ.get('ARFLOW_OUT_UP', '1') != '0'  # A/B switch for tools/ and tests: 0 = composed ATen path
+
+
+def out_up_supported(x):
+    """True where the model routes its output upsamples to out_upsample / out_tail: CUDA fp32, ARFLOW_OUT_UP not 0."""
+    return bool(_OUT_UP and x.is_cuda and x.dtype == torch.float32)
+
+
+def _plane_view(x):
+    """Return (tensor, batch_stride) so that a [B,C,H,W] channel slice of a wider tensor is used in place (planes contiguous)."""
+    B, C, H, W = x.shape
+    st = x.stride()
+    if st[3] == 1 and st[2] == W and st[1] == H * W and (B == 1 or st[0] >= C * H * W):
+        return x, (st[0] if B > 1 else C * H * W)
+    return x.contiguous(), C * H * W
+
+
+def _out_up_bwd(g, B, C, h, w, n_flow):
+    """Adjoint of one x2 step: g [B,C,2h,2w] (any channel slice with contiguous planes) -> [B,C,h,w]."""
+    g, gbs = _plane_view(g)
+    gin = torch.empty(B, C, h, w, device=g.device, dtype=torch.float32)
+    with torch.cuda.device_of(g):
+        _call('arflow_out_up2_bwd', _p(g), gbs, _p(gin), C * h * w, B, C, h, w, n_flow, _stream(), key=(B, C, h, w, 'bwd'))
+    return gin
+
+
+class OutUpsampleFunction(torch.autograd.Function):
+    """models/uflow_prob_model.py:223-250 upsample_out as one launch: out[:, c] = s_c * interpolate(x[:, c] + b_c, x2,
+    bilinear, align_corners=False), s_c = 2 for the first n_flow channels, b_c = diag_bias for the next n_diag.  The adjoint
+    is a gather (arflow_out_up2_bwd): reproducible in either mode, so the node does not sample the mode."""
+
+    @staticmethod
+    def forward(ctx, out, x, n_flow, n_diag, diag_bias):
+        # (`out` first: autograd treats input 0 of a node that writes into a view as the tensor modified in place)
+        _need_gpu(x, out)
+        if x.dim() != 4:
+            raise ValueError('out_upsample expects a [B,C,h,w] tensor')
+        B, C, h, w = x.shape
+        n_flow, n_diag = int(n_flow), int(n_diag)
+        if n_flow < 0 or n_diag < 0 or n_flow + n_diag > C:
+            raise ValueError('out_upsample: n_flow %d + n_diag %d exceed the %d channels' % (n_flow, n_diag, C))
+        x, xbs = _plane_view(x)
+        if out is None:
+            out = torch.empty(B, C, 2 * h, 2 * w, device=x.device, dtype=torch.float32)
+        else:
+            if tuple(out.shape) != (B, C, 2 * h, 2 * w):
+                raise ValueError('out_upsample: out must be [B,C,2h,2w]')
+            view, _ = _plane_view(out)
+            if view is not out:
+                raise ValueError('out_upsample: out must have contiguous planes (a channel slice of a contiguous buffer)')
+            ctx.mark_dirty(out)
+        _, obs = _plane_view(out)
+        with torch.cuda.device_of(x):
+            _call('arflow_out_up2_fwd', _p(x), xbs, _p(out), obs, B, C, h, w, n_flow, n_diag, float(diag_bias), _stream(),
+                  key=(B, C, h, w, 'fwd'))
+        ctx.cfg = (B, C, h, w, n_flow)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        return None, _out_up_bwd(gout, *ctx.cfg), None, None, None
+
+
+def out_upsample(x, n_flow, n_diag, diag_bias, out=None):
+    """x [B,C,h,w] (may be a channel slice) -> [B,C,2h,2w]; `out` may be a channel slice of a preallocated buffer (it is
+    written in place and returned).  diag_bias is a constant: no gradient."""
+    return OutUpsampleFunction.apply(out, x, n_flow, n_diag, diag_bias)
+
+
+class OutTailFunction(torch.autograd.Function):
+    """The model's last two upsample_out calls (level 2 -> level 1 -> level 0) in one launch from one read of x; bitwise
+    what two out_upsample calls give.  Backward: two arflow_out_up2_bwd launches (either gradient may be absent)."""
+
+    @staticmethod
+    def forward(ctx, x, n_flow, n_diag, diag_bias):
+        _need_gpu(x)
+        if x.dim() != 4:
+            raise ValueError('out_tail expects a [B,C,h,w] tensor')
+        B, C, h, w = x.shape
+        n_flow, n_diag = int(n_flow), int(n_diag)
+        if n_flow < 0 or n_diag < 0 or n_flow + n_diag > C:
+            raise ValueError('out_tail: n_flow %d + n_diag %d exceed the %d channels' % (n_flow, n_diag, C))
+        x, xbs = _plane_view(x)
+        ctx.set_materialize_grads(False)
+        out1 = torch.empty(B, C, 2 * h, 2 * w, device=x.device, dtype=torch.float32)
+        out0 = torch.empty(B, C, 4 * h, 4 * w, device=x.device, dtype=torch.float32)
+        with torch.cuda.device_of(x):
+            _call('arflow_out_tail_fwd', _p(x), xbs, _p(out1), _p(out0), B, C, h, w, n_flow, n_diag, float(diag_bias),
+                  _stream(), key=(B, C, h, w, 'tail'))
+        ctx.cfg = (B, C, h, w, n_flow)
+        return out1, out0
+
+    @staticmethod
+    def backward(ctx, g1, g0):
+        B, C, h, w, n_flow = ctx.cfg
+        if g0 is not None:
+            g10 = _out_up_bwd(g0, B, C, 2 * h, 2 * w, n_flow)
+            g1 = g10 if g1 is None else g1 + g10
+        if g1 is None:
+            return None, None, None, None
+        return _out_up_bwd(g1, B, C, h, w, n_flow), None, None, None
+
+
+def out_tail(x, n_flow, n_diag, diag_bias):
+    """x [B,C,h,w] -> (out1 [B,C,2h,2w], out0 [B,C,4h,4w]) = (out_upsample(x), out_upsample(out_upsample(x)))."""
+    return OutTailFunction.apply(x, n_flow, n_diag, diag_bias)
+
+
 def interpolate_flow(flow, factor, align_corners):
     """The models' flow upsample: ATen's F.interpolate in default mode (unchanged), flow_upsample in deterministic mode."""
     if flow.is_cuda and flow.dtype == torch.float32 and is_deterministic():

@@ -3,10 +3,14 @@
 (README.md:32-50:  inference.py -m <ckpt> -s 384 640 -i img1 img2 [img0 img1 img2]); the fork's own
 inference.py only drives its probabilistic models.
 
-    python -m arflow_amd.inference -s 384 640 -i a.png b.png [-m ckpt.pth.tar] [-o flow.flo] [--arch pwclite|pwclite_uflow|uflow]
+    python -m arflow_amd.inference -s 384 640 -i a.png b.png [-m ckpt.pth.tar] [-o flow.flo] [--arch pwclite|pwclite_uflow|uflow|uflow_prob]
+                                [--entropy-out ent.npy]
 
 Runs on the GPU through the HIP kernels.  Without -m the network is seeded-random (no checkpoint ships
-with the reference: .MISSING_LARGE_BLOBS), which still exercises the whole path.
+with the reference: .MISSING_LARGE_BLOBS), which still exercises the whole path.  --arch uflow_prob is PWCProbFlow with
+out_channels [2, 2, 0]; --entropy-out writes its full-resolution log-diagonal channels flows_fw[0][:, 2:4] as [H,W,2] -- what
+the reference's ELBO trainer evaluates as the per-component entropy for `diag`, and for `sparse` without inv_cov
+(trainer/uflow_elbo_trainer.py:175,191), and what `python -m arflow_amd.evaluate --entropy` reads.
 """
 import argparse
 
@@ -34,6 +38,9 @@ def build_model(kind, n_frames, ckpt=None, seed=0):
                        n_frames=2, reduce_dense=False)
     elif kind == 'uflow':
         cfg = AttrDict(type='uflow', level_dropout=0.0, feature_norm=True)
+    elif kind == 'uflow_prob':
+        cfg = AttrDict(type='uflow_prob', level_dropout=0.0, feature_norm=True, out_channels=[2, 2, 0], inv_cov=False,
+                       n_pyramids=1, mixture_weights=False)
     else:
         raise NotImplementedError(kind)
     model = get_model(cfg)
@@ -49,11 +56,23 @@ def build_model(kind, n_frames, ckpt=None, seed=0):
 
 
 @torch.no_grad()
-def infer(model, frames, device):
-    """frames: list of [3,H,W] tensors in [0,1] -> forward flow of the (middle) reference frame, [H,W,2]."""
+def infer(model, frames, device, want_entropy=False):
+    """frames: list of [3,H,W] tensors in [0,1] -> forward flow of the (middle) reference frame, [H,W,2]; with want_entropy
+    (PWCProbFlow only) also its log-diagonal channels, [H,W,2]."""
     x = torch.cat(frames, 0).unsqueeze(0).to(device)
-    res = model(x, with_bk=False) if len(frames) == 2 else model(x)
-    return res['flows_fw'][0][0].permute(1, 2, 0).float().cpu().numpy()
+    prob = hasattr(model, 'upsample_out')
+    if want_entropy and not prob:
+        raise ValueError('only the probabilistic model (--arch uflow_prob) has an entropy output')
+    if prob:
+        if len(frames) != 2:
+            raise ValueError('PWCProbFlow takes two frames')
+        res = model(x[:, :3], x[:, 3:], with_bk=False)
+    else:
+        res = model(x, with_bk=False) if len(frames) == 2 else model(x)
+    out = res['flows_fw'][0][0].permute(1, 2, 0).float().cpu().numpy()
+    if want_entropy:
+        return out[..., 0:2], out[..., 2:4]
+    return out[..., 0:2]
 
 
 def main():
@@ -62,14 +81,19 @@ def main():
     ap.add_argument('-s', '--test_shape', default=[384, 640], type=int, nargs=2)
     ap.add_argument('-i', '--img_list', nargs='+', required=True)
     ap.add_argument('-o', '--output', default=None, help='write the flow as .flo')
-    ap.add_argument('--arch', default='pwclite', choices=['pwclite', 'pwclite_uflow', 'uflow'])
+    ap.add_argument('--arch', default='pwclite', choices=['pwclite', 'pwclite_uflow', 'uflow', 'uflow_prob'])
+    ap.add_argument('--entropy-out', default=None, help='write the log-diagonal channels as .npy [H,W,2] (uflow_prob)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('arflow_amd.inference needs a GPU: the correlation / warp kernels have no CPU fallback')
     device = torch.device('cuda')
     frames = [load_image(p, args.test_shape) for p in args.img_list]
     model = build_model(args.arch, len(frames), args.model).to(device)
-    flow = infer(model, frames, device)
+    if args.entropy_out:
+        flow, ent = infer(model, frames, device, want_entropy=True)
+        np.save(args.entropy_out, np.ascontiguousarray(ent))
+    else:
+        flow = infer(model, frames, device)
     print('flow %s  mean |u|=%.4f |v|=%.4f' % (flow.shape, np.abs(flow[..., 0]).mean(), np.abs(flow[..., 1]).mean()))
     if args.output:
         write_flow(args.output, flow)

@@ -1,8 +1,9 @@
-"""models/get_model.py:8-25 for the deterministic flow models (the probabilistic research variants
-are out of scope)."""
+"""models/get_model.py:8-25: the deterministic flow models and PWCProbFlow, the single-pyramid probabilistic model of
+configs/chairs_uflow_elbo*.json (ComponentNet, MixtureWeightsNet and PWCLiteProb are out of scope)."""
 from .pwclite import PWCLite
 from .pwclite_uflow import PWCLiteUflow
 from .uflow_model import PWCFlow
+from .uflow_prob_model import PWCProbFlow
 
 
 def get_model(cfg):
@@ -12,4 +13,6 @@ def get_model(cfg):
         return PWCLiteUflow(cfg)
     if cfg.type == 'uflow':
         return PWCFlow(cfg)
+    if cfg.type == 'uflow_prob':
+        return PWCProbFlow(cfg)
     raise NotImplementedError(cfg.type)

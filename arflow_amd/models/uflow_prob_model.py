@@ -1,0 +1,210 @@
+"""PWCProbFlow (probabilistic UFlow port) host model on the gfx950 ops; contract of models/uflow_prob_model.py:149-517.
+This is what configs/chairs_uflow_elbo*.json instantiate (``"model": {"type": "uflow_prob"}``): PWCFlow with wider heads.
+Every level carries out_channels = [L, M, N] channels -- L = 2 flow channels (used for warping), M log-diagonal channels of
+the covariance / precision factor, N further channels (the off-diagonal band) that only the output level produces -- and
+brings them to the next level with upsample_out (:223-250): AF.out_upsample / AF.out_tail.
+
+The ops the CPU oracle substitutes (oracle.host_models.oracle_ops) are reached through the uflow_model module's attributes
+and blocks.bias_act, so a twin of this model runs on the oracle ops as it stands; such a twin (bias_act swapped out) also
+keeps the composed ATen upsample, the convention of blocks.HeadConv.native."""
+import math
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as func
+
+from .. import functional as AF
+from .. import uflow_utils
+from . import blocks
+from . import uflow_model as mum
+from .blocks import ConvAct, init_conv_weights
+from .uflow_model import PWCFeaturePyramid, PWCFlow
+
+
+class PWCProbFlow(nn.Module):
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        if cfg.n_pyramids != 1:
+            raise NotImplementedError('PWCProbFlow: n_pyramids = %r (only 1: ComponentNet / mixtures are out of scope)'
+                                      % (cfg.n_pyramids,))
+        if cfg.mixture_weights:
+            raise NotImplementedError('PWCProbFlow: mixture_weights = %r (MixtureWeightsNet is out of scope)'
+                                      % (cfg.mixture_weights,))
+        if len(cfg.out_channels) != 3 or cfg.out_channels[0] != 2:
+            raise NotImplementedError('PWCProbFlow: out_channels = %r (one flow pair: out_channels[0] must be 2)'
+                                      % (list(cfg.out_channels),))
+        self._leaky_relu_alpha = 0.1
+        self._drop_out_rate = cfg.level_dropout
+        self._num_context_up_channels = 32
+        self._num_levels = 5
+        self._normalize_before_cost_volume = cfg.feature_norm
+        self._out_channels = [int(c) for c in cfg.out_channels]
+        self._inv_cov = bool(cfg.inv_cov)
+        # added to the log-diagonal at every x2 upsample (:170): the standard deviation doubles with the resolution
+        self._diag_bias = -math.log(2) if cfg.inv_cov else math.log(2)
+        # registration order matters for state_dict order: refine, flow layers, upsample, pyramid(s)
+        self._refine_model = self._build_refinement_model()
+        self._flow_layers = self._build_flow_layers()
+        self._context_up_layers = nn.ModuleList(
+            [nn.ConvTranspose2d(32, 32, kernel_size=(4, 4), stride=2, padding=1) for _ in range(self._num_levels)])
+        self._feature_pyramid_extractor = nn.ModuleList([PWCFeaturePyramid() for _ in range(cfg.n_pyramids)])
+
+    def init_weights(self):
+        init_conv_weights(self, 'kaiming')  # :209-221: kaiming-normal fan_in, zero biases
+
+    def _build_flow_layers(self):
+        """:440-477: as PWCFlow, but every level's input has context_up and out_up (the top level too), and the head emits
+        L + M channels at levels 4..2 and L + M + N at level 1."""
+        result = nn.ModuleList([None])
+        n01, nall = sum(self._out_channels[0:2]), sum(self._out_channels)
+        for i in range(1, self._num_levels):
+            layers = nn.ModuleList()
+            c_in = 81 + 32 + n01 + self._num_context_up_channels
+            for c in (128, 128, 96, 64, 32):
+                layers.append(ConvAct(nn.Conv2d(c_in, c, kernel_size=(3, 3), stride=1, padding='same'),
+                                      nn.LeakyReLU(negative_slope=self._leaky_relu_alpha)))
+                c_in += c
+            layers.append(nn.Conv2d(32, nall if i == 1 else n01, kernel_size=(3, 3), padding='same'))
+            result.append(layers)
+        return result
+
+    def _build_refinement_model(self):
+        """:479-502: the dilated refinement over all L + M + N channels."""
+        layers = []
+        nall = sum(self._out_channels)
+        c_in = 32 + nall
+        for c, d in [(128, 1), (128, 2), (128, 4), (96, 8), (64, 16), (32, 1)]:
+            layers.append(nn.Conv2d(c_in, c, kernel_size=(3, 3), stride=1, padding='same', dilation=d))
+            layers.append(nn.LeakyReLU(negative_slope=self._leaky_relu_alpha))
+            c_in = c
+        layers.append(nn.Conv2d(c_in, nall, kernel_size=(3, 3), stride=1, padding='same'))
+        return nn.ModuleList(layers)
+
+    _drops = PWCFlow._drops  # one draw per level 4..1, then one for the refinement; all of a direction before the next
+
+    def _native_up(self, x):
+        return AF.out_up_supported(x) and blocks.bias_act is AF.bias_leaky_relu
+
+    def upsample_out(self, out):
+        """:223-250.  One launch on the GPU path, else the composed ATen path group by group."""
+        n0, n1, _ = self._out_channels
+        if self._native_up(out):
+            return AF.out_upsample(out, n0, n1, self._diag_bias)
+        ups = [uflow_utils.upsample(out[:, 0:n0], is_flow=True)]
+        if n1 > 0:
+            ups.append(uflow_utils.upsample(out[:, n0:n0 + n1] + self._diag_bias, is_flow=False))
+        if out.size(1) > n0 + n1:
+            ups.append(uflow_utils.upsample(out[:, n0 + n1:], is_flow=False))
+        return torch.cat(ups, dim=1)
+
+    def forward_2_frames(self, feature_pyramid1, feature_pyramid2, drops=None, moments=None):
+        """:252-389.  moments: as PWCFlow.forward_2_frames."""
+        n0, n1, n2 = self._out_channels
+        n01 = n0 + n1
+        alpha = self._leaky_relu_alpha
+        norm = self._normalize_before_cost_volume
+        context = out = context_up = None
+        outs = []
+        k = 0
+        top = self._num_levels - 1
+        for level in range(top, 0, -1):
+            features1, features2 = feature_pyramid1[level], feature_pyramid2[level]
+            B, _, H, W = features1.shape
+            r1 = moments[0][level] if moments is not None else None
+            if level == top:
+                # :263-273: zero context_up, zero flow, and log_diag planes chosen so that the diag_bias of the upsamples
+                # down to the output level leaves ~0 there.  The warp by the zero flow is the identity and is not run.
+                start = torch.cat([features1.new_zeros(B, self._num_context_up_channels + n0, H, W),
+                                   features1.new_full((B, n1, H, W), -(self._num_levels - 3) * self._diag_bias)], 1)
+                out_up = start[:, self._num_context_up_channels:]
+                if norm and AF.level_supported(features1, None, True):
+                    r2 = moments[1][level] if moments is not None else None
+                    cfg = AF.LevelCfg([0, 'vol', 1], 'avg', alpha, 4)
+                    x_in = AF.level(features1, features2, None, cfg, start, features1, x1_rows=r1, x2_rows=r2)
+                else:
+                    f1n, w2n = mum.normalize_features([features1, features2], normalize=norm, center=norm,
+                                                      moments_across_channels=True, moments_across_images=True)
+                    x_in = mum.cost_volume_concat(f1n, w2n, (start,), (features1,), max_displacement=4, negative_slope=alpha)
+            elif norm and AF.level_supported(features1, out[:, 0:2], True):
+                # the fused level upsamples and warps with the flow pair itself ('flow' slot); the other channels of
+                # out_up come from the output-upsample kernel and travel as a member
+                if self._native_up(out):
+                    rest_up = AF.out_upsample(out[:, n0:], 0, n1, self._diag_bias)
+                else:
+                    rest_up = uflow_utils.upsample(out[:, n0:] + self._diag_bias, is_flow=False)
+                cfg = AF.LevelCfg([0, 'flow', 1, 'vol', 2], 'avg', alpha, 4, True, False, 'zeros', True, AF.NORM_UFLOW)
+                x_in, flow_up = AF.level(features1, features2, out[:, 0:2], cfg, context_up, rest_up, features1, x1_rows=r1)
+                out_up = torch.cat([flow_up, rest_up], 1)
+            else:
+                out_up = self.upsample_out(out)
+                warped2 = mum.uflow_utils.resample_flow(features2, out_up[:, 0:2])  # :282
+                f1n, w2n = mum.normalize_features([features1, warped2], normalize=norm, center=norm,
+                                                  moments_across_channels=True, moments_across_images=True)
+                x_in = mum.cost_volume_concat(f1n, w2n, (context_up, out_up), (features1,), max_displacement=4,
+                                              negative_slope=alpha)
+            layers = self._flow_layers[level]
+            x_out = None
+            for layer in layers[:-1]:
+                x_out = layer(x_in)
+                x_in = torch.cat([x_in, x_out], dim=1)
+            context = x_out
+            out = layers[-1](context)
+            if drops is not None:
+                context = context * drops[k]
+                out = out * drops[k]
+            k += 1
+            if out.shape[1] > n01:  # :337-341: the output level's head is wider than what came up the pyramid
+                out_up = func.pad(out_up, (0, 0, 0, 0, 0, out.shape[1] - n01))
+            out = out + out_up
+            context_up = self._context_up_layers[level](context)
+            outs.insert(0, out)
+        refinement = torch.cat([context, out], dim=1)
+        mods = list(self._refine_model)
+        i = 0
+        while i < len(mods):  # Conv2d followed by LeakyReLU -> bias-free conv + fused bias / LeakyReLU pass
+            m = mods[i]
+            if isinstance(m, nn.Conv2d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.LeakyReLU):
+                refinement = blocks.bias_act(func.conv2d(refinement, m.weight, None, m.stride, m.padding, m.dilation),
+                                             m.bias, mods[i + 1].negative_slope)
+                i += 2
+            else:
+                refinement = m(refinement)
+                i += 1
+        if drops is not None:
+            refinement = refinement * drops[k]
+        refined = out + refinement
+        # :375-381: log(precision) / 2 not too small, log(variance) / 2 neither too small nor too large
+        log_diag = refined[:, n0:n01]
+        log_diag = torch.clamp(log_diag, min=-5.0) if self._inv_cov else torch.clamp(log_diag, max=10.0, min=-10.0)
+        outs[0] = torch.cat([refined[:, 0:n0], log_diag, refined[:, n01:]], dim=1)
+        if self._native_up(outs[0]):
+            out_1, out_0 = AF.out_tail(outs[0], n0, n1, self._diag_bias)
+        else:
+            out_1 = self.upsample_out(outs[0])
+            out_0 = self.upsample_out(out_1)
+        outs.insert(0, out_1)
+        outs.insert(0, out_0)
+        return outs
+
+    def forward(self, img1, img2, with_bk=True):
+        B = img1.size(0)
+        extractor = self._feature_pyramid_extractor[0]
+        pyr_all = extractor(torch.cat([img1, img2], 0))
+        moms = extractor.pyramid_moments
+        have_m = moms is not None and all(t is not None for t in moms)
+        res = {}
+        if with_bk:
+            # both directions as one 2B pass, as PWCFlow.forward: first maps = the extractor's batch as it stands, second
+            # maps = its halves swapped; the same for the rows of partial moments
+            a = list(pyr_all)
+            b = [torch.cat([p[B:], p[:B]], 0) for p in pyr_all]
+            m = (list(moms), [torch.roll(t, B, 0) for t in moms]) if have_m else None
+            flows = self.forward_2_frames(a, b, self._drops(2, B, img1.device), m)
+            res['flows_fw'] = [f[:B] for f in flows]
+            res['flows_bw'] = [f[B:] for f in flows]
+        else:
+            m = ([t[:B] for t in moms], [t[B:] for t in moms]) if have_m else None
+            res['flows_fw'] = self.forward_2_frames([p[:B] for p in pyr_all], [p[B:] for p in pyr_all],
+                                                    self._drops(1, B, img1.device), m)
+        return res

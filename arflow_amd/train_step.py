@@ -32,6 +32,14 @@ WORKLOADS = {
     'pwcflow+uflow_loss': (
         dict(type='uflow', feature_norm=True, level_dropout=0.1),
         dict(type='uflow', edge_constant=150, w_smooth=4.0, w_census=1.0, with_bk=True, smooth_order=1)),
+    # configs/chairs_uflow_elbo_nondiag.json:23-55 (model type 'uflow_prob' = PWCProbFlow, banded covariance factor)
+    'pwcprobflow+uflow_elbo_loss': (
+        dict(type='uflow_prob', feature_norm=True, level_dropout=0.1, out_channels=[2, 2, 30], inv_cov=False, n_pyramids=1,
+             mixture_weights=False),
+        dict(type='uflow_elbo', edge_constant=150, edge_asymp=0.01, w_smooth=4.0, penalty_smooth='charbonnier',
+             closed_form_smooth=False, data_loss=['census'], data_weight=[1.0], data_penalty=['abs_robust_loss'],
+             w_entropy=0.1, w_oof=0.0, w_occ=0.0, with_bk=True, approx='sparse', n_components=1, cov_supp=3, inv_cov=False,
+             approx_entropy=False, occ_type='sample', n_samples=4, offdiag_reg=0.0, natural_grad=False)),
 }
 
 
@@ -72,12 +80,19 @@ class TrainStep:
         self.last = None
 
     def __call__(self, img_pair):
+        if self.loss_cfg.type == 'uflow_elbo':  # trainer/uflow_elbo_trainer.py: the model and the loss take the two frames
+            res = self.model(img_pair[:, :3], img_pair[:, 3:], with_bk=True)
+            out = self.loss(res, img_pair[:, :3], img_pair[:, 3:])
+            return self._step(out)
         res = self.model(img_pair, with_bk=True)
         if self.loss_cfg.type == 'mv':
             out = self.loss(res['flows_fw'], res['flows_bw'], img_pair)
         else:
             flows = [torch.cat([fw, bw], 1) for fw, bw in zip(res['flows_fw'], res['flows_bw'])]
             out = self.loss(flows, img_pair)
+        return self._step(out)
+
+    def _step(self, out):
         self.reducer.zero_grad()
         out[0].backward()
         self.reducer.finish()

@@ -87,6 +87,23 @@ int arflow_flow_up_fwd(const float* flow, float* out, int B, int h, int w, int f
                        arflow_stream_t stream);
 int arflow_flow_up_bwd(const float* gfine, float* gcoarse, int B, int h, int w, int factor, int align_corners,
                        arflow_stream_t stream);
+/* Output upsample of the probabilistic PWC model (models/uflow_prob_model.py:223-250 upsample_out) over all channels in one
+ * launch: out[b,c] = s_c * upsample_bilinear2d(in[b,c] + b_c, x2, align_corners=False) with s_c = 2 for c < n_flow (else 1)
+ * and b_c = diag_bias for n_flow <= c < n_flow + n_diag (else 0); the bias is added on load, before the blend.  fp32, planes
+ * contiguous (h*w floats between channels); every tensor has its own batch stride in floats (>= C * plane when B > 1), so
+ * `in` can be a channel slice of a wider tensor and `out` a slot of a concatenated buffer.  in: [B,C,h,w] -> out:
+ * [B,C,2h,2w].  One float4 store per lane where w is even and out / out_bstride are 16-byte aligned, else a scalar path.
+ * arflow_out_up2_bwd is the adjoint as a GATHER (gfine [B,C,2h,2w] -> gcoarse [B,C,h,w]): one coarse cell adds the <= 4x4
+ * fine pixels that read it, rows then columns ascending; every element of gcoarse written, no atomics, bitwise
+ * reproducible.  arflow_out_tail_fwd applies the rule twice in one launch -- out1 [B,C,2h,2w] and out0 [B,C,4h,4w], both
+ * contiguous, from one read of `in` -- and is bitwise equal to two arflow_out_up2_fwd launches (its adjoint is two
+ * arflow_out_up2_bwd launches). */
+int arflow_out_up2_fwd(const float* in, long in_bstride, float* out, long out_bstride, int B, int C, int h, int w, int n_flow,
+                       int n_diag, float diag_bias, arflow_stream_t stream);
+int arflow_out_up2_bwd(const float* gfine, long gfine_bstride, float* gcoarse, long gcoarse_bstride, int B, int C, int h,
+                       int w, int n_flow, arflow_stream_t stream);
+int arflow_out_tail_fwd(const float* in, long in_bstride, float* out1, float* out0, int B, int C, int h, int w, int n_flow,
+                        int n_diag, float diag_bias, arflow_stream_t stream);
 /* HIP keeps ONE "last error" per host thread.  If a code was already pending when an entry point is entered
  * (left by the host framework or an unchecked earlier call) it is not attributed to this library's launch and
  * not dropped either: the first such hipError_t is kept (and reported once on stderr) until the host reads it

@@ -163,6 +163,89 @@ def band_bench(dev, g, B=8, S=4, M=96, N=160, launches=30, repeats=5):
         B, S, H, W, k, med, lo, hi, sum(len(v) for v in calls.values()), sorted({n for n, _ in calls})), flush=True)
 
 
+def out_up_bench(dev, g, B2=8, launches=30, repeats=5):
+    """the output upsample of PWCProbFlow -- AF.out_upsample / AF.out_tail (one launch each way) next to
+    the composed ATen path the model runs with ARFLOW_OUT_UP=0 (split, bias add, F.interpolate per group, x2, cat, and
+    ATen's autograd of that), at the workload's own shapes with 2B = 8: C = 4 at the 12x20, 24x40 and 48x80 inputs, and the
+    tail (two steps) at 34 x 96 x 160.  The two versions alternate, `repeats` windows of `launches` calls each: median and
+    (min .. max).  Bytes are algorithmic: every input element read once, every output element written once (backward: the
+    fine gradients read once, the coarse one written once); the share is of the HBM3E spec peak, 8 TB/s."""
+    import math
+    import statistics
+    import torch.nn.functional as F
+    from arflow_amd import functional as AF
+    bias = math.log(2.0)
+
+    def composed(x, n_flow=2, n_diag=2):
+        up = lambda v: F.interpolate(v, scale_factor=2.0, mode='bilinear', align_corners=False)  # noqa: E731
+        parts = [up(x[:, :n_flow]) * 2.0, up(x[:, n_flow:n_flow + n_diag] + bias)]
+        if x.shape[1] > n_flow + n_diag:
+            parts.append(up(x[:, n_flow + n_diag:]))
+        return torch.cat(parts, 1)
+
+    def spread(fns):
+        for fn in fns.values():
+            for _ in range(20):
+                fn()
+        torch.cuda.synchronize()
+        t = {name: [] for name in fns}
+        for _ in range(repeats):
+            for name, fn in fns.items():
+                t[name].append(timeit(fn, launches))
+                MANIFEST[-1].update(name='out_up/' + name, shape=[])
+        return {name: (statistics.median(v), min(v), max(v)) for name, v in t.items()}
+
+    def report(tag, res, nbytes):
+        for what in ('fwd', 'bwd'):
+            f, t = res['fused ' + what], res['aten ' + what]
+            nb = nbytes[what]
+            print('out_up %-22s %s  fused %8.1f us (%.1f .. %.1f) %7.1f GB/s %5.2f%% of the 8 TB/s HBM peak | ATen %8.1f us '
+                  '(%.1f .. %.1f) %7.1f GB/s | %.2fx, ranges %s' % (
+                      tag, what, f[0], f[1], f[2], nb / f[0] / 1e3, 100 * nb / f[0] / 1e3 / HBM_PEAK_GBS, t[0], t[1], t[2],
+                      nb / t[0] / 1e3, t[0] / f[0], 'apart' if (f[2] < t[1] or t[2] < f[1]) else 'OVERLAP'), flush=True)
+
+    for C, h, w in ((4, 12, 20), (4, 24, 40), (4, 48, 80)):
+        x = torch.randn(B2, C, h, w, device=dev, generator=g).requires_grad_(True)
+        go = torch.randn(B2, C, 2 * h, 2 * w, device=dev, generator=g)
+        yf, ya = AF.out_upsample(x, 2, 2, bias), composed(x)
+
+        def ffwd():
+            with torch.no_grad():
+                AF.out_upsample(x, 2, 2, bias)
+
+        def afwd():
+            with torch.no_grad():
+                composed(x)
+        res = spread({'fused fwd': ffwd, 'aten fwd': afwd,
+                      'fused bwd': lambda: torch.autograd.grad(yf, x, go, retain_graph=True),
+                      'aten bwd': lambda: torch.autograd.grad(ya, x, go, retain_graph=True)})
+        n = 4 * B2 * C * h * w
+        report('x2 %s' % [B2, C, h, w], res, {'fwd': 5 * n, 'bwd': 5 * n})
+    C, h, w = 34, 96, 160
+    x = torch.randn(B2, C, h, w, device=dev, generator=g).requires_grad_(True)
+    g1 = torch.randn(B2, C, 2 * h, 2 * w, device=dev, generator=g)
+    g0 = torch.randn(B2, C, 4 * h, 4 * w, device=dev, generator=g)
+    tf = AF.out_tail(x, 2, 2, bias)
+    a1 = composed(x)
+    ta = (a1, composed(a1))
+    print('out_up tail: same bits as the composed path: out1 %s, out0 %s' % (torch.equal(tf[0], ta[0]), torch.equal(tf[1], ta[1])))
+
+    def tfwd():
+        with torch.no_grad():
+            AF.out_tail(x, 2, 2, bias)
+
+    def tafwd():
+        with torch.no_grad():
+            composed(composed(x))
+    res = spread({'fused fwd': tfwd, 'aten fwd': tafwd,
+                  'fused bwd': lambda: torch.autograd.grad(tf, x, [g1, g0], retain_graph=True),
+                  'aten bwd': lambda: torch.autograd.grad(ta, x, [g1, g0], retain_graph=True)})
+    n = 4 * B2 * C * h * w
+    # forward: x read, out1 and out0 written; backward: g0 and g1 read, gx written (the level-1 gradient in between is
+    # the composed algorithm's own traffic, not counted)
+    report('tail %s' % [B2, C, h, w], res, {'fwd': 21 * n, 'bwd': 21 * n})
+
+
 def main():
     if os.environ.get('ARFLOW_LIB_PATH'):  # an alternative build of the library (A/B timing; tools only)
         _lib.LIB_PATH = os.environ['ARFLOW_LIB_PATH']
@@ -493,6 +576,8 @@ def main():
                 p(A), p(Bc), p(Cc), p(gA), P, M, N, s), max(3, args.iters // 10)), 4 * P * M * N)
     if want('band'):  # the fused sparse-covariance sampler (csrc/band.hip) against the reference's formulation in torch ops
         band_bench(dev, g)
+    if want('out_up'):  # the probabilistic model's output upsample (csrc/out_up.hip) against the composed ATen path
+        out_up_bench(dev, g)
     if args.manifest:
         json.dump(MANIFEST, open(args.manifest, 'w'), indent=1)
     if not rows:  # only ops that keep their own byte model (the head convolutions) were selected
