@@ -9,9 +9,16 @@
 //
 // In eager PyTorch this is ~14 launches forward and ~30 backward per pyramid level, each a full pass
 // over the feature tensors.  Here: forward = one moment pass (float4 loads, fp32 per-thread partials
-// over <= 64 values, double from the wave reduction on -- sum(x^2) - sum(x)^2/n is then exact to fp32
-// for any mean / spread ratio) + one apply pass; backward = one pass for the two sums the chain rule
-// needs + one apply pass.  HBM-bound: 3 reads + 1 write of each tensor forward, 4 reads + 1 write backward.
+// over 16 values per tensor and trip, double from there on) + one apply pass; backward = one pass for the
+// two sums the chain rule needs + one apply pass.  HBM-bound: 3 reads + 1 write of each tensor forward,
+// 4 reads + 1 write backward.
+// Accuracy: the double stage makes sum(x^2) - sum(x)^2/n exact to fp32 GIVEN the partials, but the fp32
+// partials in front of it are not exact, and the subtraction amplifies their error by kappa = E[x^2]/var
+// = 1 + (mean/spread)^2: the variance carries a relative error of up to (16 kappa + 30 |mu| E|x| / var) u,
+// u = 2^-24 (derived in tests/corr_ref.py, held per element by tests/test_corr_gpu.py).  Centred features
+// (kappa ~ 1, what the models produce) get sd to a few u; at mean/spread = 25 the guarantee is ~7e-4 relative
+// (measured 5e-7, ten times the scalar paths'); at mean/spread = 1000 nothing is guaranteed and 0.2-0.4 % is measured on the float4
+// paths.  The scalar paths (n % 4 != 0) are double from the first value and free of this.
 #include "common.hpp"
 #include "featnorm_stats.hpp"
 
