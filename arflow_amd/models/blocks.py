@@ -185,11 +185,31 @@ def init_conv_weights(module, scheme):
                 nn.init.constant_(layer.bias, 0)
 
 
-def pair_batches(pyr1, pyr2):
-    """Stack (frame1, frame2) and (frame2, frame1) along the batch axis so that the forward and the
-    backward flow are estimated in ONE pass at batch 2B -- every op on the path is per-sample, so the
-    result equals the reference's two sequential passes (models/pwclite.py:267-269) while every launch
-    covers twice the pixels."""
-    a = [torch.cat([p, q], 0) for p, q in zip(pyr1, pyr2)]
-    b = [torch.cat([q, p], 0) for p, q in zip(pyr1, pyr2)]
-    return a, b
+def level_drops(training, rate, n, n_passes, batch_per_pass, device):
+    """Level-dropout multipliers [n, n_passes * batch_per_pass, 1, 1, 1], or None outside training / at rate 0.  Drawn from
+    the CPU RNG in the reference's order: the n draws of a pass (one per level, then one for the context / refinement net;
+    models/pwclite_uflow.py:226-229,240-242) before those of the next pass."""
+    if not (training and rate > 0):
+        return None
+    vals = [[float(torch.rand(1) > rate) for _ in range(n)] for _ in range(n_passes)]
+    t = torch.tensor(vals, dtype=torch.float32)                      # [passes, n]
+    t = t.repeat_interleave(batch_per_pass, dim=0).t().contiguous()  # [n, passes*B]
+    return t.to(device, non_blocking=True).view(n, -1, 1, 1, 1)
+
+
+def pair_pass(pyr_all, moms, B, with_bk, run):
+    """The two-frame pass over the extractor's output for the batch (frame1; frame2): `pyr_all` its 2B pyramid, `moms` the
+    rows of partial moments per level or None, run(pyr1, pyr2, n_passes, moments) the model's decoder (moments = (rows of
+    the first maps, rows of the second maps) or None when any level has none).  with_bk: the forward and the backward flow
+    are estimated in ONE pass at batch 2B -- every op on the path is per-sample, so the result equals the reference's two
+    sequential passes (models/pwclite.py:267-269) while every launch covers twice the pixels.  The first maps of the 2B
+    (fw; bw) samples are the extractor's batch as it stands (no copy), the second maps its two halves swapped; the same
+    holds for the moment rows."""
+    have_m = moms is not None and all(t is not None for t in moms)
+    if with_bk:
+        swapped = [torch.cat([p[B:], p[:B]], 0) for p in pyr_all]
+        m = (list(moms), [torch.roll(t, B, 0) for t in moms]) if have_m else None
+        flows = run(list(pyr_all), swapped, 2, m)
+        return {'flows_fw': [f[:B] for f in flows], 'flows_bw': [f[B:] for f in flows]}
+    m = ([t[:B] for t in moms], [t[B:] for t in moms]) if have_m else None
+    return {'flows_fw': run([p[:B] for p in pyr_all], [p[B:] for p in pyr_all], 1, m)}

@@ -7,7 +7,7 @@ from .. import functional as AF
 from ..correlation import Correlation
 from ..warp_utils import flow_warp
 from .blocks import (ContextNetwork, FeatureExtractor, FlowEstimatorDense, FlowEstimatorReduce, conv,
-                     init_conv_weights, pair_batches)
+                     init_conv_weights, pair_pass)
 
 
 class PWCLite(nn.Module):
@@ -110,17 +110,12 @@ class PWCLite(nn.Module):
         B = x.size(0)
         # one extractor pass over all frames (batch n*B) instead of n passes
         pyr_all = self.feature_pyramid_extractor(torch.cat(imgs, 0))
+        if n_frames == 2:
+            # the image level the reference appends to its pyramids is never read: forward_2_frames leaves at output_level
+            return pair_pass(pyr_all, None, B, with_bk, lambda p1, p2, n_passes, m: self.forward_2_frames(p1, p2))
         pyrs = [[p[i * B:(i + 1) * B] for p in pyr_all] + [imgs[i]] for i in range(n_frames)]
         res = {}
-        if n_frames == 2:
-            if with_bk:
-                a, b = pair_batches(pyrs[0], pyrs[1])
-                flows = self.forward_2_frames(a, b)
-                res['flows_fw'] = [f[:B] for f in flows]
-                res['flows_bw'] = [f[B:] for f in flows]
-            else:
-                res['flows_fw'] = self.forward_2_frames(pyrs[0], pyrs[1])
-        elif n_frames == 3:
+        if n_frames == 3:
             flows_10, flows_12 = self.forward_3_frames(pyrs[0], pyrs[1], pyrs[2])
             res['flows_fw'], res['flows_bw'] = flows_12, flows_10
         elif n_frames == 5:

@@ -6,7 +6,7 @@ from .. import functional as AF
 from ..correlation import Correlation
 from ..warp_utils import flow_warp
 from .blocks import (ContextNetwork, FeatureExtractor, FlowEstimatorDense, FlowEstimatorReduce, deconv,
-                     init_conv_weights)
+                     init_conv_weights, level_drops, pair_pass)
 
 
 def normalize_features(features_list):
@@ -64,15 +64,8 @@ class PWCLiteUflow(nn.Module):
         init_conv_weights(self, 'xavier')
 
     def _drops(self, n_passes, batch_per_pass, device):
-        """Level-dropout multipliers, drawn from the CPU RNG in the reference's order (per pass:
-        one per level, then one for the context net; models/pwclite_uflow.py:226-229,240-242)."""
-        n = self.output_level + 2
-        if not (self.training and self.level_dropout > 0):
-            return None
-        vals = [[float(torch.rand(1) > self.level_dropout) for _ in range(n)] for _ in range(n_passes)]
-        t = torch.tensor(vals, dtype=torch.float32)                      # [passes, n]
-        t = t.repeat_interleave(batch_per_pass, dim=0).t().contiguous()  # [n, passes*B]
-        return t.to(device, non_blocking=True).view(n, -1, 1, 1, 1)
+        """One multiplier per level, then one for the context net."""
+        return level_drops(self.training, self.level_dropout, self.output_level + 2, n_passes, batch_per_pass, device)
 
     def forward_2_frames(self, x1_pyramid, x2_pyramid, drops=None, moments=None):
         """models/pwclite_uflow.py:193-252.  moments: optional (x1 rows, x2 rows) lists per pyramid level, the feature maps'
@@ -129,23 +122,7 @@ class PWCLiteUflow(nn.Module):
         if n_frames != 2:
             raise NotImplementedError
         B = x.size(0)
-        imgs = [x[:, 0:3], x[:, 3:6]]
-        pyr_all = self.feature_pyramid_extractor(torch.cat(imgs, 0))
-        moms = self.feature_pyramid_extractor.pyramid_moments
-        have_m = moms is not None and all(t is not None for t in moms)
-        p1 = [p[:B] for p in pyr_all] + [imgs[0]]
-        p2 = [p[B:] for p in pyr_all] + [imgs[1]]
-        res = {}
-        if with_bk:
-            # first maps of the 2B (fw; bw) samples = the extractor's batch as it stands (no copy); second maps = its
-            # two halves swapped; the same holds for the rows of partial moments
-            a = list(pyr_all)  # (the image level the reference appends to its pyramids is never read, pwclite_uflow.py:203)
-            b = [torch.cat([p[B:], p[:B]], 0) for p in pyr_all]
-            m = ([t for t in moms], [torch.roll(t, B, 0) for t in moms]) if have_m else None
-            flows = self.forward_2_frames(a, b, self._drops(2, B, x.device), m)
-            res['flows_fw'] = [f[:B] for f in flows]
-            res['flows_bw'] = [f[B:] for f in flows]
-        else:
-            m = ([t[:B] for t in moms], [t[B:] for t in moms]) if have_m else None
-            res['flows_fw'] = self.forward_2_frames(p1, p2, self._drops(1, B, x.device), m)
-        return res
+        # (the image level the reference appends to its pyramids is never read, pwclite_uflow.py:203)
+        pyr_all = self.feature_pyramid_extractor(torch.cat([x[:, 0:3], x[:, 3:6]], 0))
+        return pair_pass(pyr_all, self.feature_pyramid_extractor.pyramid_moments, B, with_bk,
+                         lambda p1, p2, n_passes, m: self.forward_2_frames(p1, p2, self._drops(n_passes, B, x.device), m))

@@ -8,7 +8,7 @@ from .. import functional as AF
 from .. import uflow_utils
 from ..correlation import cost_volume_concat
 from . import blocks
-from .blocks import ConvAct, init_conv_weights, pair_batches
+from .blocks import ConvAct, init_conv_weights, level_drops, pair_pass
 
 
 def normalize_features(feature_list, normalize, center, moments_across_channels, moments_across_images):
@@ -69,6 +69,62 @@ class PWCFeaturePyramid(nn.Module):
         return features
 
 
+def build_flow_layers(c_ins, c_heads, alpha):
+    """models/uflow_model.py:297-323: per level 1.. (index 0 stays empty) 5 dense 3x3 blocks (128,128,96,64,32) on an input
+    of c_ins[level - 1] channels and a 32 -> c_heads[level - 1] head that sees only the last block."""
+    result = nn.ModuleList([None])
+    for c_in, c_head in zip(c_ins, c_heads):
+        layers = nn.ModuleList()
+        for c in (128, 128, 96, 64, 32):
+            layers.append(ConvAct(nn.Conv2d(c_in, c, kernel_size=(3, 3), stride=1, padding='same'),
+                                  nn.LeakyReLU(negative_slope=alpha)))
+            c_in += c
+        layers.append(nn.Conv2d(32, c_head, kernel_size=(3, 3), padding='same'))
+        result.append(layers)
+    return result
+
+
+def build_refinement_model(c_in, c_out, alpha):
+    """models/uflow_model.py:325-348: six dilated 3x3 convs with LeakyReLU, then a c_out-channel 3x3 conv."""
+    layers = []
+    for c, d in [(128, 1), (128, 2), (128, 4), (96, 8), (64, 16), (32, 1)]:
+        layers.append(nn.Conv2d(c_in, c, kernel_size=(3, 3), stride=1, padding='same', dilation=d))
+        layers.append(nn.LeakyReLU(negative_slope=alpha))
+        c_in = c
+    layers.append(nn.Conv2d(c_in, c_out, kernel_size=(3, 3), stride=1, padding='same'))
+    return nn.ModuleList(layers)
+
+
+def dense_level(layers, x_in, drop):
+    """The decoder of one level behind its input: the dense blocks concatenate as they go, the head sees the last block's
+    output, and level dropout (drop, or None) multiplies both.  -> (context, out)."""
+    context = None
+    for layer in layers[:-1]:
+        context = layer(x_in)
+        x_in = torch.cat([x_in, context], dim=1)
+    out = layers[-1](context)
+    if drop is not None:
+        context = context * drop
+        out = out * drop
+    return context, out
+
+
+def refine(mods, x):
+    """The refinement model over x: a Conv2d followed by a LeakyReLU runs as bias-free conv + fused bias / LeakyReLU pass."""
+    mods = list(mods)
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, nn.Conv2d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.LeakyReLU):
+            x = blocks.bias_act(func.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation), m.bias,
+                                mods[i + 1].negative_slope)
+            i += 2
+        else:
+            x = m(x)
+            i += 1
+    return x
+
+
 class PWCFlow(nn.Module):
     def __init__(self, cfg):
         super().__init__()
@@ -78,8 +134,10 @@ class PWCFlow(nn.Module):
         self._num_levels = 5
         self._normalize_before_cost_volume = cfg.feature_norm
         # registration order matters for state_dict order: refine, flow layers, upsample, pyramid
-        self._refine_model = self._build_refinement_model()
-        self._flow_layers = self._build_flow_layers()
+        self._refine_model = build_refinement_model(32 + 2, 2, self._leaky_relu_alpha)
+        # every level but the top one also sees the flow and the context from the level above
+        self._flow_layers = build_flow_layers([81 + 32 + 2 + self._num_context_up_channels] * (self._num_levels - 2) + [81 + 32],
+                                              [2] * (self._num_levels - 1), self._leaky_relu_alpha)
         self._context_up_layers = nn.ModuleList(
             [nn.ConvTranspose2d(32, 32, kernel_size=(4, 4), stride=2, padding=1) for _ in range(self._num_levels)])
         self._feature_pyramid_extractor = PWCFeaturePyramid()
@@ -87,39 +145,9 @@ class PWCFlow(nn.Module):
     def init_weights(self):
         init_conv_weights(self, 'xavier')
 
-    def _build_flow_layers(self):
-        """models/uflow_model.py:297-323: per level 5 dense 3x3 blocks (128,128,96,64,32) and a 32->2
-        head that sees only the last block."""
-        result = nn.ModuleList([None])
-        for i in range(1, self._num_levels):
-            layers = nn.ModuleList()
-            c_in = 81 + 32 + (0 if i == self._num_levels - 1 else 2 + self._num_context_up_channels)
-            for c in (128, 128, 96, 64, 32):
-                layers.append(ConvAct(nn.Conv2d(c_in, c, kernel_size=(3, 3), stride=1, padding='same'),
-                                      nn.LeakyReLU(negative_slope=self._leaky_relu_alpha)))
-                c_in += c
-            layers.append(nn.Conv2d(32, 2, kernel_size=(3, 3), padding='same'))
-            result.append(layers)
-        return result
-
-    def _build_refinement_model(self):
-        """models/uflow_model.py:325-348."""
-        layers = []
-        c_in = 32 + 2
-        for c, d in [(128, 1), (128, 2), (128, 4), (96, 8), (64, 16), (32, 1)]:
-            layers.append(nn.Conv2d(c_in, c, kernel_size=(3, 3), stride=1, padding='same', dilation=d))
-            layers.append(nn.LeakyReLU(negative_slope=self._leaky_relu_alpha))
-            c_in = c
-        layers.append(nn.Conv2d(c_in, 2, kernel_size=(3, 3), stride=1, padding='same'))
-        return nn.ModuleList(layers)
-
     def _drops(self, n_passes, batch_per_pass, device):
-        n = (self._num_levels - 1) + 1  # one per level 4..1, then one for the refinement
-        if not (self.training and self._drop_out_rate > 0):
-            return None
-        vals = [[float(torch.rand(1) > self._drop_out_rate) for _ in range(n)] for _ in range(n_passes)]
-        t = torch.tensor(vals, dtype=torch.float32).repeat_interleave(batch_per_pass, dim=0).t().contiguous()
-        return t.to(device, non_blocking=True).view(n, -1, 1, 1, 1)
+        """One multiplier per level 4..1, then one for the refinement."""
+        return level_drops(self.training, self._drop_out_rate, self._num_levels, n_passes, batch_per_pass, device)
 
     def forward_2_frames(self, feature_pyramid1, feature_pyramid2, drops=None, moments=None):
         """models/uflow_model.py:138-245.  moments: optional (rows of the first maps, rows of the second maps) per pyramid
@@ -154,33 +182,13 @@ class PWCFlow(nn.Module):
                 before = () if level == top else (context_up, flow_up)
                 x_in = cost_volume_concat(f1n, w2n, before, (features1,), max_displacement=4,
                                           negative_slope=self._leaky_relu_alpha)
-            layers = self._flow_layers[level]
-            x_out = None
-            for layer in layers[:-1]:
-                x_out = layer(x_in)
-                x_in = torch.cat([x_in, x_out], dim=1)
-            context = x_out
-            flow = layers[-1](context)
-            if drops is not None:
-                context = context * drops[k]
-                flow = flow * drops[k]
+            context, flow = dense_level(self._flow_layers[level], x_in, None if drops is None else drops[k])
             k += 1
             if level != top:
                 flow = flow + flow_up
             context_up = self._context_up_layers[level](context)
             flows.insert(0, flow)
-        refinement = torch.cat([context, flow], dim=1)
-        mods = list(self._refine_model)
-        i = 0
-        while i < len(mods):  # Conv2d followed by LeakyReLU -> bias-free conv + fused bias / LeakyReLU pass
-            m = mods[i]
-            if isinstance(m, nn.Conv2d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.LeakyReLU):
-                refinement = blocks.bias_act(func.conv2d(refinement, m.weight, None, m.stride, m.padding, m.dilation),
-                                             m.bias, mods[i + 1].negative_slope)
-                i += 2
-            else:
-                refinement = m(refinement)
-                i += 1
+        refinement = refine(self._refine_model, torch.cat([context, flow], dim=1))
         if drops is not None:
             refinement = refinement * drops[k]
         flows[0] = flow + refinement
@@ -194,21 +202,5 @@ class PWCFlow(nn.Module):
             raise NotImplementedError
         B = x.size(0)
         pyr_all = self._feature_pyramid_extractor(torch.cat([x[:, 0:3], x[:, 3:6]], 0))
-        moms = self._feature_pyramid_extractor.pyramid_moments
-        have_m = moms is not None and all(t is not None for t in moms)
-        p1 = [p[:B] for p in pyr_all]
-        p2 = [p[B:] for p in pyr_all]
-        res = {}
-        if with_bk:
-            # first maps of the 2B (fw; bw) samples = the extractor's batch as it stands (no copy), second maps = its two
-            # halves swapped; the same holds for the rows of partial moments
-            a = list(pyr_all)
-            b = [torch.cat([p[B:], p[:B]], 0) for p in pyr_all]
-            m = (list(moms), [torch.roll(t, B, 0) for t in moms]) if have_m else None
-            flows = self.forward_2_frames(a, b, self._drops(2, B, x.device), m)
-            res['flows_fw'] = [f[:B] for f in flows]
-            res['flows_bw'] = [f[B:] for f in flows]
-        else:
-            m = ([t[:B] for t in moms], [t[B:] for t in moms]) if have_m else None
-            res['flows_fw'] = self.forward_2_frames(p1, p2, self._drops(1, B, x.device), m)
-        return res
+        return pair_pass(pyr_all, self._feature_pyramid_extractor.pyramid_moments, B, with_bk,
+                         lambda p1, p2, n_passes, m: self.forward_2_frames(p1, p2, self._drops(n_passes, B, x.device), m))

@@ -2,11 +2,7 @@
 This is what configs/chairs_uflow_elbo*.json instantiate (``"model": {"type": "uflow_prob"}``): PWCFlow with wider heads.
 Every level carries out_channels = [L, M, N] channels -- L = 2 flow channels (used for warping), M log-diagonal channels of
 the covariance / precision factor, N further channels (the off-diagonal band) that only the output level produces -- and
-brings them to the next level with upsample_out (:223-250): AF.out_upsample / AF.out_tail.
-
-The ops the CPU oracle substitutes (oracle.host_models.oracle_ops) are reached through the uflow_model module's attributes
-and blocks.bias_act, so a twin of this model runs on the oracle ops as it stands; such a twin (bias_act swapped out) also
-keeps the composed ATen upsample, the convention of blocks.HeadConv.native."""
+brings them to the next level with upsample_out (:223-250): AF.out_upsample / AF.out_tail."""
 import math
 
 import torch
@@ -16,9 +12,12 @@ import torch.nn.functional as func
 from .. import functional as AF
 from .. import uflow_utils
 from . import blocks
+# normalize_features, cost_volume_concat and uflow_utils.resample_flow are called as attributes of the uflow_model module
+# (mum.*), never bound here: oracle.host_models.oracle_ops substitutes exactly those attributes, and blocks.bias_act, so a
+# twin of this model runs on the oracle ops as it stands
 from . import uflow_model as mum
-from .blocks import ConvAct, init_conv_weights
-from .uflow_model import PWCFeaturePyramid, PWCFlow
+from .blocks import init_conv_weights, level_drops, pair_pass
+from .uflow_model import PWCFeaturePyramid, build_flow_layers, build_refinement_model, dense_level, refine
 
 
 class PWCProbFlow(nn.Module):
@@ -44,8 +43,12 @@ class PWCProbFlow(nn.Module):
         # added to the log-diagonal at every x2 upsample (:170): the standard deviation doubles with the resolution
         self._diag_bias = -math.log(2) if cfg.inv_cov else math.log(2)
         # registration order matters for state_dict order: refine, flow layers, upsample, pyramid(s)
-        self._refine_model = self._build_refinement_model()
-        self._flow_layers = self._build_flow_layers()
+        n01, nall = sum(self._out_channels[0:2]), sum(self._out_channels)
+        self._refine_model = build_refinement_model(32 + nall, nall, self._leaky_relu_alpha)  # :479-502: all L + M + N channels
+        # :440-477: every level's input has context_up and out_up (the top level too); the head emits L + M + N channels at
+        # level 1 and L + M at levels 2..4
+        self._flow_layers = build_flow_layers([81 + 32 + n01 + self._num_context_up_channels] * (self._num_levels - 1),
+                                              [nall] + [n01] * (self._num_levels - 2), self._leaky_relu_alpha)
         self._context_up_layers = nn.ModuleList(
             [nn.ConvTranspose2d(32, 32, kernel_size=(4, 4), stride=2, padding=1) for _ in range(self._num_levels)])
         self._feature_pyramid_extractor = nn.ModuleList([PWCFeaturePyramid() for _ in range(cfg.n_pyramids)])
@@ -53,37 +56,12 @@ class PWCProbFlow(nn.Module):
     def init_weights(self):
         init_conv_weights(self, 'kaiming')  # :209-221: kaiming-normal fan_in, zero biases
 
-    def _build_flow_layers(self):
-        """:440-477: as PWCFlow, but every level's input has context_up and out_up (the top level too), and the head emits
-        L + M channels at levels 4..2 and L + M + N at level 1."""
-        result = nn.ModuleList([None])
-        n01, nall = sum(self._out_channels[0:2]), sum(self._out_channels)
-        for i in range(1, self._num_levels):
-            layers = nn.ModuleList()
-            c_in = 81 + 32 + n01 + self._num_context_up_channels
-            for c in (128, 128, 96, 64, 32):
-                layers.append(ConvAct(nn.Conv2d(c_in, c, kernel_size=(3, 3), stride=1, padding='same'),
-                                      nn.LeakyReLU(negative_slope=self._leaky_relu_alpha)))
-                c_in += c
-            layers.append(nn.Conv2d(32, nall if i == 1 else n01, kernel_size=(3, 3), padding='same'))
-            result.append(layers)
-        return result
-
-    def _build_refinement_model(self):
-        """:479-502: the dilated refinement over all L + M + N channels."""
-        layers = []
-        nall = sum(self._out_channels)
-        c_in = 32 + nall
-        for c, d in [(128, 1), (128, 2), (128, 4), (96, 8), (64, 16), (32, 1)]:
-            layers.append(nn.Conv2d(c_in, c, kernel_size=(3, 3), stride=1, padding='same', dilation=d))
-            layers.append(nn.LeakyReLU(negative_slope=self._leaky_relu_alpha))
-            c_in = c
-        layers.append(nn.Conv2d(c_in, nall, kernel_size=(3, 3), stride=1, padding='same'))
-        return nn.ModuleList(layers)
-
-    _drops = PWCFlow._drops  # one draw per level 4..1, then one for the refinement; all of a direction before the next
+    def _drops(self, n_passes, batch_per_pass, device):
+        """One multiplier per level 4..1, then one for the refinement."""
+        return level_drops(self.training, self._drop_out_rate, self._num_levels, n_passes, batch_per_pass, device)
 
     def _native_up(self, x):
+        """A twin that has swapped bias_act out keeps the composed ATen upsample: the convention of blocks.HeadConv.native."""
         return AF.out_up_supported(x) and blocks.bias_act is AF.bias_leaky_relu
 
     def upsample_out(self, out):
@@ -143,34 +121,14 @@ class PWCProbFlow(nn.Module):
                                                   moments_across_channels=True, moments_across_images=True)
                 x_in = mum.cost_volume_concat(f1n, w2n, (context_up, out_up), (features1,), max_displacement=4,
                                               negative_slope=alpha)
-            layers = self._flow_layers[level]
-            x_out = None
-            for layer in layers[:-1]:
-                x_out = layer(x_in)
-                x_in = torch.cat([x_in, x_out], dim=1)
-            context = x_out
-            out = layers[-1](context)
-            if drops is not None:
-                context = context * drops[k]
-                out = out * drops[k]
+            context, out = dense_level(self._flow_layers[level], x_in, None if drops is None else drops[k])
             k += 1
             if out.shape[1] > n01:  # :337-341: the output level's head is wider than what came up the pyramid
                 out_up = func.pad(out_up, (0, 0, 0, 0, 0, out.shape[1] - n01))
             out = out + out_up
             context_up = self._context_up_layers[level](context)
             outs.insert(0, out)
-        refinement = torch.cat([context, out], dim=1)
-        mods = list(self._refine_model)
-        i = 0
-        while i < len(mods):  # Conv2d followed by LeakyReLU -> bias-free conv + fused bias / LeakyReLU pass
-            m = mods[i]
-            if isinstance(m, nn.Conv2d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.LeakyReLU):
-                refinement = blocks.bias_act(func.conv2d(refinement, m.weight, None, m.stride, m.padding, m.dilation),
-                                             m.bias, mods[i + 1].negative_slope)
-                i += 2
-            else:
-                refinement = m(refinement)
-                i += 1
+        refinement = refine(self._refine_model, torch.cat([context, out], dim=1))
         if drops is not None:
             refinement = refinement * drops[k]
         refined = out + refinement
@@ -191,20 +149,5 @@ class PWCProbFlow(nn.Module):
         B = img1.size(0)
         extractor = self._feature_pyramid_extractor[0]
         pyr_all = extractor(torch.cat([img1, img2], 0))
-        moms = extractor.pyramid_moments
-        have_m = moms is not None and all(t is not None for t in moms)
-        res = {}
-        if with_bk:
-            # both directions as one 2B pass, as PWCFlow.forward: first maps = the extractor's batch as it stands, second
-            # maps = its halves swapped; the same for the rows of partial moments
-            a = list(pyr_all)
-            b = [torch.cat([p[B:], p[:B]], 0) for p in pyr_all]
-            m = (list(moms), [torch.roll(t, B, 0) for t in moms]) if have_m else None
-            flows = self.forward_2_frames(a, b, self._drops(2, B, img1.device), m)
-            res['flows_fw'] = [f[:B] for f in flows]
-            res['flows_bw'] = [f[B:] for f in flows]
-        else:
-            m = ([t[:B] for t in moms], [t[B:] for t in moms]) if have_m else None
-            res['flows_fw'] = self.forward_2_frames([p[:B] for p in pyr_all], [p[B:] for p in pyr_all],
-                                                    self._drops(1, B, img1.device), m)
-        return res
+        return pair_pass(pyr_all, extractor.pyramid_moments, B, with_bk,
+                         lambda p1, p2, n_passes, m: self.forward_2_frames(p1, p2, self._drops(n_passes, B, img1.device), m))
