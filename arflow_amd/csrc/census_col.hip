@@ -41,30 +41,22 @@ __global__ __launch_bounds__(census_col::NT) void fwd_col_kernel(const float* __
   const int x = x0 + lane;
   float part[2] = {0.f, 0.f};
   if (lane >= R && x < W) {
-    const bool colin = x >= R && x < W - R;
 #pragma unroll
     for (int i = 0; i < cc::K; ++i) {
       const int y = y0 + w * cc::K + i;
       if (y < H) {
         float mv = tm[(R + w * cc::K + i) * cc::PITCH + lane];  // mask_invalid; x the upsampled range map
         if (occ) mv *= cc::up4_lds(tocc, H / 4, W / 4, y0, ox, y, x);
-        const float pm = (colin && y >= R && y < H - R) ? mv : 0.f;
-        const float lg = __log2f(fabsf(s[i]) + 0.01f);
-        part[0] += exp2f(0.4f * lg) * pm;
-        part[1] += pm;
+        float dh;
+        ham_loss_terms(s[i], interior(y, x, H, W, R) ? mv : 0.f, part, dh);
         const long o = (long)b * cs + (long)y * W + x;
         if (mask_out) mask_out[o] = mv;
-        dham_out[o] = pm * 0.4f * exp2f(-0.6f * lg);
+        dham_out[o] = dh;
       }
     }
   }
   af_block_sum<2>(part, red);
-  if (threadIdx.x == 0) {
-    if (pair && (b & 1))
-      af_store_partial(sums, nrows, 0.f, 0.f, part[0], part[1]);
-    else
-      af_store_partial(sums, nrows, part[0], part[1], 0.f);
-  }
+  if (threadIdx.x == 0) store_dir_partial(sums, nrows, part, pair, b);
 }
 
 template <int R>
@@ -92,15 +84,14 @@ __device__ __forceinline__ void bwd_col_body(const float* __restrict__ gray_a, c
   if (lane < R || x >= W) return;
   // d loss / d grey_b(p) = sc * acc (census4::bwd_kernel's value before the colour weights; the x255 lives in the
   // grey plane), times the warp's flow gradient (tcx, tcy)
-  const float sc = (scale ? scale[pair ? (b & 1) : 0] : 1.f) * (0.1f * -2.f * 0.81f);  // pair: one scale per direction
+  const float sc = dir_scale(scale, pair, b);
 #pragma unroll
   for (int i = 0; i < cc::K; ++i) {
     const int y = y0 + w * cc::K + i;
     if (y < H) {
       const int o = (R + w * cc::K + i) * cc::PITCH + lane;
-      float* gf = gflow + (long)b * 2 * cs + (long)y * W + x;
-      gf[0] = sc * acc[i] * tcx[o];
-      gf[cs] = sc * acc[i] * tcy[o];
+      const float a1[1] = {acc[i]}, cx[1] = {tcx[o]}, cy[1] = {tcy[o]};
+      store_flow_grad<1>(gflow + (long)b * 2 * cs + (long)y * W + x, cs, sc, a1, cx, cy);
     }
   }
 }
@@ -130,11 +121,7 @@ __global__ __launch_bounds__(census_col::NT) void pair_bwd_smooth_col_kernel(con
     bwd_col_body<R>(gray, gray, flow, fbs, dham, scale2, gflow, nimg, H, W, 1);
     return;
   }
-  const unsigned i = blockIdx.x - census_blocks;  // (b, y, x-block) of the level-2 grid
-  const unsigned nxb = (unsigned)((sa.W + 255) / 256);
-  const int xb = (int)(i % nxb), y = (int)((i / nxb) % (unsigned)sa.H), b = (int)(i / (nxb * (unsigned)sa.H));
-  const int x = xb * 256 + (int)threadIdx.x;
-  if (b < nimg && x < sa.W) smooth_bwd_pixel<3>(sa, coef, gflow2, b, y, x);
+  smooth_bwd_role(sa, coef, gflow2, nimg, blockIdx.x - census_blocks);
 }
 
 }  // namespace census_warp
@@ -149,11 +136,10 @@ int census_col_fwd(const float* gray_a, const float* gray_b, const float* flow, 
                    hipStream_t st) {
   namespace cw = census_warp;
   dim3 g(col_grid(B, H, W, radius)), t(census_col::NT);
-  switch (radius) {
-    case 1: hipLaunchKernelGGL(cw::fwd_col_kernel<1>, g, t, 0, st, gray_a, gray_b, flow, fbs, occ_small, mask_out, dham, sums, nrows, B, H, W, pair); break;
-    case 2: hipLaunchKernelGGL(cw::fwd_col_kernel<2>, g, t, 0, st, gray_a, gray_b, flow, fbs, occ_small, mask_out, dham, sums, nrows, B, H, W, pair); break;
-    default: hipLaunchKernelGGL(cw::fwd_col_kernel<3>, g, t, 0, st, gray_a, gray_b, flow, fbs, occ_small, mask_out, dham, sums, nrows, B, H, W, pair); break;
-  }
+  af_dispatch_radius(radius, [&](auto R) {
+    hipLaunchKernelGGL(cw::fwd_col_kernel<decltype(R)::value>, g, t, 0, st, gray_a, gray_b, flow, fbs, occ_small, mask_out, dham,
+                       sums, nrows, B, H, W, pair);
+  });
   return af_launch_status();
 }
 
@@ -161,11 +147,10 @@ int census_col_bwd(const float* gray_a, const float* gray_b, const float* flow, 
                    const float* scale, float* gflow, int B, int H, int W, int radius, int pair, hipStream_t st) {
   namespace cw = census_warp;
   dim3 g(col_grid(B, H, W, radius)), t(census_col::NT);
-  switch (radius) {
-    case 1: hipLaunchKernelGGL(cw::bwd_col_kernel<1>, g, t, 0, st, gray_a, gray_b, flow, fbs, dham, scale, gflow, B, H, W, pair); break;
-    case 2: hipLaunchKernelGGL(cw::bwd_col_kernel<2>, g, t, 0, st, gray_a, gray_b, flow, fbs, dham, scale, gflow, B, H, W, pair); break;
-    default: hipLaunchKernelGGL(cw::bwd_col_kernel<3>, g, t, 0, st, gray_a, gray_b, flow, fbs, dham, scale, gflow, B, H, W, pair); break;
-  }
+  af_dispatch_radius(radius, [&](auto R) {
+    hipLaunchKernelGGL(cw::bwd_col_kernel<decltype(R)::value>, g, t, 0, st, gray_a, gray_b, flow, fbs, dham, scale, gflow, B, H, W,
+                       pair);
+  });
   return af_launch_status();
 }
 
@@ -176,12 +161,10 @@ int census_col_pair_bwd_smooth(const float* gray, const float* flow, long fbs, c
   namespace cw = census_warp;
   const SmoothArgs sa{flow2, img2, 3, h2, w2, flow2_bstride, flow_scale, alpha, order, wmode, penalty};
   const unsigned cb = col_grid(B2, H, W, radius);
-  const unsigned sb = (unsigned)af_cdiv(sa.W, 256) * (unsigned)sa.H * (unsigned)B2;
-  dim3 g(cb + sb), t(census_col::NT);
-  switch (radius) {
-    case 1: hipLaunchKernelGGL(cw::pair_bwd_smooth_col_kernel<1>, g, t, 0, st, gray, flow, fbs, dham, scale2, gflow, B2, H, W, cb, sa, coef2, gflow2); break;
-    case 2: hipLaunchKernelGGL(cw::pair_bwd_smooth_col_kernel<2>, g, t, 0, st, gray, flow, fbs, dham, scale2, gflow, B2, H, W, cb, sa, coef2, gflow2); break;
-    default: hipLaunchKernelGGL(cw::pair_bwd_smooth_col_kernel<3>, g, t, 0, st, gray, flow, fbs, dham, scale2, gflow, B2, H, W, cb, sa, coef2, gflow2); break;
-  }
+  dim3 g(cb + smooth_role_blocks(sa, B2)), t(census_col::NT);
+  af_dispatch_radius(radius, [&](auto R) {
+    hipLaunchKernelGGL(cw::pair_bwd_smooth_col_kernel<decltype(R)::value>, g, t, 0, st, gray, flow, fbs, dham, scale2, gflow, B2, H,
+                       W, cb, sa, coef2, gflow2);
+  });
   return af_launch_status();
 }

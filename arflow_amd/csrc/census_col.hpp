@@ -17,7 +17,8 @@
 //   * only left neighbours send, so only the R leftmost lanes of a wave are halo (their sums are incomplete and dropped):
 //     64 - R useful columns per wave; rows R above / below the strip are evaluated as senders only.
 // Evaluations per owned pixel: (24 K + 42) / K * 64 / 61 = 30.7 (K = 8, R = 3) instead of 48 (+ the centre tap).
-// The ROUNDING differs from the ordered kernels only in the order the 48 terms of a pixel are added.
+// The ROUNDING differs from the ordered kernels only in the order the 48 terms of a pixel are added: the pair term is
+// pair_dist / pair_grad of census_dev.hpp for every family.
 #pragma once
 #include "census_tile.hpp"
 #include "taps.hpp"
@@ -162,9 +163,7 @@ __device__ __forceinline__ void fill_tiles(float* __restrict__ ta, float* __rest
           t3[o] = sx * t[k].dx;
           t4[o] = sy * t[k].dy;
         } else {
-          // mask_invalid(flow_to_warp(flow)), utils/uflow_utils.py:35-50 (as warp_fwd_kernel's `valid`)
-          const float cx = (float)gx[k] + u[k], cy = (float)gy[k] + v[k];
-          const float mv = (cx >= 0.f && cx <= (float)(W - 1) && cy >= 0.f && cy <= (float)(H - 1)) ? 1.f : 0.f;
+          const float mv = flow_valid(gx[k], gy[k], u[k], v[k], H, W);
           t2[o] = in[k] ? mv : 0.f;
         }
       }
@@ -176,9 +175,7 @@ __device__ __forceinline__ void fill_tiles(float* __restrict__ ta, float* __rest
 // range map under the tile are staged once per workgroup, already clamped (one load per thread instead of 4 gathers per
 // pixel), and up4_lds applies torch's bilinear arithmetic (align_corners=False, as up4_clamped) to them.
 constexpr int OCC_R = TROWS / 4 + 2, OCC_C = 64 / 4 + 3, OCC_P = OCC_C + 1;
-__device__ __forceinline__ int up4_first(int p) {  // first source cell of output index p (>= 0)
-  return (int)fmaxf(0.25f * ((float)p + 0.5f) - 0.5f, 0.f);
-}
+__device__ __forceinline__ int up4_first(int p) { return (int)up4_src(p); }  // first source cell of output index p (>= 0)
 __device__ __forceinline__ void stage_occ(float* __restrict__ tocc, const float* __restrict__ occ, int h4, int w4, int y0,
                                           int x0) {  // y0, x0: first OWNED row / column of the tile (>= 0)
   const int oy0 = up4_first(y0), ox0 = up4_first(x0);
@@ -189,14 +186,10 @@ __device__ __forceinline__ void stage_occ(float* __restrict__ tocc, const float*
   }
 }
 __device__ __forceinline__ float up4_lds(const float* __restrict__ tocc, int h4, int w4, int y0, int x0, int y, int x) {
-  const float sy = fmaxf(0.25f * ((float)y + 0.5f) - 0.5f, 0.f), sx = fmaxf(0.25f * ((float)x + 0.5f) - 0.5f, 0.f);
-  const int ya = (int)sy, xa = (int)sx;
-  const int yb = ya + (ya < h4 - 1 ? 1 : 0), xb = xa + (xa < w4 - 1 ? 1 : 0);
-  const float ly = sy - (float)ya, lx = sx - (float)xa;
+  const Up4 c = up4_coords(h4, w4, y, x);
   const int oy0 = up4_first(y0), ox0 = up4_first(x0);
-  const float v00 = tocc[(ya - oy0) * OCC_P + xa - ox0], v01 = tocc[(ya - oy0) * OCC_P + xb - ox0];
-  const float v10 = tocc[(yb - oy0) * OCC_P + xa - ox0], v11 = tocc[(yb - oy0) * OCC_P + xb - ox0];
-  return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+  return c.blend(tocc[(c.ya - oy0) * OCC_P + c.xa - ox0], tocc[(c.ya - oy0) * OCC_P + c.xb - ox0],
+                 tocc[(c.yb - oy0) * OCC_P + c.xa - ox0], tocc[(c.yb - oy0) * OCC_P + c.xb - ox0]);
 }
 
 // column `col` of a tile, rows [row0, row0 + K + 2R) -> registers
@@ -212,41 +205,10 @@ __device__ __forceinline__ void shift_right_1(float (&t)[NV]) {
   for (int k = 0; k < NV; ++k) t[k] = __shfl_up(t[k], 1, 64);  // lane l <- lane l-1 (lane 0 keeps its own: a halo lane)
 }
 
-// upsample(clamp(occ, 0, 1), x4)[y, x]: torch bilinear, align_corners=False (as up4_clamp_mul_kernel, smooth.hip)
-__device__ __forceinline__ float up4_clamped(const float* __restrict__ occ, int h, int w, int y, int x) {
-  const float sy = fmaxf(0.25f * ((float)y + 0.5f) - 0.5f, 0.f), sx = fmaxf(0.25f * ((float)x + 0.5f) - 0.5f, 0.f);
-  const int y0 = (int)sy, x0 = (int)sx;
-  const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-  const float ly = sy - (float)y0, lx = sx - (float)x0;
-  auto cl = [](float v) { return fminf(fmaxf(v, 0.f), 1.f); };
-  const float v00 = cl(occ[(long)y0 * w + x0]), v01 = cl(occ[(long)y0 * w + x1]);
-  const float v10 = cl(occ[(long)y1 * w + x0]), v11 = cl(occ[(long)y1 * w + x1]);
-  return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
-}
-
 template <int NV>
 __device__ __forceinline__ void pin(float (&t)[NV]) {
 #pragma unroll
   for (int k = 0; k < NV; ++k) asm volatile("" : "+v"(t[k]));
-}
-
-// soft census distance of one pixel pair: (t_a - t_b)^2 / (0.1 + (t_a - t_b)^2), t = d / sqrt(0.81 + d^2)
-__device__ __forceinline__ float pair_dist(float ac, float bc, float an, float bn) {
-  const float da = an - ac, db = bn - bc;
-  const float tb = db * __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-  const float e = fmaf(da, __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f)), -tb), sq = e * e;
-  return sq * __builtin_amdgcn_rcpf(0.1f + sq);  // (folding this product into the two accumulations as FMAs: forward 81 -> 84 us)
-}
-// its derivative w.r.t. the warped grey value of the FIRST pixel (before the constant 0.1 * -2 * 0.81), as
-// census_warp::bwd_body evaluates it; odd under exchange of the two pixels
-__device__ __forceinline__ float pair_grad(float ac, float bc, float an, float bn) {
-  const float da = ac - an, db = bc - bn;
-  const float ua = __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f));
-  const float ub = __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-  const float e = fmaf(da, ua, -(db * ub));
-  const float q = __builtin_amdgcn_rcpf(fmaf(e, e, 0.1f));
-  const float w = q * ub;  // q^2 e ub^3 = (q ub)^2 (e ub): 4 multiplications instead of 5
-  return (w * w) * (e * ub);
 }
 
 // Sum over the (2R+1)^2 - 1 neighbours of every pixel of the lane's K-row strip: s[i] = sum_o dist(pixel i, pixel i + o).

@@ -39,19 +39,6 @@ constexpr int GUARD = 4;                  // floats before / after V and the car
 __host__ __device__ constexpr int carry_base(int ky) { return (2 * MAXR + 1) * LW * (ky * (ky - 1) / 2); }  // rows before ky
 constexpr int CARRY = carry_base(MAXR + 1);  // floats per parity
 
-template <int R>
-__device__ __forceinline__ void load_plane(float* __restrict__ tile, const float* __restrict__ g, int H, int W, int cy0,
-                                           int tx0 /* image column of tile column 0 */, int tid) {
-  constexpr int NR = CH + R, NQ = 18;
-  for (int i = tid; i < NR * NQ; i += NT) {
-    const int r = i / NQ, q = i - r * NQ;
-    const int gy = cy0 + r, gx = tx0 + 4 * q;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = *reinterpret_cast<const float4*>(g + (long)gy * W + gx);
-    *reinterpret_cast<float4*>(tile + r * PITCH + 4 * q) = v;
-  }
-}
-
 // warped grey tile: rows [cy0, cy0+CH+R), tile columns 1 .. 70 (image tx0+1 ..); zero outside the image.
 // Rounds of UNR pixels per thread: all flow loads of a round in flight together, then all 4 x UNR taps.
 template <int R>
@@ -89,17 +76,6 @@ __device__ __forceinline__ void load_warped(float* __restrict__ tile, const floa
     for (int k = 0; k < UNR; ++k)
       if (dst[k] >= 0) tile[dst[k]] = in[k] ? tap_blend(p[k], a[k]) : 0.f;
   }
-}
-
-__device__ __forceinline__ float up4_clamped(const float* __restrict__ occ, int h, int w, int y, int x) {
-  const float sy = fmaxf(0.25f * ((float)y + 0.5f) - 0.5f, 0.f), sx = fmaxf(0.25f * ((float)x + 0.5f) - 0.5f, 0.f);
-  const int y0 = (int)sy, x0 = (int)sx;
-  const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-  const float ly = sy - (float)y0, lx = sx - (float)x0;
-  auto cl = [](float v) { return fminf(fmaxf(v, 0.f), 1.f); };
-  const float v00 = cl(occ[(long)y0 * w + x0]), v01 = cl(occ[(long)y0 * w + x1]);
-  const float v10 = cl(occ[(long)y1 * w + x0]), v11 = cl(occ[(long)y1 * w + x1]);
-  return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
 }
 
 __device__ __forceinline__ void st4(float* p, const float (&v)[4]) {
@@ -151,19 +127,11 @@ __device__ __forceinline__ void pass_send(const Lds& L, int g, int ly, int parit
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int k = 4 + p + kx;  // window column of the neighbour
-      const float da = wa[k] - ca[p], db = wb[k] - cb[p];
       if (!BWD) {
-        const float tb = db * __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-        const float e = fmaf(da, __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f)), -tb), sq = e * e;
-        v[p] = sq * __builtin_amdgcn_rcpf(0.1f + sq);
+        v[p] = pair_dist(ca[p], cb[p], wa[k], wb[k]);
         acc[p] += v[p];
       } else {
-        const float ua = __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f));
-        const float ub = __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-        const float e = fmaf(da, ua, -(db * ub));
-        const float q = __builtin_amdgcn_rcpf(fmaf(e, e, 0.1f));
-        const float hd = ((q * e) * q) * ((ub * ub) * ub);
-        v[p] = (wg[k] + cg[p]) * hd;
+        v[p] = (wg[k] + cg[p]) * pair_grad(wa[k], wb[k], ca[p], cb[p]);  // (the derivative at the NEIGHBOUR: odd)
         acc[p] -= v[p];
       }
     }
@@ -260,35 +228,18 @@ __global__ __launch_bounds__(NT, 2) void kernel(const float* __restrict__ gray_a
     const int x0 = sx0 - 4 + 4 * g;  // image column of this lane's first pixel
     const bool out_col = g >= 1 && g <= SW / 4 && x0 < W;
 #ifdef SYM_AB_NO_WARP  // A/B timing only (tools/): plain tile instead of the sampled one -> wrong results
-    load_plane<R>(lds_gb, gb_p, H, W, cy0, sx0 - 8, tid);
+    census4::load_plane_rows<CH + R>(lds_gb, gb_p, H, W, cy0, sx0 - 8, tid);
 #else
     load_warped<R>(lds_gb, gb_p, fl, H, W, cy0, sx0 - 8, tid);
 #endif
-    load_plane<R>(lds_ga, ga_p, H, W, cy0, sx0 - 8, tid);
-    if (BWD) load_plane<R>(lds_gw, dham + b * cs, H, W, cy0, sx0 - 8, tid);
+    census4::load_plane_rows<CH + R>(lds_ga, ga_p, H, W, cy0, sx0 - 8, tid);
+    if (BWD) census4::load_plane_rows<CH + R>(lds_gw, dham + b * cs, H, W, cy0, sx0 - 8, tid);
     __syncthreads();
     const int y = cy0 + ly;
     const bool out = out_col && y >= sy0 && y < sy1;  // this lane's 4 pixels are outputs of this strip
     // backward: the corner differences of the grey plane at this lane's pixels (gathers in flight during the passes)
     float cdx[4] = {0.f, 0.f, 0.f, 0.f}, cdy[4] = {0.f, 0.f, 0.f, 0.f};
-    if (BWD && out) {
-      const long o = (long)y * W + x0;
-      const float4 fu = *reinterpret_cast<const float4*>(fl + o);
-      const float4 fv = *reinterpret_cast<const float4*>(fl + cs + o);
-      const float uu[4] = {fu.x, fu.y, fu.z, fu.w}, vv[4] = {fv.x, fv.y, fv.z, fv.w};
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const Taps t = make_taps((float)(x0 + p), (float)y, uu[p], vv[p], H, W, H, W, ARFLOW_PAD_ZEROS, true, ARFLOW_NORM_UFLOW);
-        const TapPlan pl = plan_taps(t, H, W);
-        float a[4], sx, sy;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) a[q] = gb_p[pl.o[q]];
-        tap_select(pl, a, a);
-        tap_corner_grad(t, a, sx, sy);
-        cdx[p] = sx * t.dx;
-        cdy[p] = sy * t.dy;
-      }
-    }
+    if (BWD && out) corner_grads4(gb_p, fl, x0, y, H, W, cdx, cdy);
     float ca[4], cb[4], cg[4] = {0.f, 0.f, 0.f, 0.f}, acc[4] = {0.f, 0.f, 0.f, 0.f};
     {
       float w0[12];
@@ -308,32 +259,12 @@ __global__ __launch_bounds__(NT, 2) void kernel(const float* __restrict__ gray_a
     if (out) {
       const long o = (long)y * W + x0;
       if (!BWD) {
-        const float4 fu = *reinterpret_cast<const float4*>(fl + o);
-        const float4 fv = *reinterpret_cast<const float4*>(fl + cs + o);
-        const float uu[4] = {fu.x, fu.y, fu.z, fu.w}, vv[4] = {fv.x, fv.y, fv.z, fv.w};
         float mv[4], dh[4];
-        const bool rowin = y >= R && y < H - R;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          const int xx = x0 + p;
-          const float cx = (float)xx + uu[p], cy = (float)y + vv[p];
-          const float val = (cx >= 0.f && cx <= (float)(W - 1) && cy >= 0.f && cy <= (float)(H - 1)) ? 1.f : 0.f;
-          mv[p] = occ ? up4_clamped(occ, H / 4, W / 4, y, xx) * val : val;
-          const float pm = (rowin && xx >= R && xx < W - R) ? mv[p] : 0.f;
-          const float lg = __log2f(fabsf(acc[p]) + 0.01f);
-          part[0] += exp2f(0.4f * lg) * pm;
-          part[1] += pm;
-          dh[p] = pm * 0.4f * exp2f(-0.6f * lg);
-        }
-        if (mask_out) *reinterpret_cast<float4*>(mask_out + (long)b * cs + o) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-        *reinterpret_cast<float4*>(dham + (long)b * cs + o) = make_float4(dh[0], dh[1], dh[2], dh[3]);
+        masked_loss4(fl, occ, acc, x0, y, H, W, R, mv, dh, part);
+        if (mask_out) store_row<4>(mask_out + (long)b * cs + o, mv);
+        store_row<4>(dham + (long)b * cs + o, dh);
       } else {
-        const float sc = (scale ? scale[0] : 1.f) * (0.1f * -2.f * 0.81f);
-        float* gf = gflow + (long)b * 2 * cs + o;
-        *reinterpret_cast<float4*>(gf) =
-            make_float4(sc * acc[0] * cdx[0], sc * acc[1] * cdx[1], sc * acc[2] * cdx[2], sc * acc[3] * cdx[3]);
-        *reinterpret_cast<float4*>(gf + cs) =
-            make_float4(sc * acc[0] * cdy[0], sc * acc[1] * cdy[1], sc * acc[2] * cdy[2], sc * acc[3] * cdy[3]);
+        store_flow_grad<4>(gflow + (long)b * 2 * cs + o, cs, dir_scale(scale, 0, b), acc, cdx, cdy);
       }
     }
   }
@@ -355,16 +286,19 @@ static int census_sym_strip_h(int B, int H, int W, int R) {
   return 16 * n - R;
 }
 
+static unsigned census_sym_grid(int B, int H, int W, int strip_h) {
+  return af_grid_for_tiles((long)af_cdiv(W, census_sym::SW) * af_cdiv(H, strip_h) * B);
+}
+
 int census_sym_fwd(const float* gray_a, const float* gray_b, const float* flow, long fbs, const float* occ_small,
                    float* mask_out, float* dham, float* sums, int nrows, int B, int H, int W, int radius, hipStream_t st) {
   namespace cs = census_sym;
   const int sh = census_sym_strip_h(B, H, W, radius);
-  dim3 g(af_grid_for_tiles((long)af_cdiv(W, cs::SW) * af_cdiv(H, sh) * B));
-  switch (radius) {
-    case 1: hipLaunchKernelGGL((cs::kernel<1, false>), g, dim3(cs::NT), 0, st, gray_a, gray_b, flow, fbs, occ_small, mask_out, dham, sums, nrows, nullptr, nullptr, B, H, W, sh); break;
-    case 2: hipLaunchKernelGGL((cs::kernel<2, false>), g, dim3(cs::NT), 0, st, gray_a, gray_b, flow, fbs, occ_small, mask_out, dham, sums, nrows, nullptr, nullptr, B, H, W, sh); break;
-    default: hipLaunchKernelGGL((cs::kernel<3, false>), g, dim3(cs::NT), 0, st, gray_a, gray_b, flow, fbs, occ_small, mask_out, dham, sums, nrows, nullptr, nullptr, B, H, W, sh); break;
-  }
+  dim3 g(census_sym_grid(B, H, W, sh));
+  af_dispatch_radius(radius, [&](auto R) {
+    hipLaunchKernelGGL((cs::kernel<decltype(R)::value, false>), g, dim3(cs::NT), 0, st, gray_a, gray_b, flow, fbs, occ_small,
+                       mask_out, dham, sums, nrows, nullptr, nullptr, B, H, W, sh);
+  });
   return af_launch_status();
 }
 
@@ -372,12 +306,11 @@ int census_sym_bwd(const float* gray_a, const float* gray_b, const float* flow, 
                    const float* scale, float* gflow, int B, int H, int W, int radius, hipStream_t st) {
   namespace cs = census_sym;
   const int sh = census_sym_strip_h(B, H, W, radius);
-  dim3 g(af_grid_for_tiles((long)af_cdiv(W, cs::SW) * af_cdiv(H, sh) * B));
+  dim3 g(census_sym_grid(B, H, W, sh));
   float* dh = const_cast<float*>(dham);
-  switch (radius) {
-    case 1: hipLaunchKernelGGL((cs::kernel<1, true>), g, dim3(cs::NT), 0, st, gray_a, gray_b, flow, fbs, nullptr, nullptr, dh, nullptr, 0, scale, gflow, B, H, W, sh); break;
-    case 2: hipLaunchKernelGGL((cs::kernel<2, true>), g, dim3(cs::NT), 0, st, gray_a, gray_b, flow, fbs, nullptr, nullptr, dh, nullptr, 0, scale, gflow, B, H, W, sh); break;
-    default: hipLaunchKernelGGL((cs::kernel<3, true>), g, dim3(cs::NT), 0, st, gray_a, gray_b, flow, fbs, nullptr, nullptr, dh, nullptr, 0, scale, gflow, B, H, W, sh); break;
-  }
+  af_dispatch_radius(radius, [&](auto R) {
+    hipLaunchKernelGGL((cs::kernel<decltype(R)::value, true>), g, dim3(cs::NT), 0, st, gray_a, gray_b, flow, fbs, nullptr, nullptr,
+                       dh, nullptr, 0, scale, gflow, B, H, W, sh);
+  });
   return af_launch_status();
 }

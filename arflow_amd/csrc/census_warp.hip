@@ -23,7 +23,6 @@
 // halo = 1.5 x the tile, 4 taps each) are served by L2 and overlap other workgroups' arithmetic.
 #include <cstdlib>
 
-#include "census_col.hpp"
 #include "census_tile.hpp"
 #include "smooth_dev.hpp"
 #include "taps.hpp"
@@ -31,21 +30,6 @@
 namespace {
 namespace census_warp {
 using namespace census4;
-using census_col::up4_clamped;
-
-// plain grey tile from a [H,W] plane: rows [ty0-R, ty0+TYH+R), columns [tx0-4, tx0+TXW+4), zero outside
-template <int R>
-__device__ __forceinline__ void load_plane(float* __restrict__ tile, const float* __restrict__ g, int H, int W, int ty0,
-                                           int tx0) {
-  constexpr int NR = TYH + 2 * R, NQ = (TXW + 8) / 4;
-  for (int i = threadIdx.x; i < NR * NQ; i += NT) {
-    const int r = i / NQ, q = i - r * NQ;
-    const int gy = ty0 - R + r, gx = tx0 - 4 + 4 * q;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = *reinterpret_cast<const float4*>(g + (long)gy * W + gx);
-    *reinterpret_cast<float4*>(tile + r * PITCH + 4 * q) = v;
-  }
-}
 
 // Grey tile of the WARPED image b: rows [ty0-R, ty0+TYH+R), columns [tx0-R, tx0+TXW+R); zero outside the image
 // (the census transform zero-pads).  All flow loads of a thread are issued together, then all its 4 x ITER taps:
@@ -141,44 +125,20 @@ __global__ __launch_bounds__(NT) void fwd_kernel(const float* __restrict__ gray_
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         const int k = p + dx + 4 - R;
-        const float da = wa[k] - ca[p], db = wb[k] - cb[p];
-        const float tb = db * __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-        const float e = fmaf(da, __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f)), -tb), sq = e * e;
-        s[p] = fmaf(sq, __builtin_amdgcn_rcpf(0.1f + sq), s[p]);
+        s[p] = pair_dist_acc(ca[p], cb[p], wa[k], wb[k], s[p]);
       }
   }
   float part[2] = {0.f, 0.f};
   if (y < H && x0 < W) {  // W % 4 == 0: the 4 pixels are inside together
     const long o = (long)y * W + x0;
-    const float4 fu = *reinterpret_cast<const float4*>(fl + o);
-    const float4 fv = *reinterpret_cast<const float4*>(fl + cs + o);
-    const float uu[4] = {fu.x, fu.y, fu.z, fu.w}, vv[4] = {fv.x, fv.y, fv.z, fv.w};
     const float* occ = occ_small ? occ_small + (long)bp * (H / 4) * (W / 4) : nullptr;
     float mv[4], dh[4];
-    const bool rowin = y >= R && y < H - R;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int xx = x0 + p;
-      // mask_invalid(flow_to_warp(flow)), utils/uflow_utils.py:35-50 (as warp_fwd_kernel's `valid`)
-      const float cx = (float)xx + uu[p], cy = (float)y + vv[p];
-      const float val = (cx >= 0.f && cx <= (float)(W - 1) && cy >= 0.f && cy <= (float)(H - 1)) ? 1.f : 0.f;
-      mv[p] = occ ? up4_clamped(occ, H / 4, W / 4, y, xx) * val : val;
-      const float pm = (rowin && xx >= R && xx < W - R) ? mv[p] : 0.f;
-      const float lg = __log2f(fabsf(s[p]) + 0.01f);
-      part[0] += exp2f(0.4f * lg) * pm;
-      part[1] += pm;
-      dh[p] = pm * 0.4f * exp2f(-0.6f * lg);
-    }
-    if (mask_out) *reinterpret_cast<float4*>(mask_out + (long)b * cs + o) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-    *reinterpret_cast<float4*>(dham_out + (long)b * cs + o) = make_float4(dh[0], dh[1], dh[2], dh[3]);
+    masked_loss4(fl, occ, s, x0, y, H, W, R, mv, dh, part);
+    if (mask_out) store_row<4>(mask_out + (long)b * cs + o, mv);
+    store_row<4>(dham_out + (long)b * cs + o, dh);
   }
   af_block_sum<2>(part, red);
-  if (threadIdx.x == 0) {
-    if (pair && (b & 1))
-      af_store_partial(sums, nrows, 0.f, 0.f, part[0], part[1]);
-    else
-      af_store_partial(sums, nrows, part[0], part[1], 0.f);
-  }
+  if (threadIdx.x == 0) store_dir_partial(sums, nrows, part, pair, b);
 }
 
 template <int R>
@@ -205,23 +165,8 @@ __device__ __forceinline__ void bwd_body(const float* __restrict__ gray_a, const
   if (y >= H || x0 >= W) return;
   // the taps of this lane's 4 pixels (corner differences of the grey plane): issued before the census loop so
   // the 16 gathers are in flight while it runs
-  const long o = (long)y * W + x0;
-  const float4 fu = *reinterpret_cast<const float4*>(fl + o);
-  const float4 fv = *reinterpret_cast<const float4*>(fl + cs + o);
-  const float uu[4] = {fu.x, fu.y, fu.z, fu.w}, vv[4] = {fv.x, fv.y, fv.z, fv.w};
-  float cdx[4], cdy[4];  // (d sample / d coordinate) * (d coordinate / d flow) per pixel
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const Taps t = make_taps((float)(x0 + p), (float)y, uu[p], vv[p], H, W, H, W, ARFLOW_PAD_ZEROS, true, ARFLOW_NORM_UFLOW);
-    const TapPlan pl = plan_taps(t, H, W);
-    float a[4], sx, sy;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) a[q] = sb[pl.o[q]];
-    tap_select(pl, a, a);
-    tap_corner_grad(t, a, sx, sy);
-    cdx[p] = sx * t.dx;
-    cdy[p] = sy * t.dy;
-  }
+  float cdx[4], cdy[4];
+  corner_grads4(sb, fl, x0, y, H, W, cdx, cdy);
   float ca[4], cb[4], cg[4], acc[4] = {0.f, 0.f, 0.f, 0.f};
   {
     float wa[12], wb[12], wg[12];
@@ -243,24 +188,13 @@ __device__ __forceinline__ void bwd_body(const float* __restrict__ gray_a, const
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         const int k = p + dx + 4 - R;
-        const float da = ca[p] - wa[k], db = cb[p] - wb[k];
-        const float ua = __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f));
-        const float ub = __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-        const float e = fmaf(da, ua, -(db * ub));
-        const float q = __builtin_amdgcn_rcpf(fmaf(e, e, 0.1f));
-        const float hd = ((q * e) * q) * ((ub * ub) * ub);
-        acc[p] = fmaf(wg[k] + cg[p], hd, acc[p]);
+        acc[p] = fmaf(wg[k] + cg[p], pair_grad(ca[p], cb[p], wa[k], wb[k]), acc[p]);
       }
     }
   }
   // d loss / d grey_b(p) = sc * acc (census4::bwd_kernel's value before the colour weights; the x255 lives in the
   // grey plane), times the warp's flow gradient
-  const float sc = (scale ? scale[pair ? (b & 1) : 0] : 1.f) * (0.1f * -2.f * 0.81f);  // pair: one scale per direction
-  float* gf = gflow + (long)b * 2 * cs + o;
-  *reinterpret_cast<float4*>(gf) =
-      make_float4(sc * acc[0] * cdx[0], sc * acc[1] * cdx[1], sc * acc[2] * cdx[2], sc * acc[3] * cdx[3]);
-  *reinterpret_cast<float4*>(gf + cs) =
-      make_float4(sc * acc[0] * cdy[0], sc * acc[1] * cdy[1], sc * acc[2] * cdy[2], sc * acc[3] * cdy[3]);
+  store_flow_grad<4>(gflow + (long)b * 2 * cs + (long)y * W + x0, cs, dir_scale(scale, pair, b), acc, cdx, cdy);
 }
 
 template <int R>
@@ -284,11 +218,7 @@ __global__ __launch_bounds__(NT) void pair_bwd_smooth_kernel(const float* __rest
     bwd_body<R>(gray, gray, flow, fbs, dham, scale2, gflow, nimg, H, W, 1);
     return;
   }
-  const unsigned i = blockIdx.x - census_blocks;  // (b, y, x-block) of the level-2 grid
-  const unsigned nxb = (unsigned)((sa.W + 255) / 256);
-  const int xb = (int)(i % nxb), y = (int)((i / nxb) % (unsigned)sa.H), b = (int)(i / (nxb * (unsigned)sa.H));
-  const int x = xb * 256 + (int)threadIdx.x;
-  if (b < nimg && x < sa.W) smooth_bwd_pixel<3>(sa, coef, gflow2, b, y, x);
+  smooth_bwd_role(sa, coef, gflow2, nimg, blockIdx.x - census_blocks);
 }
 
 // grey plane (x255) of an RGB image and, optionally, its bilinear x1/4 copy (align_corners=False on a multiple-of-4
@@ -312,12 +242,7 @@ __global__ __launch_bounds__(256) void down4_gray_kernel(const float* __restrict
     for (int r = 0; r < 4; ++r) px[c][r] = *reinterpret_cast<const float4*>(p + c * cs + (long)r * W);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    float4 g;
-    g.x = ((px[0][r].x * 0.2989f + px[1][r].x * 0.5870f) + px[2][r].x * 0.1140f) * 255.f;
-    g.y = ((px[0][r].y * 0.2989f + px[1][r].y * 0.5870f) + px[2][r].y * 0.1140f) * 255.f;
-    g.z = ((px[0][r].z * 0.2989f + px[1][r].z * 0.5870f) + px[2][r].z * 0.1140f) * 255.f;
-    g.w = ((px[0][r].w * 0.2989f + px[1][r].w * 0.5870f) + px[2][r].w * 0.1140f) * 255.f;
-    *reinterpret_cast<float4*>(gray + (long)b * cs + (long)(4 * y + r) * W + 4 * x) = g;
+    *reinterpret_cast<float4*>(gray + (long)b * cs + (long)(4 * y + r) * W + 4 * x) = gray255(px[0][r], px[1][r], px[2][r]);
   }
   if (small) {
 #pragma unroll
@@ -377,31 +302,36 @@ extern "C" int arflow_down4_gray(const float* im, float* small, float* gray, int
   return arflow_down4_gray_z(im, small, gray, nullptr, B, H, W, stream);
 }
 
-static int census_warp_fwd_impl(const float* gray_a, const float* gray_b, const float* flow, long flow_bstride,
-                                const float* occ_small, float* mask_out, float* dham, float* sums, int B, int H,
-                                int W, int radius, arflow_stream_t stream, int pair) {
-  af_clear_stale_error();
+// what the fused entry points require of their shared arguments (p4, p5: dham and sums / gflow)
+static int census_warp_check(const float* gray_a, const float* gray_b, const float* flow, const float* p4, const float* p5,
+                             long flow_bstride, int B, int H, int W, int radius) {
   AF_REQUIRE_PTR(gray_a);
   AF_REQUIRE_PTR(gray_b);
   AF_REQUIRE_PTR(flow);
-  AF_REQUIRE_PTR(dham);
-  AF_REQUIRE_PTR(sums);
+  AF_REQUIRE_PTR(p4);
+  AF_REQUIRE_PTR(p5);
   AF_REQUIRE(B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 8 * 65535, ARFLOW_ESHAPE);
   AF_REQUIRE(arflow_census_warp_supported(H, W), ARFLOW_ESHAPE);
   AF_REQUIRE(flow_bstride >= 2L * H * W, ARFLOW_ESHAPE);
   AF_REQUIRE(radius >= 1 && radius <= 3, ARFLOW_EPARAM);
+  return ARFLOW_OK;
+}
+
+static int census_warp_fwd_impl(const float* gray_a, const float* gray_b, const float* flow, long flow_bstride,
+                                const float* occ_small, float* mask_out, float* dham, float* sums, int B, int H,
+                                int W, int radius, arflow_stream_t stream, int pair) {
+  af_clear_stale_error();
+  if (const int rc = census_warp_check(gray_a, gray_b, flow, dham, sums, flow_bstride, B, H, W, radius)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int nrows = af_sums_rows(B, H, W);
   if (use_sym() && !pair) return census_sym_fwd(gray_a, gray_b, flow, flow_bstride, occ_small, mask_out, dham, sums, nrows, B, H, W, radius, st);
   namespace cw = census_warp;
   if (use_col())
     return census_col_fwd(gray_a, gray_b, flow, flow_bstride, occ_small, mask_out, dham, sums, nrows, B, H, W, radius, pair, st);
-  dim3 g(af_grid_for_tiles((long)af_cdiv(W, cw::TXW) * af_cdiv(H, cw::TYH) * B));
-  switch (radius) {
-    case 1: hipLaunchKernelGGL(cw::fwd_kernel<1>, g, dim3(cw::NT), 0, st, gray_a, gray_b, flow, flow_bstride, occ_small, mask_out, dham, sums, nrows, B, H, W, pair); break;
-    case 2: hipLaunchKernelGGL(cw::fwd_kernel<2>, g, dim3(cw::NT), 0, st, gray_a, gray_b, flow, flow_bstride, occ_small, mask_out, dham, sums, nrows, B, H, W, pair); break;
-    default: hipLaunchKernelGGL(cw::fwd_kernel<3>, g, dim3(cw::NT), 0, st, gray_a, gray_b, flow, flow_bstride, occ_small, mask_out, dham, sums, nrows, B, H, W, pair); break;
-  }
+  af_dispatch_radius(radius, [&](auto R) {
+    hipLaunchKernelGGL(cw::fwd_kernel<decltype(R)::value>, dim3(cw::grid(B, H, W)), dim3(cw::NT), 0, st, gray_a, gray_b, flow,
+                       flow_bstride, occ_small, mask_out, dham, sums, nrows, B, H, W, pair);
+  });
   return af_launch_status();
 }
 
@@ -425,25 +355,15 @@ static int census_warp_bwd_impl(const float* gray_a, const float* gray_b, const 
                                 const float* dham, const float* scale, float* gflow, int B, int H, int W,
                                 int radius, arflow_stream_t stream, int pair) {
   af_clear_stale_error();
-  AF_REQUIRE_PTR(gray_a);
-  AF_REQUIRE_PTR(gray_b);
-  AF_REQUIRE_PTR(flow);
-  AF_REQUIRE_PTR(dham);
-  AF_REQUIRE_PTR(gflow);
-  AF_REQUIRE(B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 8 * 65535, ARFLOW_ESHAPE);
-  AF_REQUIRE(arflow_census_warp_supported(H, W), ARFLOW_ESHAPE);
-  AF_REQUIRE(flow_bstride >= 2L * H * W, ARFLOW_ESHAPE);
-  AF_REQUIRE(radius >= 1 && radius <= 3, ARFLOW_EPARAM);
+  if (const int rc = census_warp_check(gray_a, gray_b, flow, dham, gflow, flow_bstride, B, H, W, radius)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (use_sym() && !pair) return census_sym_bwd(gray_a, gray_b, flow, flow_bstride, dham, scale, gflow, B, H, W, radius, st);
   namespace cw = census_warp;
   if (use_col(true)) return census_col_bwd(gray_a, gray_b, flow, flow_bstride, dham, scale, gflow, B, H, W, radius, pair, st);
-  dim3 g(af_grid_for_tiles((long)af_cdiv(W, cw::TXW) * af_cdiv(H, cw::TYH) * B));
-  switch (radius) {
-    case 1: hipLaunchKernelGGL(cw::bwd_kernel<1>, g, dim3(cw::NT), 0, st, gray_a, gray_b, flow, flow_bstride, dham, scale, gflow, B, H, W, pair); break;
-    case 2: hipLaunchKernelGGL(cw::bwd_kernel<2>, g, dim3(cw::NT), 0, st, gray_a, gray_b, flow, flow_bstride, dham, scale, gflow, B, H, W, pair); break;
-    default: hipLaunchKernelGGL(cw::bwd_kernel<3>, g, dim3(cw::NT), 0, st, gray_a, gray_b, flow, flow_bstride, dham, scale, gflow, B, H, W, pair); break;
-  }
+  af_dispatch_radius(radius, [&](auto R) {
+    hipLaunchKernelGGL(cw::bwd_kernel<decltype(R)::value>, dim3(cw::grid(B, H, W)), dim3(cw::NT), 0, st, gray_a, gray_b, flow,
+                       flow_bstride, dham, scale, gflow, B, H, W, pair);
+  });
   return af_launch_status();
 }
 
@@ -468,6 +388,7 @@ extern "C" int arflow_uflow_pair_bwd(const float* gray, const float* flow, long 
                                      float flow_scale, float alpha, int order, int wmode, int penalty,
                                      arflow_stream_t stream) {
   af_clear_stale_error();
+  // (its own pointers and shapes first: every null pointer is reported before any shape, every shape before any parameter)
   AF_REQUIRE_PTR(gray);
   AF_REQUIRE_PTR(flow);
   AF_REQUIRE_PTR(dham);
@@ -477,22 +398,19 @@ extern "C" int arflow_uflow_pair_bwd(const float* gray, const float* flow, long 
   AF_REQUIRE_PTR(img2);
   AF_REQUIRE_PTR(coef2);
   AF_REQUIRE_PTR(gflow2);
-  AF_REQUIRE(B2 > 0 && B2 % 2 == 0 && H > 0 && W > 0 && B2 <= 65535 && H <= 8 * 65535 && h2 > 0 && w2 > 0, ARFLOW_ESHAPE);
-  AF_REQUIRE(arflow_census_warp_supported(H, W), ARFLOW_ESHAPE);
-  AF_REQUIRE(flow_bstride >= 2L * H * W && flow2_bstride >= 2L * h2 * w2, ARFLOW_ESHAPE);
-  AF_REQUIRE(radius >= 1 && radius <= 3, ARFLOW_EPARAM);
+  AF_REQUIRE(B2 % 2 == 0 && h2 > 0 && w2 > 0, ARFLOW_ESHAPE);
+  AF_REQUIRE(flow2_bstride >= 2L * h2 * w2, ARFLOW_ESHAPE);
+  if (const int rc = census_warp_check(gray, gray, flow, dham, gflow, flow_bstride, B2, H, W, radius)) return rc;
   AF_REQUIRE((order == 1 || order == 2) && (wmode == 0 || wmode == 1) && (penalty == 0 || penalty == 1), ARFLOW_EPARAM);
   namespace cw = census_warp;
   const SmoothArgs sa{flow2, img2, 3, h2, w2, flow2_bstride, flow_scale, alpha, order, wmode, penalty};
   hipStream_t st = (hipStream_t)stream;
   if (use_col(true)) return census_col_pair_bwd_smooth(gray, flow, flow_bstride, dham, scale2, gflow, B2, H, W, radius, flow2, flow2_bstride, img2, h2, w2,
                                                          flow_scale, alpha, order, wmode, penalty, coef2, gflow2, st);
-  const unsigned cb = af_grid_for_tiles((long)af_cdiv(W, cw::TXW) * af_cdiv(H, cw::TYH) * B2);
-  const unsigned sb = (unsigned)af_cdiv(w2, 256) * (unsigned)h2 * (unsigned)B2;
-  switch (radius) {
-    case 1: hipLaunchKernelGGL(cw::pair_bwd_smooth_kernel<1>, dim3(cb + sb), dim3(cw::NT), 0, st, gray, flow, flow_bstride, dham, scale2, gflow, B2, H, W, cb, sa, coef2, gflow2); break;
-    case 2: hipLaunchKernelGGL(cw::pair_bwd_smooth_kernel<2>, dim3(cb + sb), dim3(cw::NT), 0, st, gray, flow, flow_bstride, dham, scale2, gflow, B2, H, W, cb, sa, coef2, gflow2); break;
-    default: hipLaunchKernelGGL(cw::pair_bwd_smooth_kernel<3>, dim3(cb + sb), dim3(cw::NT), 0, st, gray, flow, flow_bstride, dham, scale2, gflow, B2, H, W, cb, sa, coef2, gflow2); break;
-  }
+  const unsigned cb = cw::grid(B2, H, W);
+  af_dispatch_radius(radius, [&](auto R) {
+    hipLaunchKernelGGL(cw::pair_bwd_smooth_kernel<decltype(R)::value>, dim3(cb + smooth_role_blocks(sa, B2)), dim3(cw::NT), 0, st,
+                       gray, flow, flow_bstride, dham, scale2, gflow, B2, H, W, cb, sa, coef2, gflow2);
+  });
   return af_launch_status();
 }

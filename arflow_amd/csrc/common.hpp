@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/arflow_hip.h"
 
 #define AF_WAVE 64
@@ -46,6 +48,18 @@ int af_deterministic();
 #define AF_REQUIRE_NONDET_OK() AF_REQUIRE(!af_deterministic(), ARFLOW_ENONDET)
 
 static inline int af_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Runs f(std::integral_constant<int, R>) for the census radius R = 1, 2 or 3 (the caller has checked the range), so that a
+// launcher names its kernel template and its argument list once:
+//   af_dispatch_radius(radius, [&](auto R) { hipLaunchKernelGGL(kernel<decltype(R)::value>, ...); });
+template <class F>
+static inline void af_dispatch_radius(int radius, F&& f) {
+  switch (radius) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 3>{}); break;
+  }
+}
 
 // Launch-shape helpers shared by translation units (the level entry points size one accumulator for either producer).
 // Few tiles (coarse pyramid levels): the 4-channel chunks of a tile are spread over up to C/4 workgroups (gridDim.y)

@@ -5,6 +5,7 @@
 //   * TernaryLoss(max_distance > 3) / census_loss(patch_size > 7) losses/loss_blocks.py:12-62, utils/uflow_utils.py:241-293
 //   * SSIM(md != 1)                                              losses/loss_blocks.py:65-84
 //   * Correlation(kernel_size, stride1, stride2, pad_size != d)  models/correlation_package/correlation_cuda_kernel.cu:41-114
+#include "census_dev.hpp"  // the census arithmetic of census_any_*
 #include "common.hpp"
 #include "ssim_dev.hpp"  // SSIM_C1 / SSIM_C2, Win, ssim_terms
 
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(256) void warp_bicubic_bwd_kernel(const float* __re
 __device__ __forceinline__ float gray255_at(const float* __restrict__ im, int H, int W, int y, int x) {
   if (y < 0 || y >= H || x < 0 || x >= W) return 0.f;  // the census transform zero-pads
   const long cs = (long)H * W, o = (long)y * W + x;
-  return ((im[o] * 0.2989f + im[o + cs] * 0.5870f) + im[o + 2 * cs] * 0.1140f) * 255.f;
+  return gray255(im[o], im[o + cs], im[o + 2 * cs]);
 }
 
 // same outputs as census4::fwd_kernel (photo.hip): ham and / or the fused census_loss pieces
@@ -191,20 +192,14 @@ __global__ __launch_bounds__(256) void census_any_fwd_kernel(const float* __rest
     const float ca = gray255_at(pa, H, W, y, x), cb = gray255_at(pb, H, W, y, x);
     float s = 0.f;
     for (int dy = -R; dy <= R; ++dy)
-      for (int dx = -R; dx <= R; ++dx) {
-        const float da = gray255_at(pa, H, W, y + dy, x + dx) - ca, db = gray255_at(pb, H, W, y + dy, x + dx) - cb;
-        const float tb = db * __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-        const float e = fmaf(da, __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f)), -tb), sq = e * e;
-        s = fmaf(sq, __builtin_amdgcn_rcpf(0.1f + sq), s);
-      }
+      for (int dx = -R; dx <= R; ++dx)
+        s = pair_dist_acc(ca, cb, gray255_at(pa, H, W, y + dy, x + dx), gray255_at(pb, H, W, y + dy, x + dx), s);
     const long o = ((long)b * H + y) * W + x;
     if (ham_out) ham_out[o] = s;
     if (mask) {
-      const float pm = (y >= R && y < H - R && x >= R && x < W - R) ? mask[o] : 0.f;
-      const float lg = __log2f(fabsf(s) + 0.01f);
-      part[0] = exp2f(0.4f * lg) * pm;
-      part[1] = pm;
-      if (dham_out) dham_out[o] = pm * 0.4f * exp2f(-0.6f * lg);
+      float dh;
+      ham_loss_terms(s, interior(y, x, H, W, R) ? mask[o] : 0.f, part, dh);
+      if (dham_out) dham_out[o] = dh;
     }
   }
   if (mask) {
@@ -223,27 +218,17 @@ __global__ __launch_bounds__(256) void census_any_bwd_kernel(const float* __rest
   const float* pb = im_b + (long)b * 3 * H * W;
   const float* gg = gham + (long)b * H * W;
   const float ca = gray255_at(pa, H, W, y, x), cb = gray255_at(pb, H, W, y, x), cg = gg[(long)y * W + x];
-  float acc = 0.f;
+  float acc[1] = {0.f};
   for (int dy = -R; dy <= R; ++dy)
     for (int dx = -R; dx <= R; ++dx) {
       if (dy == 0 && dx == 0) continue;
       const int yy = y - dy, xx = x - dx;  // the pixel at r - kk
       const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
       const float wg = in ? gg[(long)yy * W + xx] : 0.f;
-      const float da = ca - gray255_at(pa, H, W, yy, xx), db = cb - gray255_at(pb, H, W, yy, xx);
-      const float ua = __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f));
-      const float ub = __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-      const float e = fmaf(da, ua, -(db * ub));
-      const float q = __builtin_amdgcn_rcpf(fmaf(e, e, 0.1f));
-      const float hd = ((q * e) * q) * ((ub * ub) * ub);
-      acc = fmaf(wg + cg, hd, acc);
+      const float hd = pair_grad(ca, cb, gray255_at(pa, H, W, yy, xx), gray255_at(pb, H, W, yy, xx));
+      acc[0] = fmaf(wg + cg, hd, acc[0]);
     }
-  const float sc = (scale ? scale[0] : 1.f) * 255.f * (0.1f * -2.f * 0.81f);
-  float* o = g_im_b + (long)b * 3 * H * W + (long)y * W + x;
-  const long cs = (long)H * W;
-  o[0] = sc * acc * 0.2989f;
-  o[cs] = sc * acc * 0.5870f;
-  o[2 * cs] = sc * acc * 0.1140f;
+  store_rgb_grad<1>(g_im_b + (long)b * 3 * H * W + (long)y * W + x, (long)H * W, dir_scale(scale, 0, 0) * 255.f, acc);
 }
 
 // ------------------------------------------------------------------------------------------------ SSIM, any window

@@ -10,17 +10,12 @@
 // comparisons run in registers, and the backward pass recomputes them instead of storing anything:
 // HBM traffic is 7 floats in + 1-2 floats out per pixel forward, 8 in + 3 out backward.  These
 // kernels are transcendental-bound (2 rsq + 1 rcp per neighbour), not HBM-bound.
-#include "common.hpp"
 #include "census_tile.hpp"
 
 namespace {
 
 constexpr int TX = 32, TY = 8;  // pixel tile = 256 threads, lanes run along x
-
-__device__ __forceinline__ float gray255(const float* __restrict__ im, long cs, long off) {
-  // ((r*0.2989 + g*0.5870) + b*0.1140) * 255, the reference's operation order
-  return ((im[off] * 0.2989f + im[off + cs] * 0.5870f) + im[off + 2 * cs] * 0.1140f) * 255.f;
-}
+inline unsigned scalar_grid(int B, int H, int W) { return af_grid_for_tiles((long)af_cdiv(W, TX) * af_cdiv(H, TY) * B); }
 
 template <int R>
 __device__ __forceinline__ void load_gray_tile(float (*tile)[TX + 2 * R + 1], const float* __restrict__ im,
@@ -31,7 +26,10 @@ __device__ __forceinline__ void load_gray_tile(float (*tile)[TX + 2 * R + 1], co
     const int r = idx / TC, c = idx - r * TC;
     const int gy = ty0 + r - R, gx = tx0 + c - R;
     float v = 0.f;  // zero padding of the intensities (conv2d padding, uflow_utils.py:257)
-    if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = gray255(im, cs, (long)gy * W + gx);
+    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+      const float* p = im + (long)gy * W + gx;
+      v = gray255(p[0], p[cs], p[2 * cs]);
+    }
     tile[r][c] = v;
   }
 }
@@ -65,25 +63,15 @@ __global__ __launch_bounds__(TX* TY) void census_fwd_kernel(const float* __restr
 #pragma unroll
   for (int dy = 0; dy <= 2 * R; ++dy)
 #pragma unroll
-    for (int dx = 0; dx <= 2 * R; ++dx) {
-      const float da = ga[ly + dy][lx + dx] - ca, db = gb[ly + dy][lx + dx] - cb;
-      const float ta = da * __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f));
-      const float tb = db * __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-      const float e = ta - tb, sq = e * e;
-      s = fmaf(sq, __builtin_amdgcn_rcpf(0.1f + sq), s);
-    }
+    for (int dx = 0; dx <= 2 * R; ++dx) s = pair_dist_acc_exact0(ca, cb, ga[ly + dy][lx + dx], gb[ly + dy][lx + dx], s);
   float part[2] = {0.f, 0.f};
   if (inside) {
     const long o = ((long)b * H + y) * W + x;
     if (ham_out) ham_out[o] = s;
     if (mask) {
-      const bool interior = x >= R && x < W - R && y >= R && y < H - R;
-      const float pm = interior ? mask[o] : 0.f;
-      const float base = fabsf(s) + 0.01f;
-      const float lg = __log2f(base);
-      part[0] = exp2f(0.4f * lg) * pm;  // (|ham|+0.01)^0.4
-      part[1] = pm;
-      if (dham_out) dham_out[o] = pm * 0.4f * exp2f(-0.6f * lg);
+      float dh;
+      ham_loss_terms(s, interior(y, x, H, W, R) ? mask[o] : 0.f, part, dh);
+      if (dham_out) dham_out[o] = dh;
     }
   }
   if (mask) {
@@ -124,28 +112,17 @@ __global__ __launch_bounds__(TX* TY) void census_bwd_kernel(const float* __restr
   const int x = tx0 + lx, y = ty0 + ly;
   if (x >= W || y >= H) return;
   const float ca = ga[ly + R][lx + R], cb = gb[ly + R][lx + R], cg = gg[ly + R][lx + R];
-  float acc = 0.f;
+  float acc[1] = {0.f};
 #pragma unroll
   for (int dy = 0; dy <= 2 * R; ++dy)
 #pragma unroll
     for (int dx = 0; dx <= 2 * R; ++dx) {
       if (dy == R && dx == R) continue;
       // tile index (ly+dy, lx+dx) is pixel r - k with k = (R-dy, R-dx)
-      const float da = ca - ga[ly + dy][lx + dx], db = cb - gb[ly + dy][lx + dx];
-      const float ua = __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f));
-      const float ub = __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-      const float e = da * ua - db * ub, sq = e * e;
-      const float q = __builtin_amdgcn_rcpf(0.1f + sq);
-      // d h/d sq = 0.1 q^2 ; d sq/d tb = -2e ; d tb/d db = 0.81 ub^3
-      const float hd = (0.1f * q * q) * (-2.f * e) * (0.81f * ub * ub * ub);
-      acc = fmaf(gg[ly + dy][lx + dx] + cg, hd, acc);
+      const float hd = pair_grad(ca, cb, ga[ly + dy][lx + dx], gb[ly + dy][lx + dx]);
+      acc[0] = fmaf(gg[ly + dy][lx + dx] + cg, hd, acc[0]);
     }
-  const float sc = (scale ? scale[0] : 1.f) * 255.f * acc;
-  float* o = g_im_b + b * ims + (long)y * W + x;
-  const long cs = (long)H * W;
-  o[0] = sc * 0.2989f;
-  o[cs] = sc * 0.5870f;
-  o[2 * cs] = sc * 0.1140f;
+  store_rgb_grad<1>(g_im_b + b * ims + (long)y * W + x, (long)H * W, dir_scale(scale, 0, 0) * 255.f, acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -198,10 +175,7 @@ __global__ __launch_bounds__(NT) void fwd_kernel(const float* __restrict__ im_a,
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         const int k = p + dx + 4 - R;  // neighbour column x0+p+dx-R  <->  window index (x0+p+dx-R) - (x0-4)
-        const float da = wa[k] - ca[p], db = wb[k] - cb[p];
-        const float tb = db * __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-        const float e = fmaf(da, __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f)), -tb), sq = e * e;
-        s[p] = fmaf(sq, __builtin_amdgcn_rcpf(0.1f + sq), s[p]);
+        s[p] = pair_dist_acc(ca[p], cb[p], wa[k], wb[k], s[p]);
       }
   }
   float part[2] = {0.f, 0.f};
@@ -212,16 +186,8 @@ __global__ __launch_bounds__(NT) void fwd_kernel(const float* __restrict__ im_a,
       const float4 mk = *reinterpret_cast<const float4*>(mask + o);
       const float mv[4] = {mk.x, mk.y, mk.z, mk.w};
       float dh[4];
-      const bool rowin = y >= R && y < H - R;
 #pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int xx = x0 + p;
-        const float pm = (rowin && xx >= R && xx < W - R) ? mv[p] : 0.f;
-        const float lg = __log2f(fabsf(s[p]) + 0.01f);
-        part[0] += exp2f(0.4f * lg) * pm;
-        part[1] += pm;
-        dh[p] = pm * 0.4f * exp2f(-0.6f * lg);
-      }
+      for (int p = 0; p < 4; ++p) ham_loss_terms(s[p], interior(y, x0 + p, H, W, R) ? mv[p] : 0.f, part, dh[p]);
       if (dham_out) *reinterpret_cast<float4*>(dham_out + o) = make_float4(dh[0], dh[1], dh[2], dh[3]);
     }
   }
@@ -244,17 +210,7 @@ __global__ __launch_bounds__(NT) void bwd_kernel(const float* __restrict__ im_a,
   const long ims = 3L * H * W;
   load_gray<R>(ga, im_a + b * ims, H, W, ty0, tx0);
   load_gray<R>(gb, im_b + b * ims, H, W, ty0, tx0);
-  {
-    constexpr int NR = TYH + 2 * R, NQ = (TXW + 8) / 4;
-    const float* g = gham + (long)b * H * W;
-    for (int i = threadIdx.x; i < NR * NQ; i += NT) {
-      const int r = i / NQ, q = i - r * NQ;
-      const int gy = ty0 - R + r, gx = tx0 - 4 + 4 * q;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = *reinterpret_cast<const float4*>(g + (long)gy * W + gx);
-      *reinterpret_cast<float4*>(gg + r * PITCH + 4 * q) = v;
-    }
-  }
+  load_plane<R>(gg, gham + (long)b * H * W, H, W, ty0, tx0);
   __syncthreads();
   const int xg = threadIdx.x & 15, ly = threadIdx.x >> 4;
   const int x0 = tx0 + 4 * xg, y = ty0 + ly;
@@ -280,27 +236,13 @@ __global__ __launch_bounds__(NT) void bwd_kernel(const float* __restrict__ im_a,
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         const int k = p + dx + 4 - R;  // tile pixel r - kk, kk = (R-dy, R-dx)
-        // d ham / d t_b = (0.1 q^2) (-2 e) (0.81 ub^3), q = 1/(0.1 + e^2): the constant -0.162 is applied
-        // once at the store; 17 VALU slots per tap (3 of them transcendental) -- the kernel is VALU-bound
-        const float da = ca[p] - wa[k], db = cb[p] - wb[k];
-        const float ua = __builtin_amdgcn_rsqf(fmaf(da, da, 0.81f));
-        const float ub = __builtin_amdgcn_rsqf(fmaf(db, db, 0.81f));
-        const float e = fmaf(da, ua, -(db * ub));
-        const float q = __builtin_amdgcn_rcpf(fmaf(e, e, 0.1f));
-        const float hd = ((q * e) * q) * ((ub * ub) * ub);
-        acc[p] = fmaf(wg[k] + cg[p], hd, acc[p]);
+        // the constant GRAD_CONST is applied once at the store; 16 VALU slots per tap (3 of them transcendental) -- the
+        // kernel is VALU-bound
+        acc[p] = fmaf(wg[k] + cg[p], pair_grad(ca[p], cb[p], wa[k], wb[k]), acc[p]);
       }
     }
   }
-  const float sc = (scale ? scale[0] : 1.f) * 255.f * (0.1f * -2.f * 0.81f);
-  float* o = g_im_b + b * ims + (long)y * W + x0;
-  const long cs = (long)H * W;
-  *reinterpret_cast<float4*>(o) =
-      make_float4(sc * acc[0] * 0.2989f, sc * acc[1] * 0.2989f, sc * acc[2] * 0.2989f, sc * acc[3] * 0.2989f);
-  *reinterpret_cast<float4*>(o + cs) =
-      make_float4(sc * acc[0] * 0.5870f, sc * acc[1] * 0.5870f, sc * acc[2] * 0.5870f, sc * acc[3] * 0.5870f);
-  *reinterpret_cast<float4*>(o + 2 * cs) =
-      make_float4(sc * acc[0] * 0.1140f, sc * acc[1] * 0.1140f, sc * acc[2] * 0.1140f, sc * acc[3] * 0.1140f);
+  store_rgb_grad<4>(g_im_b + b * ims + (long)y * W + x0, (long)H * W, dir_scale(scale, 0, 0) * 255.f, acc);
 }
 }  // namespace census4
 
@@ -328,21 +270,16 @@ extern "C" int arflow_census_fwd(const float* im_a, const float* im_b, const flo
     return census_any_fwd(im_a, im_b, mask, ham, dham, sums, nrows, B, H, W, radius, st);
   }
   if ((W & 3) == 0) {
-    namespace c4 = census4;
-    dim3 g4(af_grid_for_tiles((long)af_cdiv(W, c4::TXW) * af_cdiv(H, c4::TYH) * B));
-    switch (radius) {
-      case 1: hipLaunchKernelGGL(c4::fwd_kernel<1>, g4, dim3(c4::NT), 0, st, im_a, im_b, mask, ham, dham, sums, nrows, B, H, W); break;
-      case 2: hipLaunchKernelGGL(c4::fwd_kernel<2>, g4, dim3(c4::NT), 0, st, im_a, im_b, mask, ham, dham, sums, nrows, B, H, W); break;
-      default: hipLaunchKernelGGL(c4::fwd_kernel<3>, g4, dim3(c4::NT), 0, st, im_a, im_b, mask, ham, dham, sums, nrows, B, H, W); break;
-    }
+    af_dispatch_radius(radius, [&](auto R) {
+      hipLaunchKernelGGL(census4::fwd_kernel<decltype(R)::value>, dim3(census4::grid(B, H, W)), dim3(census4::NT), 0, st, im_a,
+                         im_b, mask, ham, dham, sums, nrows, B, H, W);
+    });
     return af_launch_status();
   }
-  dim3 grid(af_grid_for_tiles((long)af_cdiv(W, TX) * af_cdiv(H, TY) * B));
-  switch (radius) {
-    case 1: hipLaunchKernelGGL(census_fwd_kernel<1>, grid, dim3(TX * TY), 0, st, im_a, im_b, mask, ham, dham, sums, nrows, B, H, W); break;
-    case 2: hipLaunchKernelGGL(census_fwd_kernel<2>, grid, dim3(TX * TY), 0, st, im_a, im_b, mask, ham, dham, sums, nrows, B, H, W); break;
-    default: hipLaunchKernelGGL(census_fwd_kernel<3>, grid, dim3(TX * TY), 0, st, im_a, im_b, mask, ham, dham, sums, nrows, B, H, W); break;
-  }
+  af_dispatch_radius(radius, [&](auto R) {
+    hipLaunchKernelGGL(census_fwd_kernel<decltype(R)::value>, dim3(scalar_grid(B, H, W)), dim3(TX * TY), 0, st, im_a, im_b, mask,
+                       ham, dham, sums, nrows, B, H, W);
+  });
   return af_launch_status();
 }
 
@@ -361,21 +298,16 @@ extern "C" int arflow_census_bwd(const float* im_a, const float* im_b, const flo
     return census_any_bwd(im_a, im_b, gham, scale, g_im_b, B, H, W, radius, st);
   }
   if ((W & 3) == 0) {
-    namespace c4 = census4;
-    dim3 g4(af_grid_for_tiles((long)af_cdiv(W, c4::TXW) * af_cdiv(H, c4::TYH) * B));
-    switch (radius) {
-      case 1: hipLaunchKernelGGL(c4::bwd_kernel<1>, g4, dim3(c4::NT), 0, st, im_a, im_b, gham, scale, g_im_b, B, H, W); break;
-      case 2: hipLaunchKernelGGL(c4::bwd_kernel<2>, g4, dim3(c4::NT), 0, st, im_a, im_b, gham, scale, g_im_b, B, H, W); break;
-      default: hipLaunchKernelGGL(c4::bwd_kernel<3>, g4, dim3(c4::NT), 0, st, im_a, im_b, gham, scale, g_im_b, B, H, W); break;
-    }
+    af_dispatch_radius(radius, [&](auto R) {
+      hipLaunchKernelGGL(census4::bwd_kernel<decltype(R)::value>, dim3(census4::grid(B, H, W)), dim3(census4::NT), 0, st, im_a,
+                         im_b, gham, scale, g_im_b, B, H, W);
+    });
     return af_launch_status();
   }
-  dim3 grid(af_grid_for_tiles((long)af_cdiv(W, TX) * af_cdiv(H, TY) * B));
-  switch (radius) {
-    case 1: hipLaunchKernelGGL(census_bwd_kernel<1>, grid, dim3(TX * TY), 0, st, im_a, im_b, gham, scale, g_im_b, B, H, W); break;
-    case 2: hipLaunchKernelGGL(census_bwd_kernel<2>, grid, dim3(TX * TY), 0, st, im_a, im_b, gham, scale, g_im_b, B, H, W); break;
-    default: hipLaunchKernelGGL(census_bwd_kernel<3>, grid, dim3(TX * TY), 0, st, im_a, im_b, gham, scale, g_im_b, B, H, W); break;
-  }
+  af_dispatch_radius(radius, [&](auto R) {
+    hipLaunchKernelGGL(census_bwd_kernel<decltype(R)::value>, dim3(scalar_grid(B, H, W)), dim3(TX * TY), 0, st, im_a, im_b, gham,
+                       scale, g_im_b, B, H, W);
+  });
   return af_launch_status();
 }
 

@@ -118,4 +118,17 @@ __device__ __forceinline__ void smooth_bwd_pixel(const SmoothArgs& a, const floa
   go[cs] = g[1];
 }
 
+// The smoothness role of the one-launch UFlowLoss backward (census_warp.hip, census_col.hip): workgroup i of the role's
+// grid (smooth_role_blocks of them, 256 threads each) owns one row of 256 columns of the level-2 flows.
+static inline unsigned smooth_role_blocks(const SmoothArgs& a, int nimg) {
+  return (unsigned)af_cdiv(a.W, 256) * (unsigned)a.H * (unsigned)nimg;
+}
+__device__ __forceinline__ void smooth_bwd_role(const SmoothArgs& sa, const float* __restrict__ coef,
+                                                float* __restrict__ gflow2, int nimg, unsigned i) {
+  const unsigned nxb = (unsigned)((sa.W + 255) / 256);
+  const int xb = (int)(i % nxb), y = (int)((i / nxb) % (unsigned)sa.H), b = (int)(i / (nxb * (unsigned)sa.H));
+  const int x = xb * 256 + (int)threadIdx.x;
+  if (b < nimg && x < sa.W) smooth_bwd_pixel<3>(sa, coef, gflow2, b, y, x);
+}
+
 }  // namespace

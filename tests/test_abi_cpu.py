@@ -73,6 +73,26 @@ def test_argument_errors_without_gpu(lib):
                for n, opt in (('arflow_warp_fwd', (None,)), ('arflow_warp_fwd_bf16', (None,)),
                               ('arflow_warp_bwd', (one, one)), ('arflow_warp_bwd_bf16', (one, one)))}
         assert set(got.values()) == {want}, (change, got)
+    # the five fused census entry points check their common arguments in one place (census_warp_check): the same fault
+    # gets the same code from each of them
+    good = dict(ga=one, fl=one, dh=one, out=one, B=2, H=8, W=8, R=3, fbs=2 * 8 * 8)
+    faults = [(dict(ga=None), -1001), (dict(fl=None), -1001), (dict(dh=None), -1001), (dict(out=None), -1001),  # null pointer
+              (dict(W=10), -1002), (dict(fbs=2 * 8 * 8 - 1), -1002),           # W % 4 != 0, flow_bstride < 2*H*W
+              (dict(R=0), -1003), (dict(R=4), -1003)]                          # radius 1..3
+    smooth = (one, 2 * 2 * 2, one, one, one, 2, 2, 1.0, 10.0, 1, 0, 1, None)   # flow2, its stride, img2, coef2, gflow2, h2, w2, ...
+
+    def fused_calls(a):
+        tail = (a['B'], a['H'], a['W'], a['R'])
+        return {'arflow_census_warp_fwd': (a['ga'], one, a['fl'], a['fbs'], None, None, a['dh'], a['out'], *tail, None),
+                'arflow_census_warp_pair_fwd': (a['ga'], a['fl'], a['fbs'], None, None, a['dh'], a['out'], *tail, None),
+                'arflow_census_warp_bwd': (a['ga'], one, a['fl'], a['fbs'], a['dh'], one, a['out'], *tail, None),
+                'arflow_census_warp_pair_bwd': (a['ga'], a['fl'], a['fbs'], a['dh'], one, a['out'], *tail, None),
+                'arflow_uflow_pair_bwd': (a['ga'], a['fl'], a['fbs'], a['dh'], one, a['out'], *tail, *smooth)}
+    for change, want in faults:
+        got = {n: getattr(lib, n)(*args) for n, args in fused_calls(dict(good, **change)).items()}
+        assert set(got.values()) == {want}, (change, got)
+    got = {n: getattr(lib, n)(*args) for n, args in fused_calls(dict(good, B=3)).items() if 'pair' in n}  # odd B2
+    assert len(got) == 3 and set(got.values()) == {-1002}, got
     assert lib.arflow_census_fwd(one, one, None, one, None, None, 1, 8, 8, 17, None) == -1003  # radius 1..16
     assert lib.arflow_down4(one, one, 1, 6, 8, None) == -1002
     assert b'NULL' in lib.arflow_strerror(-1001)
