@@ -108,6 +108,10 @@ PROTOTYPES = {
     'arflow_triag_inverse_diagonal': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'arflow_band_mv_fwd': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_band_mv_bwd': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_lowrank_sample_fwd': [c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_lowrank_work_size': [c_i, c_i, c_i, c_i],
+    'arflow_lowrank_logdet_fwd': [c_fp, c_l, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_lowrank_bwd': [c_fp, c_l, c_fp, c_fp, c_l, c_fp, c_fp, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_uncert_rows': [c_i, c_i],
     'arflow_uncert_prep': [c_fp, c_fp, c_fp, c_l, c_fp, c_fp, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_sparsify_sums': [c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp],
@@ -140,7 +144,7 @@ def load():
     for name, argtypes in PROTOTYPES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
-        fn.restype = c_l if name.endswith(('_ws_bytes', '_pack_bytes')) else c_i
+        fn.restype = c_l if name.endswith(('_ws_bytes', '_pack_bytes', '_work_size')) else c_i
     lib.arflow_strerror.argtypes = [c_i]
     lib.arflow_strerror.restype = ctypes.c_char_p
     if lib.arflow_abi_version() != ABI_VERSION:

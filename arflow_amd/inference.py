@@ -4,15 +4,19 @@
 inference.py only drives its probabilistic models.
 
     python -m arflow_amd.inference -s 384 640 -i a.png b.png [-m ckpt.pth.tar] [-o flow.flo] [--arch pwclite|pwclite_uflow|uflow|uflow_prob]
-                                [--entropy-out ent.npy]
+                                [--columns R] [--entropy-out ent.npy]
 
 Runs on the GPU through the HIP kernels.  Without -m the network is seeded-random (no checkpoint ships
 with the reference: .MISSING_LARGE_BLOBS), which still exercises the whole path.  --arch uflow_prob is PWCProbFlow with
 out_channels [2, 2, 0]; --entropy-out writes its full-resolution log-diagonal channels flows_fw[0][:, 2:4] as [H,W,2] -- what
 the reference's ELBO trainer evaluates as the per-component entropy for `diag`, and for `sparse` without inv_cov
-(trainer/uflow_elbo_trainer.py:175,191), and what `python -m arflow_amd.evaluate --entropy` reads.
+(trainer/uflow_elbo_trainer.py:175,191), and what `python -m arflow_amd.evaluate --entropy` reads.  With --columns R the model
+is the low-rank family's (out_channels [2, 0, 2R], configs/chairs_uflow_elbo_lowrank.json) and --entropy-out writes the map
+the reference's inference and validation compute for it (inference.py:76-84, trainer/uflow_elbo_trainer.py:193-197):
+upsample(log(sum_k std_k^2) / 2 + 2 log 4, x4, align_corners=False) of the level-2 columns, in plain torch.
 """
 import argparse
+import math
 
 import numpy as np
 import torch
@@ -30,7 +34,7 @@ def load_image(path, size):
     return torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0).permute(2, 0, 1)
 
 
-def build_model(kind, n_frames, ckpt=None, seed=0):
+def build_model(kind, n_frames, ckpt=None, seed=0, columns=0):
     if kind == 'pwclite':
         cfg = AttrDict(type='pwclite', upsample=True, n_frames=n_frames, reduce_dense=True)
     elif kind == 'pwclite_uflow':
@@ -39,8 +43,9 @@ def build_model(kind, n_frames, ckpt=None, seed=0):
     elif kind == 'uflow':
         cfg = AttrDict(type='uflow', level_dropout=0.0, feature_norm=True)
     elif kind == 'uflow_prob':
-        cfg = AttrDict(type='uflow_prob', level_dropout=0.0, feature_norm=True, out_channels=[2, 2, 0], inv_cov=False,
-                       n_pyramids=1, mixture_weights=False)
+        cfg = AttrDict(type='uflow_prob', level_dropout=0.0, feature_norm=True,
+                       out_channels=[2, 0, 2 * columns] if columns else [2, 2, 0], inv_cov=False, n_pyramids=1,
+                       mixture_weights=False)
     else:
         raise NotImplementedError(kind)
     model = get_model(cfg)
@@ -58,7 +63,8 @@ def build_model(kind, n_frames, ckpt=None, seed=0):
 @torch.no_grad()
 def infer(model, frames, device, want_entropy=False):
     """frames: list of [3,H,W] tensors in [0,1] -> forward flow of the (middle) reference frame, [H,W,2]; with want_entropy
-    (PWCProbFlow only) also its log-diagonal channels, [H,W,2]."""
+    (PWCProbFlow only) also its log-diagonal channels -- for the low-rank family (no log-diagonal channels) the entropy map of
+    lowrank_entropy_map --, [H,W,2]."""
     x = torch.cat(frames, 0).unsqueeze(0).to(device)
     prob = hasattr(model, 'upsample_out')
     if want_entropy and not prob:
@@ -71,8 +77,18 @@ def infer(model, frames, device, want_entropy=False):
         res = model(x, with_bk=False) if len(frames) == 2 else model(x)
     out = res['flows_fw'][0][0].permute(1, 2, 0).float().cpu().numpy()
     if want_entropy:
+        if model._out_channels[1] == 0:
+            ent = lowrank_entropy_map(res['flows_fw'][2][:, 2:])
+            return out[..., 0:2], ent[0].permute(1, 2, 0).float().cpu().numpy()
         return out[..., 0:2], out[..., 2:4]
     return out[..., 0:2]
+
+
+def lowrank_entropy_map(std):
+    """std [B,2R,h,w], the level-2 columns (channel 2k + c: column k of flow component c) -> [B,2,4h,4w]: the marginal
+    log standard deviation log(sum_k std_k^2) / 2 per component, brought to full resolution (inference.py:76-84)."""
+    ent = torch.log(torch.stack((std[:, 0::2].square().sum(1), std[:, 1::2].square().sum(1)), 1)) / 2
+    return torch.nn.functional.interpolate(ent + 2 * math.log(4), scale_factor=4, mode='bilinear', align_corners=False)
 
 
 def main():
@@ -82,13 +98,16 @@ def main():
     ap.add_argument('-i', '--img_list', nargs='+', required=True)
     ap.add_argument('-o', '--output', default=None, help='write the flow as .flo')
     ap.add_argument('--arch', default='pwclite', choices=['pwclite', 'pwclite_uflow', 'uflow', 'uflow_prob'])
+    ap.add_argument('--columns', default=0, type=int, help='uflow_prob: the low-rank family with this many columns (1..16)')
     ap.add_argument('--entropy-out', default=None, help='write the log-diagonal channels as .npy [H,W,2] (uflow_prob)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('arflow_amd.inference needs a GPU: the correlation / warp kernels have no CPU fallback')
     device = torch.device('cuda')
     frames = [load_image(p, args.test_shape) for p in args.img_list]
-    model = build_model(args.arch, len(frames), args.model).to(device)
+    if args.columns and (args.arch != 'uflow_prob' or not 1 <= args.columns <= 16):
+        raise SystemExit('--columns takes 1..16 and needs --arch uflow_prob')
+    model = build_model(args.arch, len(frames), args.model, columns=args.columns).to(device)
     if args.entropy_out:
         flow, ent = infer(model, frames, device, want_entropy=True)
         np.save(args.entropy_out, np.ascontiguousarray(ent))

@@ -11,14 +11,16 @@ sampled flows, and its sampled charbonnier smoothness is edge_asymp s(0) + (1 - 
 UFlowLoss's first-order smoothness at edge constant alpha.
 
 Supported: approx 'diag' (inv_cov, approx_entropy, closed_form_smooth with order_smooth 1 / 2 and isotropic_smooth) and
-'sparse' (inv_cov false, cov_supp 1..3, offdiag_reg); any n_samples; with_bk; w_oof, w_occ.  Everything else raises
-NotImplementedError naming the value.  A missing `isotropic_smooth` / `order_smooth` reads as False / 1 (the reference
+'sparse' (inv_cov false, cov_supp 1..3, offdiag_reg) and 'lowrank' (inv_cov false, columns 1..16: the sampler and the Gram
+log-determinants of csrc/lowrank.hip; approx_entropy is not consulted, as in the reference); any
+n_samples; with_bk; w_oof, w_occ.  Everything else raises NotImplementedError naming the value.  A missing `isotropic_smooth` / `order_smooth` reads as False / 1 (the reference
 raises AttributeError on its own chairs_uflow_elbo_nondiag.json, which omits them).
 """
 import torch
 import torch.nn as nn
 
 from .. import functional as AF
+from ..lowrank import RMAX, reparam_lowrank_pair
 from ..triag_solve import reparam_triag_pair
 from ..uflow_utils import census_loss, flow_to_warp, image_grads
 
@@ -54,8 +56,17 @@ class UFlowElboLoss(nn.Module):
         self.cfg = cfg
         self.fused = True  # False: the unfused photometric path (warp, mask upsample and census as separate launches)
         self.pair = True   # False: the two directions one after the other (the reference's order)
-        if cfg.approx not in ('diag', 'sparse'):
-            raise NotImplementedError("approx: %r (supported: 'diag', 'sparse')" % (cfg.approx,))
+        if cfg.approx not in ('diag', 'sparse', 'lowrank'):
+            raise NotImplementedError("approx: %r (supported: 'diag', 'sparse', 'lowrank')" % (cfg.approx,))
+        if cfg.approx == 'lowrank':
+            columns = getattr(cfg, 'columns', None)
+            if columns is None:
+                raise NotImplementedError("approx: 'lowrank' needs `columns` (1..%d), the number of columns per flow "
+                                          "component" % RMAX)
+            if int(columns) != columns or not 1 <= int(columns) <= RMAX:
+                raise NotImplementedError('columns: %r (supported: 1..%d)' % (columns, RMAX))
+            if cfg.inv_cov:
+                raise NotImplementedError("inv_cov: True with approx: 'lowrank'")
         if cfg.occ_type != 'sample':
             raise NotImplementedError("occ_type: %r (supported: 'sample')" % (cfg.occ_type,))
         if list(cfg.data_loss) != ['census']:
@@ -77,8 +88,14 @@ class UFlowElboLoss(nn.Module):
 
     # ---- the pieces -------------------------------------------------------------------------------------------
     def _split(self, net):
-        """Level-2 output [B,C,h,w] -> mean, log_diag, diag = exp(+-log_diag), offdiag (None for 'diag') as channel slices."""
+        """Level-2 output [B,C,h,w] -> mean, log_diag, diag = exp(+-log_diag), offdiag (None for 'diag') as channel slices;
+        'lowrank': mean, None, None, std [B,2 columns,h,w]."""
         cfg = self.cfg
+        if cfg.approx == 'lowrank':
+            R = int(cfg.columns)
+            if net.shape[1] != 2 + 2 * R:
+                raise ValueError('approx lowrank with columns %d needs %d level-2 channels (got %d)' % (R, 2 + 2 * R, net.shape[1]))
+            return net[:, 0:2], None, None, net[:, 2:2 + 2 * R]
         mean, log_diag = net[:, 0:2], net[:, 2:4]
         off = None
         if cfg.approx == 'sparse':
@@ -151,9 +168,9 @@ class UFlowElboLoss(nn.Module):
 
     # ---- forward ----------------------------------------------------------------------------------------------
     def forward(self, res_dict, im1_0, im2_0, eps=None):
-        """res_dict['flows_fw'][2], ['flows_bw'][2]: the level-2 outputs [B,C,h,w] (mean, log_diag, off-diagonals);
-        im1_0, im2_0 [B,3,4h,4w]; eps: (eps12, eps21), each [S B,2,h,w], drawn on the device (forward direction first) when
-        None.  -> (total, loss_warp, loss_smooth, loss_entropy, loss_oof, flow12_2, occu_mask12, valid_mask12)."""
+        """res_dict['flows_fw'][2], ['flows_bw'][2]: the level-2 outputs [B,C,h,w] (mean, log_diag, off-diagonals; 'lowrank':
+        mean, columns); im1_0, im2_0 [B,3,4h,4w]; eps: (eps12, eps21), each [S B,2,h,w] ('lowrank': [S B,2 columns,1,1]), drawn
+        on the device (forward direction first) when None.  -> (total, loss_warp, loss_smooth, loss_entropy, loss_oof, flow12_2, occu_mask12, valid_mask12)."""
         cfg = self.cfg
         if cfg.natural_grad:
             raise NotImplementedError("Natural gradient is not implemented!")
@@ -170,17 +187,26 @@ class UFlowElboLoss(nn.Module):
         mean21, log_diag21, diag21, off21 = self._split(net21)
 
         # reparameterisation: both directions into one (fw, bw) tensor
+        lowrank = cfg.approx == 'lowrank'
         if eps is None:
-            eps12 = torch.randn(S * B, 2, h, w, device=net12.device, dtype=net12.dtype)
-            eps21 = torch.randn(S * B, 2, h, w, device=net12.device, dtype=net12.dtype)
+            shape = (S * B, off12.shape[1], 1, 1) if lowrank else (S * B, 2, h, w)
+            eps12 = torch.randn(shape, device=net12.device, dtype=net12.dtype)
+            eps21 = torch.randn(shape, device=net12.device, dtype=net12.dtype)
         else:
             eps12, eps21 = eps
-        flows2 = reparam_triag_pair((mean12, diag12, off12, eps12), (mean21, diag21, off21, eps21), k, S)  # [S B,4,h,w]
+        if lowrank:  # off12, off21: the columns
+            flows2, logdet = reparam_lowrank_pair((mean12, off12, eps12), (mean21, off21, eps21), S)  # [S B,4,h,w], [2,B,2]
+        else:
+            flows2 = reparam_triag_pair((mean12, diag12, off12, eps12), (mean21, diag21, off21, eps21), k, S)  # [S B,4,h,w]
         flow12_2, flow21_2 = flows2[:, 0:2], flows2[:, 2:4]
 
         # entropy
         sign = -1.0 if cfg.inv_cov else 1.0
-        if cfg.approx == 'diag' and not cfg.inv_cov and cfg.approx_entropy:
+        if lowrank:  # :362-381: (logdet G_u + logdet G_v) / (2 h w), mean over the batch, per direction
+            loss_entropy = cfg.w_entropy * (logdet[0].sum(1) / (2 * h * w)).mean()
+            if with_bk:
+                loss_entropy = loss_entropy + cfg.w_entropy * (logdet[1].sum(1) / (2 * h * w)).mean()
+        elif cfg.approx == 'diag' and not cfg.inv_cov and cfg.approx_entropy:
             t12 = (flow12_2 - mean12.detach().repeat(S, 1, 1, 1)) / diag12.detach().repeat(S, 1, 1, 1)
             loss_entropy = cfg.w_entropy * torch.sum(t12 * t12 / 2, dim=1).mean()
             if with_bk:

@@ -2,7 +2,9 @@
 This is what configs/chairs_uflow_elbo*.json instantiate (``"model": {"type": "uflow_prob"}``): PWCFlow with wider heads.
 Every level carries out_channels = [L, M, N] channels -- L = 2 flow channels (used for warping), M log-diagonal channels of
 the covariance / precision factor, N further channels (the off-diagonal band) that only the output level produces -- and
-brings them to the next level with upsample_out (:223-250): AF.out_upsample / AF.out_tail."""
+brings them to the next level with upsample_out (:223-250): AF.out_upsample / AF.out_tail.
+M = 0 is the low-rank family (out_channels [2, 0, 2 columns]): the pyramid then carries the flow pair
+alone, and no zero-channel tensor is built or handed to a kernel."""
 import math
 
 import torch
@@ -93,8 +95,9 @@ class PWCProbFlow(nn.Module):
             if level == top:
                 # :263-273: zero context_up, zero flow, and log_diag planes chosen so that the diag_bias of the upsamples
                 # down to the output level leaves ~0 there.  The warp by the zero flow is the identity and is not run.
-                start = torch.cat([features1.new_zeros(B, self._num_context_up_channels + n0, H, W),
-                                   features1.new_full((B, n1, H, W), -(self._num_levels - 3) * self._diag_bias)], 1)
+                start = features1.new_zeros(B, self._num_context_up_channels + n0, H, W)
+                if n1 > 0:
+                    start = torch.cat([start, features1.new_full((B, n1, H, W), -(self._num_levels - 3) * self._diag_bias)], 1)
                 out_up = start[:, self._num_context_up_channels:]
                 if norm and AF.level_supported(features1, None, True):
                     r2 = moments[1][level] if moments is not None else None
@@ -107,13 +110,18 @@ class PWCProbFlow(nn.Module):
             elif norm and AF.level_supported(features1, out[:, 0:2], True):
                 # the fused level upsamples and warps with the flow pair itself ('flow' slot); the other channels of
                 # out_up come from the output-upsample kernel and travel as a member
-                if self._native_up(out):
-                    rest_up = AF.out_upsample(out[:, n0:], 0, n1, self._diag_bias)
+                if n1 == 0:  # the flow pair is all that comes up the pyramid: no rest member
+                    cfg = AF.LevelCfg([0, 'flow', 'vol', 1], 'avg', alpha, 4, True, False, 'zeros', True, AF.NORM_UFLOW)
+                    x_in, out_up = AF.level(features1, features2, out[:, 0:2], cfg, context_up, features1, x1_rows=r1)
                 else:
-                    rest_up = uflow_utils.upsample(out[:, n0:] + self._diag_bias, is_flow=False)
-                cfg = AF.LevelCfg([0, 'flow', 1, 'vol', 2], 'avg', alpha, 4, True, False, 'zeros', True, AF.NORM_UFLOW)
-                x_in, flow_up = AF.level(features1, features2, out[:, 0:2], cfg, context_up, rest_up, features1, x1_rows=r1)
-                out_up = torch.cat([flow_up, rest_up], 1)
+                    if self._native_up(out):
+                        rest_up = AF.out_upsample(out[:, n0:], 0, n1, self._diag_bias)
+                    else:
+                        rest_up = uflow_utils.upsample(out[:, n0:] + self._diag_bias, is_flow=False)
+                    cfg = AF.LevelCfg([0, 'flow', 1, 'vol', 2], 'avg', alpha, 4, True, False, 'zeros', True, AF.NORM_UFLOW)
+                    x_in, flow_up = AF.level(features1, features2, out[:, 0:2], cfg, context_up, rest_up, features1,
+                                             x1_rows=r1)
+                    out_up = torch.cat([flow_up, rest_up], 1)
             else:
                 out_up = self.upsample_out(out)
                 warped2 = mum.uflow_utils.resample_flow(features2, out_up[:, 0:2])  # :282
@@ -133,9 +141,12 @@ class PWCProbFlow(nn.Module):
             refinement = refinement * drops[k]
         refined = out + refinement
         # :375-381: log(precision) / 2 not too small, log(variance) / 2 neither too small nor too large
-        log_diag = refined[:, n0:n01]
-        log_diag = torch.clamp(log_diag, min=-5.0) if self._inv_cov else torch.clamp(log_diag, max=10.0, min=-10.0)
-        outs[0] = torch.cat([refined[:, 0:n0], log_diag, refined[:, n01:]], dim=1)
+        if n1 > 0:
+            log_diag = refined[:, n0:n01]
+            log_diag = torch.clamp(log_diag, min=-5.0) if self._inv_cov else torch.clamp(log_diag, max=10.0, min=-10.0)
+            outs[0] = torch.cat([refined[:, 0:n0], log_diag, refined[:, n01:]], dim=1)
+        else:  # the clamp acts on an empty slice
+            outs[0] = refined
         if self._native_up(outs[0]):
             out_1, out_0 = AF.out_tail(outs[0], n0, n1, self._diag_bias)
         else:

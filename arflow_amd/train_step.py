@@ -40,6 +40,14 @@ WORKLOADS = {
              closed_form_smooth=False, data_loss=['census'], data_weight=[1.0], data_penalty=['abs_robust_loss'],
              w_entropy=0.1, w_oof=0.0, w_occ=0.0, with_bk=True, approx='sparse', n_components=1, cov_supp=3, inv_cov=False,
              approx_entropy=False, occ_type='sample', n_samples=4, offdiag_reg=0.0, natural_grad=False)),
+    # configs/chairs_uflow_elbo_lowrank.json:7-39 (PWCProbFlow without log-diagonal channels, 15 columns per flow component)
+    'pwcprobflow+uflow_elbo_lowrank': (
+        dict(type='uflow_prob', feature_norm=True, level_dropout=0.0, out_channels=[2, 0, 30], inv_cov=False, n_pyramids=1,
+             mixture_weights=False),
+        dict(type='uflow_elbo', edge_constant=150, edge_asymp=0.01, w_smooth=4.0, penalty_smooth='charbonnier',
+             closed_form_smooth=False, data_loss=['census'], data_weight=[1.0], data_penalty=['abs_robust_loss'],
+             w_entropy=0.1, w_oof=0.0, w_occ=0.0, with_bk=True, approx='lowrank', columns=15, n_components=1, inv_cov=False,
+             approx_entropy=False, occ_type='sample', n_samples=4, offdiag_reg=0.0, natural_grad=False)),
 }
 
 

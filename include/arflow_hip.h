@@ -607,6 +607,33 @@ int arflow_band_mv_bwd(const float* diag, long diag_bs, const float* off, long o
                        long gdiag_bs, float* goff, long goff_bs, int B, int S, int M, int N, int k, int transpose,
                        arflow_stream_t stream);
 
+/* ---- the low-rank covariance family: fused sampler, Gram log-determinant, one backward (csrc/lowrank.hip) ------
+ * reparam_lowrank and the entropy of approx 'lowrank' of losses/uflow_elbo_loss.py:180-188, :362-381.
+ * std [B][2R][M][N]: channel 2k + c is column k of flow component c in {0, 1}; 1 <= R <= 16; p = y N + x.  Sample s of batch
+ * item b is plane s B + b of Z, gZ and row s B + b of eps [S B][2R] (contiguous).  Every tensor is fp32 with contiguous planes
+ * and its OWN batch stride in floats (read only when there is a second item), so channel slices are passed in place.
+ *   arflow_lowrank_sample_fwd:  Z[sB+b,c,p] = mean[b,c,p] + sum_k std[b,2k+c,p] eps[sB+b,2k+c]; the products are rounded and
+ *     added in k order onto the mean.  std is read once for all S samples.
+ *   arflow_lowrank_logdet_fwd:  G[b,c] = U U^T with U = std[b, c::2] as [R][M N], accumulated in float64 (exact products);
+ *     logdet [B][2] = log det G and ginv [B][2][R][R] = G^-1, from a float64 Cholesky factorisation, rounded once to fp32.
+ *     work: arflow_lowrank_work_size(B, R, M, N) doubles (< 0: the ARFLOW_E* code), need not be initialised.  Two launches;
+ *     a pivot that is not positive gives NaN for that (b, c)'s logdet and ginv (no host synchronisation).
+ *   arflow_lowrank_bwd, one launch:  gmean[b,c,p] = sum_s gZ[sB+b,c,p] (NULL: not wanted);
+ *     gstd[b,2i+c,p] = sum_s eps[sB+b,2i+c] gZ[sB+b,c,p] + 2 glogdet[b,c] sum_j ginv[b,c,i,j] std[b,2j+c,p].  gZ may be NULL
+ *     (no sampler term; eps is then not read) and glogdet [B][2] (a DEVICE pointer) may be NULL (no log-det term; ginv is
+ *     then not read).
+ * No atomics: the same bits in either mode.  Every element of every output is stored.
+ * ARFLOW_ENULL: a required pointer is NULL; ARFLOW_EPARAM: R outside 1..16; ARFLOW_ESHAPE: B, S, M or N < 1, a batch stride
+ * smaller than its item, M N >= 2^31, B > 32767.  Outputs must not overlap inputs. */
+int arflow_lowrank_sample_fwd(const float* mean, long mean_bs, const float* std, long std_bs, const float* eps, float* Z,
+                              long z_bs, int B, int S, int R, int M, int N, arflow_stream_t stream);
+long arflow_lowrank_work_size(int B, int R, int M, int N);
+int arflow_lowrank_logdet_fwd(const float* std, long std_bs, double* work, float* logdet, float* ginv, int B, int R, int M,
+                              int N, arflow_stream_t stream);
+int arflow_lowrank_bwd(const float* std, long std_bs, const float* eps, const float* gZ, long gz_bs, const float* ginv,
+                       const float* glogdet, float* gmean, long gmean_bs, float* gstd, long gstd_bs, int B, int S, int R,
+                       int M, int N, arflow_stream_t stream);
+
 /* ---- uncertainty metrics: sparsification curves and the calibration histogram -----------------------------------
  * The device side of evaluate_uncertainty / sp_plot / CalibrationCurve of utils/flow_utils.py:186-320 (DESIGN.md section
  * 19).  The `rows` conventions of arflow_flow_eval hold for all three: a row buffer need not be initialised, every row is

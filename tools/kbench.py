@@ -163,6 +163,93 @@ def band_bench(dev, g, B=8, S=4, M=96, N=160, launches=30, repeats=5):
         B, S, H, W, k, med, lo, hi, sum(len(v) for v in calls.values()), sorted({n for n, _ in calls})), flush=True)
 
 
+def lowrank_bench(dev, g, S=4, R=15, launches=30, repeats=5):
+    """the low-rank node (sampler + Gram log-determinants, one backward launch) at B = 8 on the 96 x 160
+    level and at B = 4 on 64 x 112, next to the reference's formulation restated in torch ops (repeat std S-fold, mul, two
+    strided channel sums, cat; two bmm and torch.logdet; ATen's autograd of all that).  Protocol of band_bench: 100 untimed
+    calls, the functions timed in alternation, `repeats` rounds, median (min .. max); the raw launches through the C ABI next
+    to them, with algorithmic bytes."""
+    import statistics
+    from arflow_amd import lowrank as LR
+
+    def torch_formulation(mean, std, eps):  # losses/uflow_elbo_loss.py:180-188, :362-370
+        B, C, h, w = std.shape
+        e = std.repeat(S, 1, 1, 1) * eps
+        z = mean.repeat(S, 1, 1, 1) + torch.cat((e[:, 0::2].sum(1, keepdim=True), e[:, 1::2].sum(1, keepdim=True)), 1)
+        u, v = std[:, 0::2].reshape(B, C // 2, h * w), std[:, 1::2].reshape(B, C // 2, h * w)
+        ld = torch.stack((torch.logdet(torch.matmul(u, u.transpose(1, 2))), torch.logdet(torch.matmul(v, v.transpose(1, 2)))), 1)
+        return z, ld
+
+    def spread(fns, shape, settle=100):
+        for fn in fns.values():
+            for _ in range(settle):
+                fn()
+        torch.cuda.synchronize()
+        t = {name: [] for name in fns}
+        for _ in range(repeats):
+            for name, fn in fns.items():
+                t[name].append(timeit(fn, launches))
+                MANIFEST[-1].update(name='lowrank/' + name, shape=shape)
+        return {name: (statistics.median(v), min(v), max(v)) for name, v in t.items()}
+
+    for B, M, N in ((8, 96, 160), (4, 64, 112)):
+        net = torch.cat((1.5 * torch.randn(B, 2, M, N, device=dev, generator=g),
+                         0.1 * torch.randn(B, 2 * R, M, N, device=dev, generator=g)), 1).requires_grad_(True)
+        eps = torch.randn(S * B, 2 * R, 1, 1, device=dev, generator=g)
+        w = torch.randn(S * B, 2, M, N, device=dev, generator=g)
+        wl = torch.randn(B, 2, device=dev, generator=g)
+
+        def fused(grad):
+            z, ld = LR._LowRank.apply(S, 1, True, True, net[:, 0:2], net[:, 2:], eps)
+            if grad:
+                torch.autograd.grad((z, ld[0]), net, (w, wl))
+
+        def plain(grad):
+            z, ld = torch_formulation(net[:, 0:2], net[:, 2:], eps)
+            if grad:
+                torch.autograd.grad((z, ld), net, (w, wl))
+
+        def no_grad(fn):
+            def run():
+                with torch.no_grad():
+                    fn(False)
+            return run
+
+        lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+        d = net.detach()
+        nb, pl = d.stride(0), M * N
+        z = torch.empty(S * B, 2, M, N, device=dev)
+        work = torch.empty(lib.arflow_lowrank_work_size(B, R, M, N), device=dev, dtype=torch.float64)
+        ld, ginv = torch.empty(B, 2, device=dev), torch.empty(B, 2, R, R, device=dev)
+        gnet = torch.empty_like(d)
+        mean_p, std_p = p(d), p(d[:, 2:])
+
+        def launch_fwd():
+            lib.arflow_lowrank_sample_fwd(mean_p, nb, std_p, nb, p(eps), p(z), 2 * pl, B, S, R, M, N, st)
+
+        def launch_logdet():
+            lib.arflow_lowrank_logdet_fwd(std_p, nb, p(work), p(ld), p(ginv), B, R, M, N, st)
+
+        def launch_bwd():
+            lib.arflow_lowrank_bwd(std_p, nb, p(eps), p(w), 2 * pl, p(ginv), p(wl), p(gnet), nb, p(gnet[:, 2:]), nb, B, S, R, M, N, st)
+
+        res = spread({'launch fwd': launch_fwd, 'launch logdet': launch_logdet, 'launch bwd': launch_bwd,
+                      'fused fwd': no_grad(fused), 'torch fwd': no_grad(plain), 'fused fwd+bwd': lambda: fused(True),
+                      'torch fwd+bwd': lambda: plain(True)}, [B, S, R, M, N])
+        # algorithmic bytes: forward std + mean + eps + z; log-det std; backward std + gZ in, gstd + gmean out
+        std_b, mean_b, z_b = 4 * B * 2 * R * pl, 4 * B * 2 * pl, 4 * S * B * 2 * pl
+        nbytes = {'launch fwd': std_b + mean_b + 4 * eps.numel() + z_b, 'launch logdet': std_b,
+                  'launch bwd': std_b + z_b + std_b + mean_b}
+        tag = 'lowrank B=%d S=%d R=%d %dx%d' % (B, S, R, M, N)
+        for name, (med, lo, hi) in res.items():
+            gbs = '%8.1f GB/s algorithmic' % (nbytes[name] / med / 1e3) if name in nbytes else ''
+            print('%s %-14s %9.1f us  (min %.1f .. max %.1f)  %s' % (tag, name, med, lo, hi, gbs), flush=True)
+        for what in ('fwd', 'fwd+bwd'):
+            f, t = res['fused ' + what], res['torch ' + what]
+            print('%s %s: fused is %.2fx the torch formulation; ranges %s' % (tag, what, t[0] / f[0],
+                                                                             'apart' if f[2] < t[1] else 'OVERLAP'), flush=True)
+
+
 def out_up_bench(dev, g, B2=8, launches=30, repeats=5):
     """the output upsample of PWCProbFlow -- AF.out_upsample / AF.out_tail (one launch each way) next to
     the composed ATen path the model runs with ARFLOW_OUT_UP=0 (split, bias add, F.interpolate per group, x2, cat, and
@@ -574,6 +661,8 @@ def main():
                     p(A), p(Bc), p(Cc), p(Dc), p(Y), p(X), p(gX), p(gA), p(gB), p(gC), p(gD), P, M, N, 0, s), args.iters), 11 * P * M * N)
             trec('arflow_triag_inverse_diagonal', timeit(lambda: lib.arflow_triag_inverse_diagonal(
                 p(A), p(Bc), p(Cc), p(gA), P, M, N, s), max(3, args.iters // 10)), 4 * P * M * N)
+    if want('lowrank'):  # the low-rank sampler and Gram log-determinant (csrc/lowrank.hip) against the torch formulation
+        lowrank_bench(dev, g)
     if want('band'):  # the fused sparse-covariance sampler (csrc/band.hip) against the reference's formulation in torch ops
         band_bench(dev, g)
     if want('out_up'):  # the probabilistic model's output upsample (csrc/out_up.hip) against the composed ATen path
