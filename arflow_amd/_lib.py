@@ -112,6 +112,11 @@ PROTOTYPES = {
     'arflow_lowrank_work_size': [c_i, c_i, c_i, c_i],
     'arflow_lowrank_logdet_fwd': [c_fp, c_l, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
     'arflow_lowrank_bwd': [c_fp, c_l, c_fp, c_fp, c_l, c_fp, c_fp, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_mixture_work_size': [c_i, c_i, c_i, c_i, c_i],
+    'arflow_mixture_sample_fwd': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_mixture_logpdf_fwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_mixture_bwd': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_mixture_entropy_map': [c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_uncert_rows': [c_i, c_i],
     'arflow_uncert_prep': [c_fp, c_fp, c_fp, c_l, c_fp, c_fp, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_sparsify_sums': [c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp],

@@ -13,7 +13,10 @@ UFlowLoss's first-order smoothness at edge constant alpha.
 Supported: approx 'diag' (inv_cov, approx_entropy, closed_form_smooth with order_smooth 1 / 2 and isotropic_smooth) and
 'sparse' (inv_cov false, cov_supp 1..3, offdiag_reg) and 'lowrank' (inv_cov false, columns 1..16: the sampler and the Gram
 log-determinants of csrc/lowrank.hip; approx_entropy is not consulted, as in the reference); any
-n_samples; with_bk; w_oof, w_occ.  Everything else raises NotImplementedError naming the value.  A missing `isotropic_smooth` / `order_smooth` reads as False / 1 (the reference
+n_samples; with_bk; w_oof, w_occ; and 'mixture' (inv_cov false, n_components 2..4: the sampler, the mixture log-density and
+their one backward launch of csrc/mixture.hip; level-2 outputs of 4 n_components channels = the
+components' means, then their log-stds; weights from res_dict['weights_fw'] / ['weights_bw'] or uniform; approx_entropy is not
+consulted, as in the reference).  Everything else raises NotImplementedError naming the value.  A missing `isotropic_smooth` / `order_smooth` reads as False / 1 (the reference
 raises AttributeError on its own chairs_uflow_elbo_nondiag.json, which omits them).
 """
 import torch
@@ -21,6 +24,7 @@ import torch.nn as nn
 
 from .. import functional as AF
 from ..lowrank import RMAX, reparam_lowrank_pair
+from ..mixture import KMAX, reparam_gmm_pair
 from ..triag_solve import reparam_triag_pair
 from ..uflow_utils import census_loss, flow_to_warp, image_grads
 
@@ -56,8 +60,13 @@ class UFlowElboLoss(nn.Module):
         self.cfg = cfg
         self.fused = True  # False: the unfused photometric path (warp, mask upsample and census as separate launches)
         self.pair = True   # False: the two directions one after the other (the reference's order)
-        if cfg.approx not in ('diag', 'sparse', 'lowrank'):
-            raise NotImplementedError("approx: %r (supported: 'diag', 'sparse', 'lowrank')" % (cfg.approx,))
+        if cfg.approx not in ('diag', 'sparse', 'lowrank', 'mixture'):
+            raise NotImplementedError("approx: %r (supported: 'diag', 'sparse', 'lowrank', 'mixture')" % (cfg.approx,))
+        if cfg.approx == 'mixture':
+            K = getattr(cfg, 'n_components', None)
+            if isinstance(K, bool) or not isinstance(K, (int, float)) or int(K) != K or not 2 <= int(K) <= KMAX:
+                raise NotImplementedError("approx: 'mixture' with n_components: %r (supported: 2..%d; one component is "
+                                          "approx: 'diag')" % (K, KMAX))
         if cfg.approx == 'lowrank':
             columns = getattr(cfg, 'columns', None)
             if columns is None:
@@ -89,8 +98,13 @@ class UFlowElboLoss(nn.Module):
     # ---- the pieces -------------------------------------------------------------------------------------------
     def _split(self, net):
         """Level-2 output [B,C,h,w] -> mean, log_diag, diag = exp(+-log_diag), offdiag (None for 'diag') as channel slices;
-        'lowrank': mean, None, None, std [B,2 columns,h,w]."""
+        'lowrank': mean, None, None, std [B,2 columns,h,w]; 'mixture': the K means [B,2K,h,w], the K log-stds, None, None."""
         cfg = self.cfg
+        if cfg.approx == 'mixture':
+            K = int(cfg.n_components)
+            if net.shape[1] != 4 * K:
+                raise ValueError('approx mixture with n_components %d needs %d level-2 channels (got %d)' % (K, 4 * K, net.shape[1]))
+            return net[:, 0:2 * K], net[:, 2 * K:4 * K], None, None
         if cfg.approx == 'lowrank':
             R = int(cfg.columns)
             if net.shape[1] != 2 + 2 * R:
@@ -159,6 +173,22 @@ class UFlowElboLoss(nn.Module):
             l_c = census_loss(a['im'], recons, AF.up4_clamp_mul(occ_small, valid))
         return l_c, occ_small
 
+    def _mixture_samples(self, res_dict, net12, net21, S, eps, comp):
+        """The mixture's samples of both directions and their log-densities (:224-237, :307-309) -> (flows [S B,4,h,w], logpdf
+        [2,S B]).  What is not given is drawn in the reference's order: components then noise, forward direction first."""
+        B, _, h, w = net12.shape
+        K = int(self.cfg.n_components)
+        if 'weights_fw' in res_dict:
+            weights = (res_dict['weights_fw'], res_dict['weights_bw'])
+        else:
+            weights = (torch.full((B, K), 1.0 / K, device=net12.device, dtype=net12.dtype),) * 2
+        dirs = []
+        for d, net in enumerate((net12, net21)):
+            c = comp[d] if comp is not None else torch.multinomial(weights[d].detach(), S, replacement=True)
+            e = eps[d] if eps is not None else torch.randn((S * B, 2, h, w), device=net.device, dtype=net.dtype)
+            dirs.append((net, weights[d], c, e))
+        return reparam_gmm_pair(dirs[0], dirs[1], S)
+
     def _prepare(self, im, S, grey):
         if grey:
             small, gray = AF.down4_gray(im)
@@ -167,15 +197,22 @@ class UFlowElboLoss(nn.Module):
         return {'im': im.repeat(S, 1, 1, 1), 'small': small.repeat(S, 1, 1, 1), 'gray': None, 'small1': small}
 
     # ---- forward ----------------------------------------------------------------------------------------------
-    def forward(self, res_dict, im1_0, im2_0, eps=None):
+    def forward(self, res_dict, im1_0, im2_0, eps=None, comp=None):
         """res_dict['flows_fw'][2], ['flows_bw'][2]: the level-2 outputs [B,C,h,w] (mean, log_diag, off-diagonals; 'lowrank':
-        mean, columns); im1_0, im2_0 [B,3,4h,4w]; eps: (eps12, eps21), each [S B,2,h,w] ('lowrank': [S B,2 columns,1,1]), drawn
-        on the device (forward direction first) when None.  -> (total, loss_warp, loss_smooth, loss_entropy, loss_oof, flow12_2, occu_mask12, valid_mask12)."""
+        mean, columns; 'mixture': means, log-stds); im1_0, im2_0 [B,3,4h,4w]; eps: (eps12, eps21), each [S B,2,h,w] ('lowrank':
+        [S B,2 columns,1,1]), drawn on the device (forward direction first) when None; comp ('mixture' only): (comp12, comp21),
+        each [B,S] int64, the recorded component draws, torch.multinomial on the device when None.  -> (total, loss_warp, loss_smooth, loss_entropy, loss_oof, flow12_2, occu_mask12, valid_mask12)."""
         cfg = self.cfg
         if cfg.natural_grad:
             raise NotImplementedError("Natural gradient is not implemented!")
         if cfg.approx == 'sparse' and cfg.inv_cov:
             raise NotImplementedError("Sparse precision matrix representation is not implemented!")
+        mixture = cfg.approx == 'mixture'
+        if mixture and cfg.inv_cov:
+            raise NotImplementedError('Inverse covariance parametrization is not implemented for mixture variational '
+                                      'approximation.')
+        if comp is not None and not mixture:
+            raise ValueError('comp: component draws belong to approx mixture (approx is %r)' % (cfg.approx,))
         net12, net21 = res_dict['flows_fw'][2], res_dict['flows_bw'][2]
         S, with_bk = int(cfg.n_samples), bool(cfg.with_bk)
         B, _, h, w = net12.shape
@@ -188,21 +225,28 @@ class UFlowElboLoss(nn.Module):
 
         # reparameterisation: both directions into one (fw, bw) tensor
         lowrank = cfg.approx == 'lowrank'
-        if eps is None:
-            shape = (S * B, off12.shape[1], 1, 1) if lowrank else (S * B, 2, h, w)
-            eps12 = torch.randn(shape, device=net12.device, dtype=net12.dtype)
-            eps21 = torch.randn(shape, device=net12.device, dtype=net12.dtype)
+        if mixture:
+            flows2, logpdf = self._mixture_samples(res_dict, net12, net21, S, eps, comp)  # [S B,4,h,w], [2,S B]
         else:
-            eps12, eps21 = eps
-        if lowrank:  # off12, off21: the columns
-            flows2, logdet = reparam_lowrank_pair((mean12, off12, eps12), (mean21, off21, eps21), S)  # [S B,4,h,w], [2,B,2]
-        else:
-            flows2 = reparam_triag_pair((mean12, diag12, off12, eps12), (mean21, diag21, off21, eps21), k, S)  # [S B,4,h,w]
+            if eps is None:
+                shape = (S * B, off12.shape[1], 1, 1) if lowrank else (S * B, 2, h, w)
+                eps12 = torch.randn(shape, device=net12.device, dtype=net12.dtype)
+                eps21 = torch.randn(shape, device=net12.device, dtype=net12.dtype)
+            else:
+                eps12, eps21 = eps
+            if lowrank:  # off12, off21: the columns
+                flows2, logdet = reparam_lowrank_pair((mean12, off12, eps12), (mean21, off21, eps21), S)  # [S B,4,h,w], [2,B,2]
+            else:
+                flows2 = reparam_triag_pair((mean12, diag12, off12, eps12), (mean21, diag21, off21, eps21), k, S)  # [S B,4,h,w]
         flow12_2, flow21_2 = flows2[:, 0:2], flows2[:, 2:4]
 
         # entropy
         sign = -1.0 if cfg.inv_cov else 1.0
-        if lowrank:  # :362-381: (logdet G_u + logdet G_v) / (2 h w), mean over the batch, per direction
+        if mixture:  # :358-361: minus the mean log-density of the samples, per direction
+            loss_entropy = -cfg.w_entropy * logpdf[0].mean()
+            if with_bk:
+                loss_entropy = loss_entropy - cfg.w_entropy * logpdf[1].mean()
+        elif lowrank:  # :362-381: (logdet G_u + logdet G_v) / (2 h w), mean over the batch, per direction
             loss_entropy = cfg.w_entropy * (logdet[0].sum(1) / (2 * h * w)).mean()
             if with_bk:
                 loss_entropy = loss_entropy + cfg.w_entropy * (logdet[1].sum(1) / (2 * h * w)).mean()

@@ -4,7 +4,9 @@ Every level carries out_channels = [L, M, N] channels -- L = 2 flow channels (us
 the covariance / precision factor, N further channels (the off-diagonal band) that only the output level produces -- and
 brings them to the next level with upsample_out (:223-250): AF.out_upsample / AF.out_tail.
 M = 0 is the low-rank family (out_channels [2, 0, 2 columns]): the pyramid then carries the flow pair
-alone, and no zero-channel tensor is built or handed to a kernel."""
+alone, and no zero-channel tensor is built or handed to a kernel.
+ComponentNet (``"type": "component"``, :109-147) is the mixture family's model: two PWCProbFlow with
+out_channels [2, 2, 0], one per mixture component, their outputs joined per level as (mean1, mean2, log_diag1, log_diag2)."""
 import math
 
 import torch
@@ -13,6 +15,7 @@ import torch.nn.functional as func
 
 from .. import functional as AF
 from .. import uflow_utils
+from ..config import AttrDict
 from . import blocks
 # normalize_features, cost_volume_concat and uflow_utils.resample_flow are called as attributes of the uflow_model module
 # (mum.*), never bound here: oracle.host_models.oracle_ops substitutes exactly those attributes, and blocks.bias_act, so a
@@ -162,3 +165,36 @@ class PWCProbFlow(nn.Module):
         pyr_all = extractor(torch.cat([img1, img2], 0))
         return pair_pass(pyr_all, extractor.pyramid_moments, B, with_bk,
                          lambda p1, p2, n_passes, m: self.forward_2_frames(p1, p2, self._drops(n_passes, B, img1.device), m))
+
+
+def flows_concat(flow1, flow2):
+    """:98-106: per level, the two components' means and then their log-diagonals."""
+    return [torch.cat((a[:, 0:2], b[:, 0:2], a[:, 2:4], b[:, 2:4]), dim=1) for a, b in zip(flow1, flow2)]
+
+
+class ComponentNet(nn.Module):
+    """:109-147: one PWCProbFlow ([2, 2, 0], one pyramid) per mixture component; state-dict keys pwcnet1.*, pwcnet2.*."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        if cfg.mixture_weights:
+            raise NotImplementedError('ComponentNet: mixture_weights = %r (MixtureWeightsNet cannot run in the reference '
+                                      'either: DESIGN.md section 26)' % (cfg.mixture_weights,))
+        cfg1, cfg2 = AttrDict(dict(cfg)), AttrDict(dict(cfg))
+        for c in (cfg1, cfg2):
+            c.out_channels = [2, 2, 0]
+            c.mixture_weights = False
+            c.n_pyramids = 1
+        self.pwcnet1 = PWCProbFlow(cfg1)
+        self.pwcnet2 = PWCProbFlow(cfg2)
+
+    def init_weights(self):
+        self.pwcnet1.init_weights()
+        self.pwcnet2.init_weights()
+
+    def forward(self, img1, img2, with_bk=True):
+        # pwcnet1, then pwcnet2: level dropout consumes the CPU generator in the reference's sequence
+        res1 = self.pwcnet1(img1, img2, with_bk=with_bk)
+        res2 = self.pwcnet2(img1, img2, with_bk=with_bk)
+        return {key: flows_concat(res1[key], res2[key]) for key in res1}

@@ -48,6 +48,15 @@ WORKLOADS = {
              closed_form_smooth=False, data_loss=['census'], data_weight=[1.0], data_penalty=['abs_robust_loss'],
              w_entropy=0.1, w_oof=0.0, w_occ=0.0, with_bk=True, approx='lowrank', columns=15, n_components=1, inv_cov=False,
              approx_entropy=False, occ_type='sample', n_samples=4, offdiag_reg=0.0, natural_grad=False)),
+    # configs/chairs_uflow_elbo_mixture.json:10-36 with the model that can run it: ComponentNet (one PWCProbFlow [2,2,0] per
+    # mixture component) and uniform weights; the keys the file omits as the other ELBO workloads set them
+    'componentnet+uflow_elbo_mixture': (
+        dict(type='component', feature_norm=True, level_dropout=0.1, out_channels=[2, 2, 0], inv_cov=False, n_pyramids=2,
+             mixture_weights=False),
+        dict(type='uflow_elbo', edge_constant=150, edge_asymp=0.01, w_smooth=4.0, penalty_smooth='charbonnier',
+             closed_form_smooth=False, data_loss=['census'], data_weight=[1.0], data_penalty=['abs_robust_loss'],
+             w_entropy=0.3, w_oof=0.0, w_occ=0.0, with_bk=True, approx='mixture', n_components=2, inv_cov=False,
+             approx_entropy=False, occ_type='sample', n_samples=6, offdiag_reg=0.0, natural_grad=False)),
 }
 
 

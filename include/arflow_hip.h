@@ -634,6 +634,48 @@ int arflow_lowrank_bwd(const float* std, long std_bs, const float* eps, const fl
                        const float* glogdet, float* gmean, long gmean_bs, float* gstd, long gstd_bs, int B, int S, int R,
                        int M, int N, arflow_stream_t stream);
 
+/* ---- the Gaussian-mixture family: fused sampler + mixture log-density, one backward, entropy map (csrc/mixture.hip) ------
+ * reparam_gmm and the entropy of approx 'mixture' of losses/uflow_elbo_loss.py:159-178, :358-361 with gaussian_mixture_log_pdf
+ * and mixture_entropy of utils/misc_utils.py:67-132.
+ * mean, log_std [B][2K][M][N]: channel 2k + c is flow component c of mixture component k; 1 <= K <= 4; p = y N + x, P = M N.
+ * weights [B][K] >= 0 (contiguous); comp [B][S] 64-bit integers (contiguous): the component sample s of item b is drawn from,
+ * a value outside 0..K-1 is clamped into it; eps [S B][2][M][N].  Sample s of item b is row n = s B + b of eps, flow, gZ and
+ * of logpdf [S B], resp [S B][K], q [S B][K] (contiguous).  Every image-like tensor is fp32 with contiguous planes and its
+ * OWN batch stride in floats (read only when there is a second item), so channel slices are passed in place.
+ *   arflow_mixture_sample_fwd, one launch:  z = comp[b][s];  flow[n,c,p] = mean[b,2z+c,p] + exp(log_std[b,2z+c,p]) eps[n,c,p]
+ *     in fp32 (the product rounded, then the sum), and float64 partial sums over CHUNK = 1024 consecutive pixels of
+ *       A[n,k] = -sum_p sum_c (log_std[b,2k+c,p] + d^2 / 2),  d = (flow[n,c,p] - mean[b,2k+c,p]) / exp(log_std[b,2k+c,p])
+ *     into work [S B][chunks][K]: arflow_mixture_work_size(B, S, K, M, N) doubles (< 0: the ARFLOW_E* code), need not be
+ *     initialised.  float4 groups when P % 4 == 0 and all planes are 16-byte aligned, scalar loads otherwise.
+ *   arflow_mixture_logpdf_fwd, one small launch: adds the partials in chunk order and writes, from float64 rounded once,
+ *       logpdf[n] = (max_k A + log sum_k w[b,k] exp(A[n,k] - max_k A)) / P
+ *       resp[n,k] = w[b,k] e_k / sum_j w[b,j] e_j,   q[n,k] = e_k / sum_j w[b,j] e_j,   e_k = exp(A[n,k] - max_k A)
+ *     (w[b,k] = 0 gives resp = 0 and a finite q).  d logpdf[n] / d w[b,k] = q[n,k] / P.
+ *   arflow_mixture_bwd, one launch, a gather (one thread per pixel of item b loops over s and k); with lambda[n] =
+ *     glogpdf[n] / P and G[n,c,p] = gZ[n,c,p] - lambda[n] sum_k resp[n,k] d / std:
+ *       gmean[b,2k+c,p]    = sum_s (lambda[n] resp[n,k] d / std + [z == k] G[n,c,p])
+ *       glog_std[b,2k+c,p] = sum_s (lambda[n] resp[n,k] (d^2 - 1) + [z == k] G[n,c,p] std[b,2k+c,p] eps[n,c,p])
+ *     The samples are recomputed from eps (the sampler's own fp32 expression).  glogpdf [S B] (a DEVICE pointer) may be NULL
+ *     (no density term; resp is then not read) and gZ may be NULL (no gradient into the samples).
+ *   arflow_mixture_entropy_map, one launch, forward only:  out[b,p] = -(1 / n) sum_i (max_k x_k + log sum_k w[b,k] exp(x_k -
+ *     max)), x_k = -sum_c (log_std + d^2 / 2) at the pixel, for the n draws comp [B][n], eps [n B][2][M][N] (draw i of item b is
+ *     row i B + b); out [B][M N] contiguous.  mean and log_std are read once per pixel.
+ * No atomics: the same bits in either mode.  Every element of every output is stored.
+ * ARFLOW_ENULL: a required pointer is NULL; ARFLOW_EPARAM: K outside 1..4; ARFLOW_ESHAPE: B, S (n), M or N < 1, a batch
+ * stride smaller than its item, M N >= 2^31, S B > 65535.  Outputs must not overlap inputs. */
+long arflow_mixture_work_size(int B, int S, int K, int M, int N);
+int arflow_mixture_sample_fwd(const float* mean, long mean_bs, const float* log_std, long ls_bs, const float* eps, long eps_bs,
+                              const long* comp, float* flow, long flow_bs, double* work, int B, int S, int K, int M, int N,
+                              arflow_stream_t stream);
+int arflow_mixture_logpdf_fwd(const double* work, const float* weights, float* logpdf, float* resp, float* q, int B, int S,
+                              int K, int M, int N, arflow_stream_t stream);
+int arflow_mixture_bwd(const float* mean, long mean_bs, const float* log_std, long ls_bs, const float* eps, long eps_bs,
+                       const long* comp, const float* resp, const float* glogpdf, const float* gZ, long gz_bs, float* gmean,
+                       long gmean_bs, float* glog_std, long gls_bs, int B, int S, int K, int M, int N, arflow_stream_t stream);
+int arflow_mixture_entropy_map(const float* mean, long mean_bs, const float* log_std, long ls_bs, const float* weights,
+                               const long* comp, const float* eps, long eps_bs, float* out, int B, int n, int K, int M, int N,
+                               arflow_stream_t stream);
+
 /* ---- uncertainty metrics: sparsification curves and the calibration histogram -----------------------------------
  * The device side of evaluate_uncertainty / sp_plot / CalibrationCurve of utils/flow_utils.py:186-320 (DESIGN.md section
  * 19).  The `rows` conventions of arflow_flow_eval hold for all three: a row buffer need not be initialised, every row is

@@ -250,6 +250,106 @@ def lowrank_bench(dev, g, S=4, R=15, launches=30, repeats=5):
                                                                              'apart' if f[2] < t[1] else 'OVERLAP'), flush=True)
 
 
+def mixture_bench(dev, g, B=4, S=6, K=2, M=96, N=160, launches=30, repeats=5):
+    """the mixture node (sampler + log-density forward, one backward launch) at the workload's level-2
+    shape at 384 x 640 (B = 4, S = 6, K = 2, 96 x 160), next to the reference's formulation restated in torch ops (multinomial
+    draws given; four gathers, transposes and a cat for the sample; mean and log_std repeated S-fold, exp, the K error maps,
+    their squares, the log-determinants, two reductions over the pixels, the weighted log-sum-exp; ATen's autograd of all
+    that).  Protocol of lowrank_bench: 100 untimed calls, the functions timed in alternation, `repeats` rounds, median (min ..
+    max); the raw launches through the C ABI next to them, with algorithmic bytes."""
+    import statistics
+    from arflow_amd import mixture as MX
+
+    def torch_formulation(mean, log_std, weights, comp, eps):  # losses/uflow_elbo_loss.py:159-178, utils/misc_utils.py:67-101
+        std = torch.exp(log_std)
+        z = comp[:, :, None, None].repeat(1, 1, M, N)
+        pick = lambda t, c: torch.gather(t, 1, 2 * z + c).transpose(1, 0).reshape(-1, 1, M, N)  # noqa: E731
+        flow = torch.cat((pick(mean, 0), pick(mean, 1)), 1) + torch.cat((pick(std, 0), pick(std, 1)), 1) * eps
+        mean_r, ls_r, w_r = mean.repeat(S, 1, 1, 1), log_std.repeat(S, 1, 1, 1), weights.repeat(S, 1)
+        std_r = torch.exp(ls_r)
+        u = (flow[:, [0]] - mean_r[:, 0::2]) / std_r[:, 0::2]
+        v = (flow[:, [1]] - mean_r[:, 1::2]) / std_r[:, 1::2]
+        x = -torch.sum(ls_r[:, 0::2] + ls_r[:, 1::2], dim=(2, 3)) - torch.sum(u * u + v * v, dim=(2, 3)) / 2
+        top, _ = torch.max(x, dim=1, keepdim=True)
+        return flow, (top + torch.log(torch.sum(w_r * torch.exp(x - top), dim=1, keepdim=True))) / (M * N)
+
+    def spread(fns, shape, settle=100):
+        for fn in fns.values():
+            for _ in range(settle):
+                fn()
+        torch.cuda.synchronize()
+        t = {name: [] for name in fns}
+        for _ in range(repeats):
+            for name, fn in fns.items():
+                t[name].append(timeit(fn, launches))
+                MANIFEST[-1].update(name='mixture/' + name, shape=shape)
+        return {name: (statistics.median(v), min(v), max(v)) for name, v in t.items()}
+
+    net = torch.cat((1.5 * torch.randn(B, 2 * K, M, N, device=dev, generator=g),
+                     -1 + 0.3 * torch.randn(B, 2 * K, M, N, device=dev, generator=g)), 1).requires_grad_(True)
+    weights = torch.full((B, K), 1.0 / K, device=dev)
+    comp = torch.multinomial(weights, S, replacement=True, generator=g)
+    eps = torch.randn(S * B, 2, M, N, device=dev, generator=g)
+    w = torch.randn(S * B, 2, M, N, device=dev, generator=g)
+    wl = torch.randn(S * B, device=dev, generator=g)
+
+    def fused(grad):
+        z, lp = MX._Mixture.apply(S, 1, net, None, weights, comp, eps)
+        if grad:
+            torch.autograd.grad((z, lp[0]), net, (w, wl))
+
+    def plain(grad):
+        z, lp = torch_formulation(net[:, :2 * K], net[:, 2 * K:], weights, comp, eps)
+        if grad:
+            torch.autograd.grad((z, lp[:, 0]), net, (w, wl))
+
+    def no_grad(fn):
+        def run():
+            with torch.no_grad():
+                fn(False)
+        return run
+
+    with torch.no_grad():  # the two formulations agree before they are timed
+        (za, la), (zb, lb) = MX._Mixture.apply(S, 1, net, None, weights, comp, eps), torch_formulation(net[:, :2 * K], net[:, 2 * K:], weights, comp, eps)
+    print('mixture: max |flow - torch| %.3e, max |logpdf - torch| %.3e' % (float((za - zb).abs().max()), float((la[0] - lb[:, 0]).abs().max())), flush=True)
+
+    lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+    d = net.detach()
+    nb, pl = d.stride(0), M * N
+    z = torch.empty(S * B, 2, M, N, device=dev)
+    work = torch.empty(lib.arflow_mixture_work_size(B, S, K, M, N), device=dev, dtype=torch.float64)
+    lp, resp, q = torch.empty(S * B, device=dev), torch.empty(S * B, K, device=dev), torch.empty(S * B, K, device=dev)
+    gnet = torch.empty_like(d)
+    mean_p, ls_p = p(d), p(d[:, 2 * K:])
+
+    def launch_fwd():
+        lib.arflow_mixture_sample_fwd(mean_p, nb, ls_p, nb, p(eps), 2 * pl, p(comp), p(z), 2 * pl, p(work), B, S, K, M, N, st)
+
+    def launch_logpdf():
+        lib.arflow_mixture_logpdf_fwd(p(work), p(weights), p(lp), p(resp), p(q), B, S, K, M, N, st)
+
+    def launch_bwd():
+        lib.arflow_mixture_bwd(mean_p, nb, ls_p, nb, p(eps), 2 * pl, p(comp), p(resp), p(wl), p(w), 2 * pl, p(gnet), nb,
+                               p(gnet[:, 2 * K:]), nb, B, S, K, M, N, st)
+
+    launch_fwd()
+    launch_logpdf()
+    res = spread({'launch fwd': launch_fwd, 'launch logpdf': launch_logpdf, 'launch bwd': launch_bwd,
+                  'fused fwd': no_grad(fused), 'torch fwd': no_grad(plain), 'fused fwd+bwd': lambda: fused(True),
+                  'torch fwd+bwd': lambda: plain(True)}, [B, S, K, M, N])
+    # algorithmic bytes: forward mean + log_std + eps in, flow out; backward mean + log_std + eps + gZ in, both gradients out
+    par_b, smp_b = 4 * B * 4 * K * pl, 4 * S * B * 2 * pl
+    nbytes = {'launch fwd': par_b + 2 * smp_b, 'launch bwd': par_b + 2 * smp_b + par_b}
+    tag = 'mixture B=%d S=%d K=%d %dx%d' % (B, S, K, M, N)
+    for name, (med, lo, hi) in res.items():
+        gbs = '%8.1f GB/s algorithmic' % (nbytes[name] / med / 1e3) if name in nbytes else ''
+        print('%s %-14s %9.1f us  (min %.1f .. max %.1f)  %s' % (tag, name, med, lo, hi, gbs), flush=True)
+    for what in ('fwd', 'fwd+bwd'):
+        f, t = res['fused ' + what], res['torch ' + what]
+        print('%s %s: fused is %.2fx the torch formulation; ranges %s' % (tag, what, t[0] / f[0],
+                                                                         'apart' if f[2] < t[1] else 'OVERLAP'), flush=True)
+
+
 def out_up_bench(dev, g, B2=8, launches=30, repeats=5):
     """the output upsample of PWCProbFlow -- AF.out_upsample / AF.out_tail (one launch each way) next to
     the composed ATen path the model runs with ARFLOW_OUT_UP=0 (split, bias add, F.interpolate per group, x2, cat, and
@@ -663,6 +763,8 @@ def main():
                 p(A), p(Bc), p(Cc), p(gA), P, M, N, s), max(3, args.iters // 10)), 4 * P * M * N)
     if want('lowrank'):  # the low-rank sampler and Gram log-determinant (csrc/lowrank.hip) against the torch formulation
         lowrank_bench(dev, g)
+    if want('mixture'):  # the mixture sampler + log-density node (csrc/mixture.hip) against the torch formulation
+        mixture_bench(dev, g)
     if want('band'):  # the fused sparse-covariance sampler (csrc/band.hip) against the reference's formulation in torch ops
         band_bench(dev, g)
     if want('out_up'):  # the probabilistic model's output upsample (csrc/out_up.hip) against the composed ATen path
