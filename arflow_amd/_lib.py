@@ -26,6 +26,8 @@ PROTOTYPES = {
     'arflow_out_up2_fwd': [c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_fp],
     'arflow_out_up2_bwd': [c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_out_tail_fwd': [c_fp, c_l, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_fp],
+    'arflow_prob_up_fwd': [c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_fp],
+    'arflow_prob_up_bwd': [c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_profile_marker': [c_i, c_fp],
     'arflow_sums_rows': [c_i, c_i, c_i],
     'arflow_corr_fwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_fp],
@@ -117,6 +119,9 @@ PROTOTYPES = {
     'arflow_mixture_logpdf_fwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_mixture_bwd': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_mixture_entropy_map': [c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_gauss_pyr_work_size': [c_fp, c_fp, c_i, c_i],
+    'arflow_gauss_pyr_sample_fwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_fp],
+    'arflow_gauss_pyr_sample_bwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_fp],
     'arflow_uncert_rows': [c_i, c_i],
     'arflow_uncert_prep': [c_fp, c_fp, c_fp, c_l, c_fp, c_fp, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_sparsify_sums': [c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp],

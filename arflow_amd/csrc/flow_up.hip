@@ -28,21 +28,8 @@ __global__ __launch_bounds__(256) void flow_up_fwd_kernel(const float* __restric
   out[idx] = f * up_blend(wx0, wx1, wy0, wy1, a00, a01, a10, a11);
 }
 
-// Adjoint: one thread per coarse cell (i, j).  The fine rows that read coarse row i are those whose source index i0 is i or
-// i - 1, i.e. src in [i - 1, i + 1): a run of consecutive rows found from the inverse of the source map and widened by two on
-// either side -- the weights themselves come from up_source, so a row outside the true run simply weighs 0 and the margin
-// only has to be generous, not exact.  Rows ascending, columns ascending inside a row: a fixed order.
-__device__ __forceinline__ void fine_run(int i, int n_in, int n_out, int factor, bool align, int& lo, int& hi) {
-  if (align) {
-    const float inv = n_in > 1 ? (float)(n_out - 1) / (float)(n_in - 1) : (float)n_out;  // fine rows per coarse row
-    lo = (int)floorf((float)(i - 1) * inv) - 2;
-    hi = (int)ceilf((float)(i + 1) * inv) + 2;
-  } else {
-    lo = factor * (i - 1) - 2;
-    hi = factor * (i + 2) + 2;
-  }
-  lo = max(lo, 0), hi = min(hi, n_out - 1);
-}
+// Adjoint: one thread per coarse cell (i, j) over the run of fine rows / columns fine_run (taps.hpp) gives; rows ascending,
+// columns ascending inside a row: a fixed order.
 __global__ __launch_bounds__(256) void flow_up_bwd_kernel(const float* __restrict__ gfine, float* __restrict__ gcoarse,
                                                           int planes, int h, int w, int factor, int align) {
   const int H = h * factor, W = w * factor;

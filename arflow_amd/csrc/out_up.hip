@@ -193,6 +193,89 @@ __global__ __launch_bounds__(256) void out_tail_fwd_kernel(const float* __restri
   }
 }
 
+// ---- the align_corners=True sibling for factors 2 and 4: models/pwclite_prob.py:183-186,216-217 ------
+//   out[b,c] = s_c * upsample_bilinear2d(in[b,c] + b_c, x f, align_corners=True),  s_c = f for c < n_flow else 1
+// Source index and weights: up_source's align branch (scale = (h - 1) / (H - 1) in fp32, src = scale * dst: ATen's order).
+template <int V>
+__global__ __launch_bounds__(256) void prob_up_fwd_kernel(const float* __restrict__ in, long in_bs, float* __restrict__ out,
+                                                          long out_bs, int B, int C, int h, int w, int f, int n_flow, int n_diag,
+                                                          float diag_bias) {
+  const int H = f * h, W = f * w, Wq = W / V;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)B * C * H * Wq) return;
+  const int xq = (int)(idx % Wq), y = (int)((idx / Wq) % H);
+  const long pl = idx / ((long)Wq * H);
+  const int c = (int)(pl % C), b = (int)(pl / C);
+  const float sc = c < n_flow ? (float)f : 1.f;  // chan_rule with the factor in place of 2
+  const float bias = (c >= n_flow && c < n_flow + n_diag) ? diag_bias : 0.f;
+  int ya, yb;
+  float wy0, wy1;
+  up_source(y, h, H, 0.f, true, ya, yb, wy0, wy1);
+  const float* s = in + (long)b * in_bs + (long)c * h * w;
+  const float* ra = s + (long)ya * w;
+  const float* rb = s + (long)yb * w;
+  float r[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    int xa, xb;
+    float wx0, wx1;
+    up_source(xq * V + k, w, W, 0.f, true, xa, xb, wx0, wx1);
+    r[k] = sc * up_blend(wx0, wx1, wy0, wy1, ra[xa] + bias, ra[xb] + bias, rb[xa] + bias, rb[xb] + bias);
+  }
+  float* o = out + (long)b * out_bs + ((long)c * H + y) * W + xq * V;
+  if constexpr (V == 4) {
+    *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
+  } else {
+    o[0] = r[0];
+  }
+}
+
+// Adjoint as a gather: one thread per coarse cell over fine_run's rows and columns (taps.hpp; the run is generous, a fine
+// pixel that does not read the cell weighs 0), rows ascending, columns ascending inside a row.  The bias has no gradient.
+// The column weights are the same for every row: the first PROB_UP_COLS of the run are computed once and kept in registers
+// (for factors 2 and 4 the run is at most 2 * 5 + 5 = 15 columns wide once w >= 4, and at most W <= 12 below that); columns
+// beyond them, should a run ever be wider, are weighed where they are used.  Same weights, same order of additions.
+constexpr int PROB_UP_COLS = 16;
+__global__ __launch_bounds__(256) void prob_up_bwd_kernel(const float* __restrict__ gfine, long gf_bs, float* __restrict__ gcoarse,
+                                                          long gc_bs, int B, int C, int h, int w, int f, int n_flow) {
+  const int H = f * h, W = f * w;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)B * C * h * w) return;
+  const int j = (int)(idx % w), i = (int)((idx / w) % h);
+  const long pl = idx / ((long)w * h);
+  const int c = (int)(pl % C), b = (int)(pl / C);
+  const float* g = gfine + (long)b * gf_bs + (long)c * H * W;
+  int ylo, yhi, xlo, xhi;
+  fine_run(i, h, H, f, true, ylo, yhi);
+  fine_run(j, w, W, f, true, xlo, xhi);
+  float wx[PROB_UP_COLS];
+#pragma unroll
+  for (int k = 0; k < PROB_UP_COLS; ++k) {
+    int a0, a1;
+    float l0, l1;
+    up_source(min(xlo + k, W - 1), w, W, 0.f, true, a0, a1, l0, l1);
+    wx[k] = (a0 == j ? l0 : 0.f) + (a1 == j ? l1 : 0.f);
+  }
+  float acc = 0.f;
+  for (int y = ylo; y <= yhi; ++y) {
+    int a0, a1;
+    float l0, l1;
+    up_source(y, h, H, 0.f, true, a0, a1, l0, l1);
+    const float wy = (a0 == i ? l0 : 0.f) + (a1 == i ? l1 : 0.f);
+    const float* gr = g + (long)y * W;
+    float row = 0.f;
+#pragma unroll
+    for (int k = 0; k < PROB_UP_COLS; ++k)
+      if (xlo + k <= xhi) row = fmaf(wx[k], gr[xlo + k], row);
+    for (int x = xlo + PROB_UP_COLS; x <= xhi; ++x) {
+      up_source(x, w, W, 0.f, true, a0, a1, l0, l1);
+      row = fmaf((a0 == j ? l0 : 0.f) + (a1 == j ? l1 : 0.f), gr[x], row);
+    }
+    acc = fmaf(wy, row, acc);
+  }
+  gcoarse[(long)b * gc_bs + ((long)c * h + i) * w + j] = (c < n_flow ? (float)f : 1.f) * acc;
+}
+
 int out_up_check(const void* a, long a_bs, const void* o, long o_bs, int B, int C, int h, int w, int n_flow, int n_diag,
                  int a_scale, int o_scale) {
   AF_REQUIRE_PTR(a);
@@ -252,5 +335,36 @@ extern "C" int arflow_out_tail_fwd(const float* in, long in_bstride, float* out1
     hipLaunchKernelGGL(out_tail_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, in, in_bstride, out1, out0, B, C,
                        h, w, n_flow, n_diag, diag_bias, ntx, nty);
   }
+  return af_launch_status();
+}
+
+extern "C" int arflow_prob_up_fwd(const float* in, long in_bstride, float* out, long out_bstride, int B, int C, int h, int w,
+                                  int factor, int n_flow, int n_diag, float diag_bias, arflow_stream_t stream) {
+  af_clear_stale_error();
+  AF_REQUIRE(factor == 2 || factor == 4, ARFLOW_EPARAM);
+  const int rc = out_up_check(in, in_bstride, out, out_bstride, B, C, h, w, n_flow, n_diag, 1, factor * factor);
+  if (rc != ARFLOW_OK) return rc;
+  AF_REQUIRE(h <= 2048 && w <= 2048, ARFLOW_ESHAPE);
+  const long n = (long)B * C * factor * factor * h * w;
+  if (((long)factor * w) % 4 == 0 && aligned16(out) && (B == 1 || out_bstride % 4 == 0)) {
+    hipLaunchKernelGGL(prob_up_fwd_kernel<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in,
+                       in_bstride, out, out_bstride, B, C, h, w, factor, n_flow, n_diag, diag_bias);
+  } else {
+    hipLaunchKernelGGL(prob_up_fwd_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in,
+                       in_bstride, out, out_bstride, B, C, h, w, factor, n_flow, n_diag, diag_bias);
+  }
+  return af_launch_status();
+}
+
+extern "C" int arflow_prob_up_bwd(const float* gfine, long gfine_bstride, float* gcoarse, long gcoarse_bstride, int B, int C,
+                                  int h, int w, int factor, int n_flow, arflow_stream_t stream) {
+  af_clear_stale_error();
+  AF_REQUIRE(factor == 2 || factor == 4, ARFLOW_EPARAM);
+  const int rc = out_up_check(gfine, gfine_bstride, gcoarse, gcoarse_bstride, B, C, h, w, n_flow, 0, factor * factor, 1);
+  if (rc != ARFLOW_OK) return rc;
+  AF_REQUIRE(h <= 2048 && w <= 2048, ARFLOW_ESHAPE);
+  const long n = (long)B * C * h * w;
+  hipLaunchKernelGGL(prob_up_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gfine,
+                     gfine_bstride, gcoarse, gcoarse_bstride, B, C, h, w, factor, n_flow);
   return af_launch_status();
 }

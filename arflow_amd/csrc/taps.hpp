@@ -114,6 +114,22 @@ __device__ __forceinline__ float up_blend(float wx0, float wx1, float wy0, float
   return wy0 * (wx0 * a00 + wx1 * a01) + wy1 * (wx0 * a10 + wx1 * a11);
 }
 
+// Gather adjoints of the resize (flow_up.hip, out_up.hip): one thread per coarse cell (i, j).  The fine rows that read
+// coarse row i are those whose source index i0 is i or i - 1, i.e. src in [i - 1, i + 1): a run of consecutive rows found from the inverse of the source map and widened by two on
+// either side -- the weights themselves come from up_source, so a row outside the true run simply weighs 0 and the margin
+// only has to be generous, not exact.  Rows ascending, columns ascending inside a row: a fixed order.
+__device__ __forceinline__ void fine_run(int i, int n_in, int n_out, int factor, bool align, int& lo, int& hi) {
+  if (align) {
+    const float inv = n_in > 1 ? (float)(n_out - 1) / (float)(n_in - 1) : (float)n_out;  // fine rows per coarse row
+    lo = (int)floorf((float)(i - 1) * inv) - 2;
+    hi = (int)ceilf((float)(i + 1) * inv) + 2;
+  } else {
+    lo = factor * (i - 1) - 2;
+    hi = factor * (i + 2) + 2;
+  }
+  lo = max(lo, 0), hi = min(hi, n_out - 1);
+}
+
 // The four target cells and weights of a forward splat at position (cx, cy) (splat_kernel, warp.hip, and its fixed-order
 // form in det_scatter.hip): variant 0 = compute_range_map, 1 = get_corresponding_map (clamped indices, weight dropped when a
 // tap left the image).

@@ -1378,6 +1378,57 @@ def out_tail(x, n_flow, n_diag, diag_bias):
     return OutTailFunction.apply(x, n_flow, n_diag, diag_bias)
 
 
+class ProbUpsampleFunction(torch.autograd.Function):
+    """models/pwclite_prob.py:183-186,216-217 as one launch: out[:, c] = s_c * interpolate(x[:, c] + b_c, x factor, bilinear,
+    align_corners=True), s_c = factor for the first n_flow channels, b_c = diag_bias for the next n_diag (DESIGN.md section
+    27).  The adjoint is a gather (arflow_prob_up_bwd): reproducible in either mode, so the node does not sample the mode."""
+
+    @staticmethod
+    def forward(ctx, out, x, factor, n_flow, n_diag, diag_bias):
+        # (`out` first, as in OutUpsampleFunction)
+        _need_gpu(x, out)
+        if x.dim() != 4:
+            raise ValueError('prob_upsample expects a [B,C,h,w] tensor')
+        B, C, h, w = x.shape
+        factor, n_flow, n_diag = int(factor), int(n_flow), int(n_diag)
+        if factor not in (2, 4):
+            raise ValueError('prob_upsample: factor must be 2 or 4 (got %r)' % (factor,))
+        if n_flow < 0 or n_diag < 0 or n_flow + n_diag > C:
+            raise ValueError('prob_upsample: n_flow %d + n_diag %d exceed the %d channels' % (n_flow, n_diag, C))
+        x, xbs = _plane_view(x)
+        if out is None:
+            out = torch.empty(B, C, factor * h, factor * w, device=x.device, dtype=torch.float32)
+        else:
+            if tuple(out.shape) != (B, C, factor * h, factor * w):
+                raise ValueError('prob_upsample: out must be [B,C,%dh,%dw]' % (factor, factor))
+            view, _ = _plane_view(out)
+            if view is not out:
+                raise ValueError('prob_upsample: out must have contiguous planes (a channel slice of a contiguous buffer)')
+            ctx.mark_dirty(out)
+        _, obs = _plane_view(out)
+        with torch.cuda.device_of(x):
+            _call('arflow_prob_up_fwd', _p(x), xbs, _p(out), obs, B, C, h, w, factor, n_flow, n_diag, float(diag_bias),
+                  _stream(), key=(B, C, h, w, factor, 'fwd'))
+        ctx.cfg = (B, C, h, w, factor, n_flow)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        B, C, h, w, factor, n_flow = ctx.cfg
+        g, gbs = _plane_view(gout)
+        gin = torch.empty(B, C, h, w, device=g.device, dtype=torch.float32)
+        with torch.cuda.device_of(g):
+            _call('arflow_prob_up_bwd', _p(g), gbs, _p(gin), C * h * w, B, C, h, w, factor, n_flow, _stream(),
+                  key=(B, C, h, w, factor, 'bwd'))
+        return None, gin, None, None, None, None
+
+
+def prob_upsample(x, factor, n_flow, n_diag, diag_bias, out=None):
+    """x [B,C,h,w] (may be a channel slice) -> [B,C,factor h,factor w], factor 2 or 4, align_corners=True; `out` may be a
+    channel slice of a preallocated buffer (it is written in place and returned).  diag_bias is a constant: no gradient."""
+    return ProbUpsampleFunction.apply(out, x, factor, n_flow, n_diag, diag_bias)
+
+
 def interpolate_flow(flow, factor, align_corners):
     """The models' flow upsample: ATen's F.interpolate in default mode (unchanged), flow_upsample in deterministic mode."""
     if flow.is_cuda and flow.dtype == torch.float32 and is_deterministic():

@@ -3,7 +3,7 @@
 (README.md:32-50:  inference.py -m <ckpt> -s 384 640 -i img1 img2 [img0 img1 img2]); the fork's own
 inference.py only drives its probabilistic models.
 
-    python -m arflow_amd.inference -s 384 640 -i a.png b.png [-m ckpt.pth.tar] [-o flow.flo] [--arch pwclite|pwclite_uflow|uflow|uflow_prob]
+    python -m arflow_amd.inference -s 384 640 -i a.png b.png [-m ckpt.pth.tar] [-o flow.flo] [--arch pwclite|pwclite_prob|pwclite_uflow|uflow|uflow_prob]
                                 [--columns R] [--entropy-out ent.npy]
 
 Runs on the GPU through the HIP kernels.  Without -m the network is seeded-random (no checkpoint ships
@@ -13,7 +13,9 @@ the reference's ELBO trainer evaluates as the per-component entropy for `diag`, 
 (trainer/uflow_elbo_trainer.py:175,191), and what `python -m arflow_amd.evaluate --entropy` reads.  With --columns R the model
 is the low-rank family's (out_channels [2, 0, 2R], configs/chairs_uflow_elbo_lowrank.json) and --entropy-out writes the map
 the reference's inference and validation compute for it (inference.py:76-84, trainer/uflow_elbo_trainer.py:193-197):
-upsample(log(sum_k std_k^2) / 2 + 2 log 4, x4, align_corners=False) of the level-2 columns, in plain torch.
+upsample(log(sum_k std_k^2) / 2 + 2 log 4, x4, align_corners=False) of the level-2 columns, in plain torch.  --arch pwclite_prob is
+PWCLiteProb (upsample, reduce_dense); its channels 2:4 are the log VARIANCE, so --entropy-out writes flows_fw[0][:, 2:4] / 2,
+the log standard deviation `evaluate --entropy` reads.
 """
 import argparse
 import math
@@ -23,7 +25,7 @@ import torch
 
 from .config import AttrDict
 from .flow_io import write_flow
-from .models import get_model
+from .models import PWCLiteProb, get_model
 
 
 def load_image(path, size):
@@ -37,6 +39,10 @@ def load_image(path, size):
 def build_model(kind, n_frames, ckpt=None, seed=0, columns=0):
     if kind == 'pwclite':
         cfg = AttrDict(type='pwclite', upsample=True, n_frames=n_frames, reduce_dense=True)
+    elif kind == 'pwclite_prob':
+        if n_frames != 2:
+            raise ValueError('PWCLiteProb takes two frames')
+        cfg = AttrDict(type='pwclite_prob', upsample=True, n_frames=2, reduce_dense=True)
     elif kind == 'pwclite_uflow':
         cfg = AttrDict(type='pwclite_uflow', level_dropout=0.0, feature_norm=True, align_corners=True, warp_pad='zeros',
                        n_frames=2, reduce_dense=False)
@@ -67,8 +73,11 @@ def infer(model, frames, device, want_entropy=False):
     lowrank_entropy_map --, [H,W,2]."""
     x = torch.cat(frames, 0).unsqueeze(0).to(device)
     prob = hasattr(model, 'upsample_out')
-    if want_entropy and not prob:
-        raise ValueError('only the probabilistic model (--arch uflow_prob) has an entropy output')
+    lite_prob = isinstance(model, PWCLiteProb)  # (flow, log-variance) outputs
+    if want_entropy and not (prob or lite_prob):
+        raise ValueError('only the probabilistic models (--arch uflow_prob, pwclite_prob) have an entropy output')
+    if lite_prob and len(frames) != 2:
+        raise ValueError('PWCLiteProb takes two frames')
     if prob:
         if len(frames) != 2:
             raise ValueError('PWCProbFlow takes two frames')
@@ -76,6 +85,8 @@ def infer(model, frames, device, want_entropy=False):
     else:
         res = model(x, with_bk=False) if len(frames) == 2 else model(x)
     out = res['flows_fw'][0][0].permute(1, 2, 0).float().cpu().numpy()
+    if lite_prob:
+        return (out[..., 0:2], out[..., 2:4] / 2) if want_entropy else out[..., 0:2]
     if want_entropy:
         if model._out_channels[1] == 0:
             ent = lowrank_entropy_map(res['flows_fw'][2][:, 2:])
@@ -97,9 +108,9 @@ def main():
     ap.add_argument('-s', '--test_shape', default=[384, 640], type=int, nargs=2)
     ap.add_argument('-i', '--img_list', nargs='+', required=True)
     ap.add_argument('-o', '--output', default=None, help='write the flow as .flo')
-    ap.add_argument('--arch', default='pwclite', choices=['pwclite', 'pwclite_uflow', 'uflow', 'uflow_prob'])
+    ap.add_argument('--arch', default='pwclite', choices=['pwclite', 'pwclite_prob', 'pwclite_uflow', 'uflow', 'uflow_prob'])
     ap.add_argument('--columns', default=0, type=int, help='uflow_prob: the low-rank family with this many columns (1..16)')
-    ap.add_argument('--entropy-out', default=None, help='write the log-diagonal channels as .npy [H,W,2] (uflow_prob)')
+    ap.add_argument('--entropy-out', default=None, help='write the log standard deviation as .npy [H,W,2] (uflow_prob, pwclite_prob)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('arflow_amd.inference needs a GPU: the correlation / warp kernels have no CPU fallback')

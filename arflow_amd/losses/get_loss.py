@@ -1,5 +1,6 @@
-"""losses/get_loss.py:9-24 for the loss types on the hot path and the ELBO objective of the probabilistic family (DESIGN.md
-section 21; the MSE research losses are out of scope)."""
+"""losses/get_loss.py:9-24 for the loss types on the hot path and the ELBO objectives of the probabilistic families (DESIGN.md
+sections 21 and 27; the MSE research losses are out of scope)."""
+from .elbo_loss import ElboLoss
 from .flow_loss import unFlowLoss
 from .fullres_loss import FullResLoss
 from .mv_loss import MvLoss
@@ -10,6 +11,8 @@ from .uflow_loss import UFlowLoss
 def get_loss(cfg):
     if cfg.type == 'unflow':
         return unFlowLoss(cfg)
+    if cfg.type == 'elbo':
+        return ElboLoss(cfg)
     if cfg.type == 'fullres':
         return FullResLoss(cfg)
     if cfg.type == 'uflow':

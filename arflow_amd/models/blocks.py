@@ -110,9 +110,10 @@ class FeatureExtractor(nn.Module):
 
 
 class FlowEstimatorDense(nn.Module):
-    """models/pwclite.py:48-66."""
+    """models/pwclite.py:48-66; ch_out as models/pwclite_prob.py:49-50 (a head wider than two channels keeps F.conv2d and the
+    tensor expression below: HeadConv.native and the dense node are two-channel)."""
 
-    def __init__(self, ch_in):
+    def __init__(self, ch_in, ch_out=2):
         super().__init__()
         self.conv1 = conv(ch_in, 128)
         self.conv2 = conv(ch_in + 128, 128)
@@ -120,7 +121,7 @@ class FlowEstimatorDense(nn.Module):
         self.conv4 = conv(ch_in + 352, 64)
         self.conv5 = conv(ch_in + 416, 32)
         self.feat_dim = ch_in + 448
-        self.conv_last = conv(ch_in + 448, 2, isReLU=False)
+        self.conv_last = conv(ch_in + 448, ch_out, isReLU=False)
 
     def native(self, x):
         """The whole estimator as one autograd node (AF.dense_estimator) under the rule HeadConv.native applies: a CUDA fp32
@@ -138,9 +139,9 @@ class FlowEstimatorDense(nn.Module):
 
 
 class FlowEstimatorReduce(nn.Module):
-    """models/pwclite.py:69-88."""
+    """models/pwclite.py:69-88; ch_out as models/pwclite_prob.py:72."""
 
-    def __init__(self, ch_in):
+    def __init__(self, ch_in, ch_out=2):
         super().__init__()
         self.conv1 = conv(ch_in, 128)
         self.conv2 = conv(128, 128)
@@ -148,7 +149,7 @@ class FlowEstimatorReduce(nn.Module):
         self.conv4 = conv(128 + 96, 64)
         self.conv5 = conv(96 + 64, 32)
         self.feat_dim = 32
-        self.predict_flow = conv(64 + 32, 2, isReLU=False)
+        self.predict_flow = conv(64 + 32, ch_out, isReLU=False)
 
     def forward(self, x):
         x1 = self.conv1(x)
@@ -160,13 +161,13 @@ class FlowEstimatorReduce(nn.Module):
 
 
 class ContextNetwork(nn.Module):
-    """models/pwclite.py:91-106 -- 7 dilated convs."""
+    """models/pwclite.py:91-106 -- 7 dilated convs; ch_out as models/pwclite_prob.py:93."""
 
-    def __init__(self, ch_in):
+    def __init__(self, ch_in, ch_out=2):
         super().__init__()
         self.convs = nn.Sequential(
             conv(ch_in, 128, 3, 1, 1), conv(128, 128, 3, 1, 2), conv(128, 128, 3, 1, 4), conv(128, 96, 3, 1, 8),
-            conv(96, 64, 3, 1, 16), conv(64, 32, 3, 1, 1), conv(32, 2, isReLU=False))
+            conv(96, 64, 3, 1, 16), conv(64, 32, 3, 1, 1), conv(32, ch_out, isReLU=False))
 
     def forward(self, x):
         return self.convs(x)

@@ -23,6 +23,13 @@ WORKLOADS = {
         dict(type='unflow', w_l1=0.15, w_ssim=0.85, w_ternary=0.0, warp_pad='border', alpha=10, occ_from_back=True,
              with_bk=True, w_smooth=75.0, w_scales=[1.0, 1.0, 1.0, 1.0, 1.0, 0.0],
              w_sm_scales=[1.0, 0.0, 0.0, 0.0, 0.0, 0.0])),
+    # build-defined (the reference ships no config for the pair): the probabilistic PWCLite and the ELBO form of the loss above,
+    # its weights on the model's five scales
+    'pwcliteprob+elbo_loss': (
+        dict(type='pwclite_prob', upsample=True, n_frames=2, reduce_dense=True),
+        dict(type='elbo', w_l1=0.15, w_ssim=0.85, w_ternary=0.0, warp_pad='border', alpha=10, occ_from_back=True,
+             with_bk=True, w_smooth=75.0, w_scales=[1.0, 1.0, 1.0, 1.0, 1.0], w_sm_scales=[1.0, 0.0, 0.0, 0.0, 0.0],
+             w_en_scales=[1.0, 1.0, 1.0, 1.0, 1.0], w_entropy=0.1)),
     # BASELINE config 5: 3-frame PWCLite (forward_3_frames) + the build-defined multi-view objective
     'pwclite3+mv_loss': (
         dict(type='pwclite', upsample=True, n_frames=3, reduce_dense=True),

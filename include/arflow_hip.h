@@ -104,6 +104,18 @@ int arflow_out_up2_bwd(const float* gfine, long gfine_bstride, float* gcoarse, l
                        int w, int n_flow, arflow_stream_t stream);
 int arflow_out_tail_fwd(const float* in, long in_bstride, float* out1, float* out0, int B, int C, int h, int w, int n_flow,
                         int n_diag, float diag_bias, arflow_stream_t stream);
+/* The align_corners=True sibling of arflow_out_up2_* for factor 2 or 4 (else ARFLOW_EPARAM), the upsample of the (flow,
+ * log-variance) state of models/pwclite_prob.py:183-186,216-217: out[b,c] = s_c * upsample_bilinear2d(in[b,c] + b_c, x factor,
+ * align_corners=True) with s_c = factor for c < n_flow (else 1) and b_c = diag_bias for n_flow <= c < n_flow + n_diag (else 0),
+ * the bias added on load.  Source coordinate and weights in ATen's fp32 order: scale = (h - 1) / (H - 1), src = scale * dst,
+ * floor, lambda and 1 - lambda.  Layout rules, slices and batch strides as arflow_out_up2_fwd; in [B,C,h,w] -> out
+ * [B,C,factor h,factor w]; float4 stores where factor * w % 4 == 0 and out / out_bstride are 16-byte aligned.  h, w <= 2048.
+ * arflow_prob_up_bwd is the adjoint as a GATHER (gfine [B,C,factor h,factor w] -> gcoarse [B,C,h,w]): one coarse cell adds
+ * the fine pixels that read it, rows then columns ascending; every element written, no atomics, bitwise reproducible. */
+int arflow_prob_up_fwd(const float* in, long in_bstride, float* out, long out_bstride, int B, int C, int h, int w, int factor,
+                       int n_flow, int n_diag, float diag_bias, arflow_stream_t stream);
+int arflow_prob_up_bwd(const float* gfine, long gfine_bstride, float* gcoarse, long gcoarse_bstride, int B, int C, int h,
+                       int w, int factor, int n_flow, arflow_stream_t stream);
 /* HIP keeps ONE "last error" per host thread.  If a code was already pending when an entry point is entered
  * (left by the host framework or an unchecked earlier call) it is not attributed to this library's launch and
  * not dropped either: the first such hipError_t is kept (and reported once on stderr) until the host reads it
@@ -675,6 +687,33 @@ int arflow_mixture_bwd(const float* mean, long mean_bs, const float* log_std, lo
 int arflow_mixture_entropy_map(const float* mean, long mean_bs, const float* log_std, long ls_bs, const float* weights,
                                const long* comp, const float* eps, long eps_bs, float* out, int B, int n, int K, int M, int N,
                                arflow_stream_t stream);
+
+/* ---- the diagonal Gaussian sampler of ElboLoss over a whole pyramid ------------------------
+ * losses/elbo_loss.py:17-27,90-91,117-124 for all n scales (1 <= n <= 6, else ARFLOW_EPARAM) in ONE launch.  Every argument
+ * that is an array has n entries on the HOST (pointers to device tensors, batch strides in floats, sizes); the tables travel
+ * to the kernel by value.  Per scale i:
+ *   net[i] [B][8][h_i][w_i]: mean_fw 0:2, logvar_fw 2:4, mean_bw 4:6, logvar_bw 6:8;  eps[i], z[i] [B][4][h_i][w_i]: the
+ *   forward direction in channels 0:2, the backward one in 2:4.  fp32, planes contiguous, each tensor with its own batch
+ *   stride (read only when B > 1): channel slices are passed in place.
+ * arflow_gauss_pyr_sample_fwd:  z = mean + RN(expf(logvar / 2) * eps) in fp32, and ent [n][2] (float64, device):
+ *   ent[i][d] = sum over b, the two channels and the pixels of logvar_d, in float64 from the load on -- per lane, by wave
+ *   butterfly, in wave order: one partial per workgroup in work (arflow_gauss_pyr_work_size(h, w, n, B) doubles, < 0: the
+ *   ARFLOW_E* code; need not be initialised), folded in a fixed order by a second one-wave-per-sum launch of the same call.
+ * arflow_gauss_pyr_sample_bwd, one launch, a per-pixel map that stores all 8 channels of every gnet[i] [B][8][h_i][w_i]:
+ *   gmean = gz,  glogvar = gz * (0.5f * expf(logvar / 2) * eps) + (float)gent[i][d]
+ *   gz (the array, or an entry of it) may be NULL: zero.  gent [n][2] is a DEVICE pointer (float64) or NULL (zero).  The
+ *   standard deviation is recomputed with the sampler's expression.
+ * float4 groups for a scale whose h w % 4 == 0 with 16-byte aligned pointers and strides, scalar accesses otherwise.  No
+ * atomics: the same bits in either mode.  Every element of every output is stored.
+ * ARFLOW_ENULL: a required pointer (or entry) is NULL; ARFLOW_EPARAM: n outside 1..6; ARFLOW_ESHAPE: B, h or w < 1, B > 65535,
+ * h w >= 2^30, a batch stride smaller than its item, more than 2^31 - 1 workgroups.  Outputs must not overlap inputs. */
+long arflow_gauss_pyr_work_size(const int* h, const int* w, int n, int B);
+int arflow_gauss_pyr_sample_fwd(const float* const* net, const long* net_bs, const float* const* eps, const long* eps_bs,
+                                float* const* z, const long* z_bs, const int* h, const int* w, int n, int B, double* work,
+                                double* ent, arflow_stream_t stream);
+int arflow_gauss_pyr_sample_bwd(const float* const* gz, const long* gz_bs, const float* const* net, const long* net_bs,
+                                const float* const* eps, const long* eps_bs, const double* gent, float* const* gnet,
+                                const long* gnet_bs, const int* h, const int* w, int n, int B, arflow_stream_t stream);
 
 /* ---- uncertainty metrics: sparsification curves and the calibration histogram -----------------------------------
  * The device side of evaluate_uncertainty / sp_plot / CalibrationCurve of utils/flow_utils.py:186-320 (DESIGN.md section

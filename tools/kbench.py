@@ -3,6 +3,7 @@
 fraction of the 8 TB/s HBM roofline.  Calls the C ABI directly (no autograd overhead).
 
     python tools/kbench.py [--iters 50] [--filter corr] [--levels uflow|pwclite]
+    python tools/kbench.py --filter gauss_pyr      # the pyramid sampler node and an ElboLoss step
 """
 import argparse
 import json
@@ -433,6 +434,105 @@ def out_up_bench(dev, g, B2=8, launches=30, repeats=5):
     report('tail %s' % [B2, C, h, w], res, {'fwd': 21 * n, 'bwd': 21 * n})
 
 
+def gauss_pyr_bench(dev, g, B=8, H=384, W=640, launches=30, repeats=5):
+    """the pyramid sampler node (arflow_amd.gauss_pyr.reparam_pyramid: one launch for all scales and both
+    directions, one fold launch, one adjoint launch) at the five scales of a 384 x 640 pair with B = 8 -- 384 x 640 ... 24 x 40,
+    the upsampled outputs of PWCLiteProb -- next to the reference's formulation restated in torch ops (per scale and direction
+    slice, repeat, exp, mul, add; the two channel sums and means of the entropy; cat; and ATen's autograd of all that), and
+    one whole ElboLoss step (forward + backward to the nets) next to unFlowLoss fed by torch-made samples.  HIP events around
+    `launches` calls after 5 warm-ups, the versions in alternation, `repeats` rounds: median (min .. max)."""
+    import statistics
+    from arflow_amd.config import AttrDict
+    from arflow_amd.gauss_pyr import reparam_pyramid
+    from arflow_amd.losses import get_loss
+    from arflow_amd.losses.flow_loss import unFlowLoss
+    from arflow_amd.train_step import WORKLOADS, synthetic_pairs
+    sizes = [(H >> k, W >> k) for k in range(5)]
+    nets = [(0.5 * torch.randn(B, 8, h, w, device=dev, generator=g)).requires_grad_(True) for h, w in sizes]
+    eps = [torch.randn(B, 4, h, w, device=dev, generator=g) for h, w in sizes]
+    gz = [torch.randn(B, 4, h, w, device=dev, generator=g) for h, w in sizes]
+    gent = torch.randn(5, 2, device=dev, generator=g, dtype=torch.float64)
+
+    def torch_node(nets):
+        zs, ents = [], []
+        for net, e in zip(nets, eps):
+            parts = []
+            for d in (0, 1):
+                mean, lv = net[:, 4 * d:4 * d + 2].repeat(1, 1, 1, 1), net[:, 4 * d + 2:4 * d + 4].repeat(1, 1, 1, 1)
+                parts.append(mean + torch.exp(lv / 2.0) * e[:, 2 * d:2 * d + 2])
+                ents.append(torch.sum(net[:, 4 * d + 2:4 * d + 4], dim=1).sum())
+            zs.append(torch.cat(parts, 1))
+        return zs, torch.stack(ents).view(5, 2)
+
+    def objective(zs, ent):
+        return sum((z * w).sum() for z, w in zip(zs, gz)) + (ent.double() * gent).sum()
+
+    def spread(fns, tag):
+        t = {name: [] for name in fns}
+        for _ in range(repeats):
+            for name, fn in fns.items():
+                t[name].append(timeit(fn, launches))
+                MANIFEST[-1].update(name='gauss_pyr/' + name, shape=[])
+        for name, v in t.items():
+            print('gauss_pyr %-28s %-22s %9.1f us (%.1f .. %.1f)' % (tag, name, statistics.median(v), min(v), max(v)), flush=True)
+        return t
+
+    def hip_fwd():
+        with torch.no_grad():
+            reparam_pyramid(nets, eps)
+
+    def aten_fwd():
+        with torch.no_grad():
+            torch_node(nets)
+    zh, eh = reparam_pyramid(nets, eps)
+    za, ea = torch_node(nets)
+    oh, oa = objective(zh, eh), objective(za, ea)
+    spread({'kernels fwd': hip_fwd, 'torch fwd': aten_fwd,
+            'kernels bwd': lambda: torch.autograd.grad(oh, nets, retain_graph=True),
+            'torch bwd': lambda: torch.autograd.grad(oa, nets, retain_graph=True)}, 'node %s x5' % [B, 8, H, W])
+    n = sum(B * h * w for h, w in sizes)
+    print('gauss_pyr algorithmic bytes: fwd %d (8 + 4 read, 4 written per pixel), bwd %d (8 + 4 + 4 read, 8 written)'
+          % (4 * 16 * n, 4 * 24 * n))
+    # the align_corners=True upsample alone, at the model's finest level with 2B = 16: the x4 of the state and the x2 of the
+    # log-variance, next to the composed ATen expression the model keeps for CPU tensors
+    import math
+    import torch.nn.functional as F
+    from arflow_amd import functional as AF
+    for f, C, nf, nd, h, w in ((4, 4, 2, 2, H // 4, W // 4), (2, 2, 0, 2, H // 8, W // 8)):
+        bias = 2 * math.log(f)
+        x = torch.randn(2 * B, C, h, w, device=dev, generator=g).requires_grad_(True)
+        go = torch.randn(2 * B, C, f * h, f * w, device=dev, generator=g)
+
+        def composed(t):
+            up = lambda v: F.interpolate(v, scale_factor=f, mode='bilinear', align_corners=True)  # noqa: E731
+            parts = ([up(t[:, :nf] * f)] if nf else []) + [up(t[:, nf:nf + nd] + bias)]
+            return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+        yk, ya = AF.prob_upsample(x, f, nf, nd, bias), composed(x)
+
+        def kfwd():
+            with torch.no_grad():
+                AF.prob_upsample(x, f, nf, nd, bias)
+
+        def afwd():
+            with torch.no_grad():
+                composed(x)
+        spread({'kernels fwd': kfwd, 'ATen fwd': afwd,
+                'kernels bwd': lambda: torch.autograd.grad(yk, x, go, retain_graph=True),
+                'ATen bwd': lambda: torch.autograd.grad(ya, x, go, retain_graph=True)}, 'prob_upsample x%d %s' % (f, [2 * B, C, h, w]))
+    lcfg = AttrDict(WORKLOADS['pwcliteprob+elbo_loss'][1])
+    elbo, plain = get_loss(lcfg), unFlowLoss(lcfg)
+    img = synthetic_pairs(B, H, W, device=dev, seed=3)
+
+    def elbo_step():
+        torch.autograd.grad(elbo(nets, img, eps=eps)[0], nets)
+
+    def torch_step():
+        zs, ent = torch_node(nets)
+        coef = torch.tensor([[0.1 / (B * h * w) / 4] * 2 for h, w in sizes], device=dev)
+        torch.autograd.grad(plain(zs, img)[0] - (ent * coef).sum(), nets)
+    spread({'ElboLoss step': elbo_step, 'unFlowLoss + torch samples': torch_step}, 'loss %s' % [B, 6, H, W])
+
+
 def main():
     if os.environ.get('ARFLOW_LIB_PATH'):  # an alternative build of the library (A/B timing; tools only)
         _lib.LIB_PATH = os.environ['ARFLOW_LIB_PATH']
@@ -769,6 +869,8 @@ def main():
         band_bench(dev, g)
     if want('out_up'):  # the probabilistic model's output upsample (csrc/out_up.hip) against the composed ATen path
         out_up_bench(dev, g)
+    if want('gauss_pyr'):  # the pyramid sampler node and one ElboLoss step (csrc/gauss_pyr.hip) against the torch formulation
+        gauss_pyr_bench(dev, g)
     if args.manifest:
         json.dump(MANIFEST, open(args.manifest, 'w'), indent=1)
     if not rows:  # only ops that keep their own byte model (the head convolutions) were selected
