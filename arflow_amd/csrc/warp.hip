@@ -478,6 +478,9 @@ __device__ __forceinline__ void run_pitch(float* __restrict__ win, const TS* __r
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < CCH; ++c) {
+      // a short last chunk: window_store left this plane alone -- the previous chunk's values, or, when C < CCH, whatever
+      // LDS held before the launch (a NaN there times the zero gradient fetch_g supplies is a NaN)
+      if (c0 + c >= C) continue;
       const float* w = win + c * HMAX * WP;
       float s[4], sx, sy;
       tap_select(p, w, wd.l, s);

@@ -277,6 +277,7 @@ def test_resample_family_golden(golden):
 @pytest.mark.parametrize('cfg', [(2, 32, 48, 80, 'zeros', True), (1, 64, 24, 40, 'border', True),
                                  (2, 3, 96, 160, 'border', False), (1, 16, 31, 57, 'zeros', False)])
 def test_flow_warp_vs_oracle(AF, oracle, cfg):
+    """max-abs against the fp32 oracle; the per-pixel statement with derived bounds on every launch path is tests/test_warp_gpu.py"""
     B, C, H, W, pad, ac = cfg
     gen = torch.Generator().manual_seed(H * W)
     x = torch.randn(B, C, H, W, generator=gen)
