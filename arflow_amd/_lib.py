@@ -122,6 +122,10 @@ PROTOTYPES = {
     'arflow_gauss_pyr_work_size': [c_fp, c_fp, c_i, c_i],
     'arflow_gauss_pyr_sample_fwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_fp],
     'arflow_gauss_pyr_sample_bwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_fp],
+    'arflow_mse_work_size': [c_i, c_i, c_i],
+    'arflow_mse_fwd': [c_fp, c_l, c_i, c_fp, c_l, c_i, c_i, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp],
+    'arflow_mse_bwd': [c_fp, c_l, c_i, c_fp, c_l, c_i, c_i, c_fp, c_l, c_fp, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_resize_flow': [c_fp, c_l, c_i, c_i, c_fp, c_l, c_i, c_i, c_i, c_i, c_fp],
     'arflow_uncert_rows': [c_i, c_i],
     'arflow_uncert_prep': [c_fp, c_fp, c_fp, c_l, c_fp, c_fp, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_sparsify_sums': [c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp],

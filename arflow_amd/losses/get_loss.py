@@ -1,8 +1,9 @@
-"""losses/get_loss.py:9-24 for the loss types on the hot path and the ELBO objectives of the probabilistic families (DESIGN.md
-sections 21 and 27; the MSE research losses are out of scope)."""
+"""losses/get_loss.py:9-24: every loss type of the reference -- 'unflow', 'elbo', 'fullres', 'uflow', 'uflow_elbo' and the
+supervised 'mse' (DESIGN.md sections 21, 27 and 28) -- and the build-defined 'mv'."""
 from .elbo_loss import ElboLoss
 from .flow_loss import unFlowLoss
 from .fullres_loss import FullResLoss
+from .mse_loss import MseLoss
 from .mv_loss import MvLoss
 from .uflow_elbo_loss import UFlowElboLoss
 from .uflow_loss import UFlowLoss
@@ -19,6 +20,8 @@ def get_loss(cfg):
         return UFlowLoss(cfg)
     if cfg.type == 'uflow_elbo':
         return UFlowElboLoss(cfg)
+    if cfg.type == 'mse':
+        return MseLoss(cfg)
     if cfg.type == 'mv':  # build-defined 3-frame objective; not a reference type
         return MvLoss(cfg)
     raise NotImplementedError(cfg.type)

@@ -64,6 +64,13 @@ WORKLOADS = {
              closed_form_smooth=False, data_loss=['census'], data_weight=[1.0], data_penalty=['abs_robust_loss'],
              w_entropy=0.3, w_oof=0.0, w_occ=0.0, with_bk=True, approx='mixture', n_components=2, inv_cov=False,
              approx_entropy=False, occ_type='sample', n_samples=6, offdiag_reg=0.0, natural_grad=False)),
+    # configs/chairs_uflow_mse.json:8-22: the supervised objective on the level-2 output of PWCProbFlow (out_channels 8 =
+    # mean, log-diagonal and the 4-neighbour coefficients of a precision factor); the step takes a ground-truth flow
+    'pwcprobflow+mse_loss': (
+        dict(type='uflow_prob', feature_norm=True, level_dropout=0.1, out_channels=[2, 2, 4], inv_cov=True, n_pyramids=1,
+             mixture_weights=False),
+        dict(type='mse', w_mse=1.0, w_entropy=0.1, diag=False, diag_dominant=False, inv_cov=True, approx_entropy=False,
+             offdiag_reg=1000.0, n_samples=1)),
 }
 
 
@@ -73,6 +80,15 @@ def synthetic_pairs(batch, height, width, frames=2, device='cuda', seed=0):
     x = torch.rand(batch, 3 * frames, height, width, generator=g)
     x = torch.nn.functional.avg_pool2d(torch.nn.functional.pad(x, (2, 2, 2, 2), mode='reflect'), 5, 1)
     return x.to(device)
+
+
+def synthetic_flow(batch, height, width, device='cuda', seed=0):
+    """A smooth ground-truth flow of a few pixels for the supervised workloads: N(0, 1) on a grid 16 times coarser, resized
+    bilinearly and scaled by 4."""
+    g = torch.Generator(device='cpu').manual_seed(seed)
+    coarse = torch.randn(batch, 2, max(height // 16, 1), max(width // 16, 1), generator=g)
+    flow = 4.0 * torch.nn.functional.interpolate(coarse, (height, width), mode='bilinear', align_corners=True)
+    return flow.to(device)
 
 
 class TrainStep:
@@ -102,8 +118,17 @@ class TrainStep:
         except (TypeError, RuntimeError):
             self.opt = torch.optim.Adam(self.model.parameters(), **kw)
         self.last = None
+        self._target = None
 
-    def __call__(self, img_pair):
+    def __call__(self, img_pair, target=None):
+        if self.loss_cfg.type == 'mse':  # supervised: the forward direction alone against the ground-truth flow
+            if target is None:  # a seeded synthetic flow of the batch's shape, made once
+                shape = (img_pair.shape[0],) + tuple(img_pair.shape[2:])
+                if self._target is None or self._target[0] != shape:
+                    self._target = (shape, synthetic_flow(*shape, device=img_pair.device, seed=7))
+                target = self._target[1]
+            res = self.model(img_pair[:, :3], img_pair[:, 3:], with_bk=False)
+            return self._step(self.loss(res['flows_fw'], target))
         if self.loss_cfg.type == 'uflow_elbo':  # trainer/uflow_elbo_trainer.py: the model and the loss take the two frames
             res = self.model(img_pair[:, :3], img_pair[:, 3:], with_bk=True)
             out = self.loss(res, img_pair[:, :3], img_pair[:, 3:])

@@ -57,6 +57,13 @@ def downsample(img, is_flow, scale_factor=2.0):
     return out * (1 / scale_factor) if is_flow else out
 
 
+def resize_flow(flow, new_shape, align_corners=False):
+    """utils/flow_utils.py:110-118 -- bilinear resize of a [B,2,H,W] flow to new_shape = (h, w), its components rescaled to
+    the new size; one launch (csrc/mse.hip), no autograd."""
+    from .mse import resize_flow as _resize_flow
+    return _resize_flow(flow, new_shape, align_corners)
+
+
 def image_grads(image_batch, stride=1):
     """utils/uflow_utils.py:207-210."""
     return (image_batch[:, :, :, stride:] - image_batch[:, :, :, :-stride],

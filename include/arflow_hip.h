@@ -715,6 +715,40 @@ int arflow_gauss_pyr_sample_bwd(const float* const* gz, const long* gz_bs, const
                                 const float* const* eps, const long* eps_bs, const double* gent, float* const* gnet,
                                 const long* gnet_bs, const int* h, const int* w, int n, int B, arflow_stream_t stream);
 
+/* ---- MseLoss: squared error against the resized ground-truth flow --------------------------
+ * losses/mse_loss.py:9-148 and resize_flow of utils/flow_utils.py:110-118.  fp32, planes contiguous, each tensor with its
+ * own batch stride in floats (read only when it has more than one item): channel slices are passed in place.
+ *   net [B][C][h][w]: mean 0:2, log_diag 2:4, and in mode 2 left 4:6 (without its last column) and over 6:8 (without its
+ *   last row);  target [B][2][H][W], any H, W >= 1;  ez [S B][2][h][w], sample s of item b at index s B + b.
+ *   mode 0: ez is the noise, z = mean + RN(expf(log_diag) ez);  mode 1: z = mean + RN(expf(-log_diag) ez);
+ *   mode 2: ez IS z (written by the 4-neighbour samplers).  align_corners 0 / 1: the taps of the bilinear resize.
+ * gt = resize_flow(target, (h, w)): the source coordinate in float64, the weights rounded to fp32 once, ATen's fp32 blend,
+ * the division by W / w (channel 0) and H / h (channel 1) in float64 rounded once.  r = z - gt in fp32.
+ * arflow_mse_fwd: sums [4] (float64, device) = { sum r^2 over all S B 2 h w elements, sum log_diag over B 2 h w, sum left^2,
+ *   sum over^2 (both 0 in modes 0 and 1) }, accumulated in float64 from r / the load on: per lane, by wave butterfly, in wave
+ *   order, one row of 4 partials per workgroup in work (arflow_mse_work_size(B, h, w) doubles, < 0: the ARFLOW_E* code; need
+ *   not be initialised), folded in a fixed order by a second one-wave launch of the same call.  z is never stored.
+ * arflow_mse_bwd, one launch; gsums [4] (float64, DEVICE) is the gradient with respect to sums.  With c = (float)(2 gsums[0]),
+ *   ge = (float)gsums[1], gz = c r:
+ *   modes 0, 1: gnet[:, 0:2] = sum_s gz, gnet[:, 2:4] = sum_s gz (+- RN(std ez)) + ge (minus in mode 1), channels 4.. zero;
+ *               gz may be NULL;
+ *   mode 2:     gz [S B][2][h][w] = c r (required), gnet[:, 0:2] = 0, [:, 2:4] = ge, [:, 4:6] = (float)(2 gsums[2]) left,
+ *               [:, 6:8] = (float)(2 gsums[3]) over (zero in the column / row the slices leave out), channels 8.. zero.
+ * arflow_resize_flow: out [B][2][h][w] = gt alone.
+ * No atomics: the same bits in either mode.  Every element of every output is stored.
+ * ARFLOW_ENULL: a required pointer is NULL;  ARFLOW_EPARAM: mode outside 0..2, align_corners outside 0 / 1, an output that
+ * overlaps an input or another output;  ARFLOW_ESHAPE: B, S, h, w, H or W < 1, S B > 65535 (B > 65535 for the resize), a plane
+ * of 2^30 or more elements, C < 4 (C < 8, h < 2 or w < 2 in mode 2), a batch stride smaller than its item. */
+long arflow_mse_work_size(int B, int h, int w);
+int arflow_mse_fwd(const float* net, long net_bs, int C, const float* target, long target_bs, int H, int W, const float* ez,
+                   long ez_bs, int B, int S, int h, int w, int mode, int align_corners, double* work, double* sums,
+                   arflow_stream_t stream);
+int arflow_mse_bwd(const float* net, long net_bs, int C, const float* target, long target_bs, int H, int W, const float* ez,
+                   long ez_bs, const double* gsums, float* gnet, long gnet_bs, float* gz, long gz_bs, int B, int S, int h, int w,
+                   int mode, int align_corners, arflow_stream_t stream);
+int arflow_resize_flow(const float* flow, long flow_bs, int H, int W, float* out, long out_bs, int B, int h, int w,
+                       int align_corners, arflow_stream_t stream);
+
 /* ---- uncertainty metrics: sparsification curves and the calibration histogram -----------------------------------
  * The device side of evaluate_uncertainty / sp_plot / CalibrationCurve of utils/flow_utils.py:186-320 (DESIGN.md section
  * 19).  The `rows` conventions of arflow_flow_eval hold for all three: a row buffer need not be initialised, every row is

@@ -4,6 +4,7 @@ fraction of the 8 TB/s HBM roofline.  Calls the C ABI directly (no autograd over
 
     python tools/kbench.py [--iters 50] [--filter corr] [--levels uflow|pwclite]
     python tools/kbench.py --filter gauss_pyr      # the pyramid sampler node and an ElboLoss step
+    python tools/kbench.py --filter mse            # one MseLoss step, fused against composed ATen ops
 """
 import argparse
 import json
@@ -533,6 +534,75 @@ def gauss_pyr_bench(dev, g, B=8, H=384, W=640, launches=30, repeats=5):
     spread({'ElboLoss step': elbo_step, 'unFlowLoss + torch samples': torch_step}, 'loss %s' % [B, 6, H, W])
 
 
+def mse_bench(dev, g, B=16, h=96, w=128, H=384, W=512, launches=30, repeats=5):
+    """one MseLoss step -- forward plus backward to the level-2 output -- at 16 x (96 x 128 from 384 x 512),
+    S = 1 and S = 4, for a diagonal mode (inv_cov) and the shipped 4-neighbour inv_cov mode, next to the reference's formulation
+    composed of ATen ops on the same GPU (losses/mse_loss.py:60-148: interpolate, two in-place divides, repeats, exp, mul, add,
+    sub, square, mean, sum, mean; the 4-neighbour solve is BackwardSubst in both versions).  HIP events around `launches` steps
+    after 5 warm-ups, the versions in alternation, `repeats` rounds: median (min .. max); GPU kernels per step counted by
+    torch.profiler where it is available."""
+    import statistics
+    import torch.nn.functional as F
+    from arflow_amd.config import AttrDict
+    from arflow_amd.losses import get_loss
+    from arflow_amd.triag_solve import BackwardSubst
+    net = torch.randn(B, 8, h, w, device=dev, generator=g)
+    net[:, 2:4] = 0.5 * net[:, 2:4] - 1.0
+    net[:, 4:8] = 0.3 * torch.rand(B, 4, h, w, device=dev, generator=g) - 0.15
+    net.requires_grad_(True)
+    target = 3.0 * torch.randn(B, 2, H, W, device=dev, generator=g)
+
+    def composed(cfg, eps):
+        S = cfg.n_samples
+        mean, ld = net[:, 0:2], net[:, 2:4]
+        off = 0
+        if cfg.diag:
+            z = mean.repeat(S, 1, 1, 1) + torch.exp(-ld.repeat(S, 1, 1, 1)) * eps
+        else:
+            left, over = net[:, 4:6, :, :-1], net[:, 6:8, :-1, :]
+            off = cfg.offdiag_reg * (torch.mean(torch.square(left)) + torch.mean(torch.square(over))) / 2.0
+            rep = lambda t: t.repeat(S, 1, 1, 1)  # noqa: E731
+            z = rep(mean) + BackwardSubst.apply(rep(torch.exp(ld)), rep(left), rep(over), None, eps)
+        ent = -cfg.w_entropy * torch.sum(ld, dim=1).mean()
+        gt = F.interpolate(target, (h, w), mode='bilinear', align_corners=False)
+        gt[:, 0] /= W / float(w)
+        gt[:, 1] /= H / float(h)
+        return cfg.w_mse * torch.mean(torch.square(z - gt.repeat(S, 1, 1, 1))) - ent + off
+
+    def kernels_per_step(fn):
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            fn()
+            torch.cuda.synchronize()
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                fn()
+                torch.cuda.synchronize()
+            return sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA'))
+        except Exception as e:  # the profiler is an extra: the timings do not depend on it
+            return 'n/a (%s)' % type(e).__name__
+
+    for diag in (True, False):
+        for S in (1, 4):
+            cfg = AttrDict(type='mse', w_mse=1.0, w_entropy=0.1, diag=diag, diag_dominant=False, inv_cov=True,
+                           approx_entropy=False, offdiag_reg=1000.0, n_samples=S)
+            loss = get_loss(cfg)
+            eps = torch.randn(S * B, 2, h, w, device=dev, generator=g)
+            fns = {'fused step': lambda: torch.autograd.grad(loss([None, None, net], target, eps=eps)[0], net),
+                   'composed ATen step': lambda: torch.autograd.grad(composed(cfg, eps), net)}
+            a, b = float(loss([None, None, net], target, eps=eps)[0].detach()), float(composed(cfg, eps).detach())
+            t = {name: [] for name in fns}
+            for _ in range(repeats):
+                for name, fn in fns.items():
+                    t[name].append(timeit(fn, launches))
+                    MANIFEST[-1].update(name='mse/' + name, shape=[])
+            tag = '%s inv_cov S=%d %s<-%s' % ('diag' if diag else '4-neighbour', S, [B, h, w], [H, W])
+            for name, v in t.items():
+                print('mse %-44s %-20s %9.1f us (%.1f .. %.1f)  GPU kernels per step: %s'
+                      % (tag, name, statistics.median(v), min(v), max(v), kernels_per_step(fns[name])), flush=True)
+            print('mse %-44s composed / fused = %.2f   (loss %.6f fused, %.6f composed)'
+                  % (tag, statistics.median(t['composed ATen step']) / statistics.median(t['fused step']), a, b), flush=True)
+
+
 def main():
     if os.environ.get('ARFLOW_LIB_PATH'):  # an alternative build of the library (A/B timing; tools only)
         _lib.LIB_PATH = os.environ['ARFLOW_LIB_PATH']
@@ -871,6 +941,8 @@ def main():
         out_up_bench(dev, g)
     if want('gauss_pyr'):  # the pyramid sampler node and one ElboLoss step (csrc/gauss_pyr.hip) against the torch formulation
         gauss_pyr_bench(dev, g)
+    if want('mse'):  # one MseLoss step on the fused residual kernels (csrc/mse.hip) against the composed ATen formulation
+        mse_bench(dev, g)
     if args.manifest:
         json.dump(MANIFEST, open(args.manifest, 'w'), indent=1)
     if not rows:  # only ops that keep their own byte model (the head convolutions) were selected
