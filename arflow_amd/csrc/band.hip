@@ -177,7 +177,6 @@ inline int check_dims(int B, int S, int M, int N) {
   return ARFLOW_OK;
 }
 // a batch stride is read only when there is a second item
-inline bool stride_ok(long stride, long count, long need) { return count <= 1 || stride >= need; }
 
 }  // namespace
 
@@ -208,9 +207,9 @@ extern "C" int arflow_band_mv_fwd(const float* mean, long mean_bs, const float* 
   const int rc = check_dims(B, S, M, N);
   if (rc != ARFLOW_OK) return rc;
   const long pl = 2L * M * N, ntap = (long)(k + 1) * (k + 1);
-  AF_REQUIRE(stride_ok(diag_bs, B, pl) && (k == 0 || stride_ok(off_bs, B, (ntap - 1) * pl)) &&
-                 (!mean || stride_ok(mean_bs, B, pl)) && stride_ok(x_bs, (long)S * B, pl) &&
-                 stride_ok(y_bs, (long)S * B, pl),
+  AF_REQUIRE(af_stride_ok(diag_bs, B, pl) && (k == 0 || af_stride_ok(off_bs, B, (ntap - 1) * pl)) &&
+                 (!mean || af_stride_ok(mean_bs, B, pl)) && af_stride_ok(x_bs, (long)S * B, pl) &&
+                 af_stride_ok(y_bs, (long)S * B, pl),
              ARFLOW_ESHAPE);
   BAND_DISPATCH(band_fwd_kernel, mean, mean_bs, diag, diag_bs, off, off_bs, X, x_bs, Y, y_bs, B, S, M, N);
   return af_launch_status();
@@ -233,10 +232,10 @@ extern "C" int arflow_band_mv_bwd(const float* diag, long diag_bs, const float* 
   const int rc = check_dims(B, S, M, N);
   if (rc != ARFLOW_OK) return rc;
   const long pl = 2L * M * N, ntap = (long)(k + 1) * (k + 1);
-  AF_REQUIRE(stride_ok(diag_bs, B, pl) && stride_ok(gdiag_bs, B, pl) &&
-                 (k == 0 || (stride_ok(off_bs, B, (ntap - 1) * pl) && stride_ok(goff_bs, B, (ntap - 1) * pl))) &&
-                 (!gmean || stride_ok(gmean_bs, B, pl)) && stride_ok(x_bs, (long)S * B, pl) &&
-                 stride_ok(gy_bs, (long)S * B, pl) && (!gX || stride_ok(gx_bs, (long)S * B, pl)),
+  AF_REQUIRE(af_stride_ok(diag_bs, B, pl) && af_stride_ok(gdiag_bs, B, pl) &&
+                 (k == 0 || (af_stride_ok(off_bs, B, (ntap - 1) * pl) && af_stride_ok(goff_bs, B, (ntap - 1) * pl))) &&
+                 (!gmean || af_stride_ok(gmean_bs, B, pl)) && af_stride_ok(x_bs, (long)S * B, pl) &&
+                 af_stride_ok(gy_bs, (long)S * B, pl) && (!gX || af_stride_ok(gx_bs, (long)S * B, pl)),
              ARFLOW_ESHAPE);
   BAND_DISPATCH(band_bwd_kernel, diag, diag_bs, off, off_bs, X, x_bs, gY, gy_bs, gX, gx_bs, gmean, gmean_bs, gdiag, gdiag_bs,
                 goff, goff_bs, B, S, M, N);

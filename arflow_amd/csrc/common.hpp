@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <type_traits>
 
 #include "../../include/arflow_hip.h"
@@ -77,8 +78,23 @@ static inline unsigned af_blocks_per_sample(int B, long n, int floats_per_block)
   return (unsigned)(nb < 1 ? 1 : nb);
 }
 
-// Sum over the 64 lanes of a wave; every lane gets the total.
+// The plane layout the family launchers take: rows, planes and channels dense, `count` items
+// `stride` floats apart.  af_stride_ok: the items do not overlap (`need` floats each).
+static inline bool af_stride_ok(long stride, long count, long need) { return count <= 1 || stride >= need; }
+// true for nullptr: optional pointers pass through it
+static inline bool af_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// every item starts on a float4 boundary: what a VEC kernel needs besides a plane that is a multiple of 4 floats
+static inline bool af_vec4_ok(const void* p, long stride, long count) {
+  return af_aligned16(p) && (count <= 1 || stride % 4 == 0);
+}
+
+// Sum over the 64 lanes of a wave by a butterfly with xor offsets 32, 16, ..., 1 (a fixed tree); every lane gets the total.
 __device__ __forceinline__ float af_wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, AF_WAVE);
+  return v;
+}
+__device__ __forceinline__ double af_wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, AF_WAVE);
   return v;
@@ -103,6 +119,58 @@ __device__ __forceinline__ void af_block_sum(float (&v)[NV], float* scratch) {
       for (int w = 0; w < nw; ++w) s += scratch[k * nw + w];
       v[k] = s;
     }
+  }
+}
+
+// Block-wide float64 sum of NV values per thread of an NT-thread workgroup, result valid in thread 0.  `scratch` needs
+// NV * NT / 64 doubles of LDS.  All threads must call.  The ORDER is part of the contract (stored float64 partials keep
+// their bits across kernels and releases): the lanes of a wave by the butterfly of af_wave_sum (xor offsets 32, 16, ..., 1),
+// then the waves 0 .. NT / 64 - 1 in index order, added to 0.0 (so a sum whose every wave partial is -0.0 comes out +0.0).
+// The butterfly is written out, not a call of af_wave_sum: with the call the hot-path kernels that use this (warp.hip,
+// level_small.hip, featnorm.hip) compile to another schedule.
+template <int NV, int NT>
+__device__ __forceinline__ void af_block_sum_f64(double (&v)[NV], double* scratch) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) scratch[k * (NT / 64) + wave] = v[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      double s = 0.0;
+      for (int w = 0; w < NT / 64; ++w) s += scratch[k * (NT / 64) + w];
+      v[k] = s;
+    }
+  }
+}
+
+// Four consecutive floats of a plane row starting at column X0: loaded with `fill` beyond W, stored up to W.  VEC: W % 4 == 0
+// and the plane 16-byte aligned (host-checked), so X0 < W implies X0 + 3 < W and the address is aligned.
+template <bool VEC>
+__device__ __forceinline__ void af_ld_cols4(const float* __restrict__ row, int X0, int W, float fill, float (&v)[4]) {
+  if (VEC) {
+    const float4 t = X0 < W ? *reinterpret_cast<const float4*>(row + X0) : make_float4(fill, fill, fill, fill);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = X0 + j < W ? row[X0 + j] : fill;
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void af_st_cols4(float* __restrict__ row, int X0, int W, const float (&v)[4]) {
+  if (VEC) {
+    if (X0 < W) *reinterpret_cast<float4*>(row + X0) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (X0 + j < W) row[X0 + j] = v[j];
   }
 }
 

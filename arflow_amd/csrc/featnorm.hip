@@ -36,7 +36,7 @@ using featnorm::moments_of;
 using featnorm::sum_rows;
 template <int NV, int NTH = NT>
 __device__ __forceinline__ void block_sum_f64(double (&v)[NV], double* scratch) {
-  featnorm::block_sum_f64<NV, NTH>(v, scratch);
+  af_block_sum_f64<NV, NTH>(v, scratch);
 }
 
 // grid (blocks per sample, B).  acc[b] += (sum x1, sum x1^2, sum x2, sum x2^2) of this block's slice.

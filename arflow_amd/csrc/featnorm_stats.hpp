@@ -84,28 +84,4 @@ __device__ __forceinline__ Moments moments_of(const MomentSrc& m, int b, long n,
   return moments_from_totals(a, n, mode);
 }
 
-// sum over the block of NV doubles per thread; result in thread 0.  scratch: NV * NTH / 64 doubles.
-template <int NV, int NTH>
-__device__ __forceinline__ void block_sum_f64(double (&v)[NV], double* scratch) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) scratch[k * (NTH / 64) + wave] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      double s = 0.0;
-      for (int w = 0; w < NTH / 64; ++w) s += scratch[k * (NTH / 64) + w];
-      v[k] = s;
-    }
-  }
-}
-
 }  // namespace featnorm

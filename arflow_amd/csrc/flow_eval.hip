@@ -18,30 +18,16 @@
 // buffer is stored by exactly one workgroup -- no atomics, no zero-fill, bitwise reproducible.  Partials are fp32 per
 // thread over its 8 pixels and double from the wave reduction on (as featnorm.hip).
 #include "common.hpp"
-#include "featnorm_stats.hpp"
 #include "taps.hpp"
 
 namespace {
 
 constexpr int NT = 256;            // threads per workgroup
 constexpr int TW = 64, TH = 32;    // tile of ground-truth pixels
-constexpr int CPT = 4;             // consecutive columns per thread (one float4)
+constexpr int CPT = 4;             // consecutive columns per thread (one float4: af_ld_cols4 / af_st_cols4, zeros beyond W)
 constexpr int RSTEP = NT / (TW / CPT);  // tile rows per pass of the workgroup: 16
 constexpr int NQ = 7;              // quantities summed (column 7 of a row is 0)
 constexpr int MAX_DIM = 16384;
-
-// four consecutive floats of a plane row starting at column X0 (zeros beyond W); VEC: W % 4 == 0 and the plane 16-byte
-// aligned, so X0 < W implies X0 + 3 < W and the address is aligned
-template <bool VEC>
-__device__ __forceinline__ void ld_cols(const float* __restrict__ row, int X0, int W, float (&v)[CPT]) {
-  if (VEC) {
-    const float4 t = X0 < W ? *reinterpret_cast<const float4*>(row + X0) : make_float4(0.f, 0.f, 0.f, 0.f);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < CPT; ++j) v[j] = X0 + j < W ? row[X0 + j] : 0.f;
-  }
-}
 
 // grid (tile columns, tile rows, B)
 template <bool VEC>
@@ -74,17 +60,17 @@ __global__ __launch_bounds__(NT) void flow_eval_kernel(const float* __restrict__
     up_source(Y, h, H, fh / fH, false, ya, yb, wy0, wy1);
     const float* gr = g + (long)Y * W;
     float gu[CPT], gv[CPT], va[CPT], no[CPT], mo[CPT], epe[CPT];
-    ld_cols<VEC>(gr, X0, W, gu);
-    ld_cols<VEC>(gr + HW, X0, W, gv);
+    af_ld_cols4<VEC>(gr, X0, W, 0.f, gu);
+    af_ld_cols4<VEC>(gr + HW, X0, W, 0.f, gv);
     if (C == 4) {
-      ld_cols<VEC>(gr + 2 * HW, X0, W, va);
-      ld_cols<VEC>(gr + 3 * HW, X0, W, no);
+      af_ld_cols4<VEC>(gr + 2 * HW, X0, W, 0.f, va);
+      af_ld_cols4<VEC>(gr + 3 * HW, X0, W, 0.f, no);
     } else {
 #pragma unroll
       for (int j = 0; j < CPT; ++j) va[j] = no[j] = X0 + j < W ? 1.f : 0.f;
     }
     if (mv) {
-      ld_cols<VEC>(mv + (long)Y * W, X0, W, mo);
+      af_ld_cols4<VEC>(mv + (long)Y * W, X0, W, 0.f, mo);
     } else {
 #pragma unroll
       for (int j = 0; j < CPT; ++j) mo[j] = 0.f;
@@ -114,20 +100,12 @@ __global__ __launch_bounds__(NT) void flow_eval_kernel(const float* __restrict__
       s[5] += e * mo[j];
       s[6] += va[j] * mo[j];
     }
-    if (em) {
-      if (VEC) {
-        if (X0 < W) *reinterpret_cast<float4*>(em + (long)Y * W + X0) = make_float4(epe[0], epe[1], epe[2], epe[3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < CPT; ++j)
-          if (X0 + j < W) em[(long)Y * W + X0 + j] = epe[j];
-      }
-    }
+    if (em) af_st_cols4<VEC>(em + (long)Y * W, X0, W, epe);
   }
   double d[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) d[q] = (double)s[q];
-  featnorm::block_sum_f64<NQ, NT>(d, scratch);
+  af_block_sum_f64<NQ, NT>(d, scratch);
   if (threadIdx.x == 0) {
     const long tiles = (long)gridDim.x * gridDim.y;
     double* r = rows + 8 * (tiles * b + (long)blockIdx.y * gridDim.x + blockIdx.x);
@@ -136,8 +114,6 @@ __global__ __launch_bounds__(NT) void flow_eval_kernel(const float* __restrict__
     r[7] = 0.0;
   }
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -158,7 +134,7 @@ extern "C" int arflow_flow_eval(const float* pred, const float* gt, const float*
   AF_REQUIRE(move == nullptr || C == 4, ARFLOW_EPARAM);
   const dim3 grid(af_cdiv(W, TW), af_cdiv(H, TH), B);
   // float4 rows of the ground-truth planes (and move / epe_map): every plane starts 16-byte aligned when W % 4 == 0
-  const bool vec = W % 4 == 0 && aligned16(gt) && aligned16(move) && aligned16(epe_map);
+  const bool vec = W % 4 == 0 && af_aligned16(gt) && af_aligned16(move) && af_aligned16(epe_map);
   if (vec)
     hipLaunchKernelGGL(flow_eval_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, pred, gt, move, rows, epe_map, h, w, C,
                        H, W);

@@ -9,7 +9,7 @@
 // The two mean planes of one (b, d) are 2 h w consecutive floats, and so are its two log-variance, noise and sample planes: a
 // "row".  A workgroup takes CHUNK consecutive elements of one row of one scale; it finds the scale from the prefix table of
 // chunk counts that travels with the pointers in the kernel argument (by value: no device-side table, no copy).  Entropy: every
-// lane adds its terms in element order, the wave adds by butterfly, the waves are added in wave order, and the workgroup stores
+// lane adds its terms in element order, the workgroup adds them in the order of af_block_sum_f64 (common.hpp) and stores
 // ONE float64 partial at work[its index]; the fold kernel (one wave per (i, d)) adds the partials lane-strided in index order
 // and by butterfly.  No atomics: the same code and bits in normal and deterministic mode.  Every element of every output is
 // stored (ent by the fold, z / gnet by the map).
@@ -37,12 +37,6 @@ struct GpArgs {
   GpScale s[GP_MAX];
   int n, B;
 };
-
-__device__ __forceinline__ double gp_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, AF_WAVE);
-  return v;
-}
 
 // the sampler's standard deviation, stated once: forward and backward must agree bit for bit
 __device__ __forceinline__ float gp_std(float logvar) { return expf(logvar / 2.0f); }
@@ -100,17 +94,9 @@ __global__ __launch_bounds__(GP_NT) void gauss_pyr_sample_kernel(const GpArgs a,
   long e0;
   if (!gp_locate(a, i, b, d, e0)) return;  // (never: the grid is the sum of the chunk counts)
   const GpScale& s = a.s[i];
-  double acc = s.vec ? gp_sample_body<true>(s, b, d, e0) : gp_sample_body<false>(s, b, d, e0);
-  acc = gp_wave_sum(acc);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) part[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = part[0];
-#pragma unroll
-    for (int w = 1; w < GP_NT / AF_WAVE; ++w) t += part[w];
-    work[blockIdx.x] = t;
-  }
+  double acc[1] = {s.vec ? gp_sample_body<true>(s, b, d, e0) : gp_sample_body<false>(s, b, d, e0)};
+  af_block_sum_f64<1, GP_NT>(acc, part);
+  if (threadIdx.x == 0) work[blockIdx.x] = acc[0];
 }
 
 // grid (2 n), one wave: ent[i,d] = the partials of (i, b, d, k) over b then k
@@ -125,7 +111,7 @@ __global__ __launch_bounds__(AF_WAVE) void gauss_pyr_fold_kernel(const GpFold f,
   const double* w = work + f.first[i];
   double acc = 0.;
   for (int j = threadIdx.x; j < cnt; j += AF_WAVE) acc += w[(long)((j / nk) * 2 + d) * nk + j % nk];
-  acc = gp_wave_sum(acc);
+  acc = af_wave_sum(acc);
   if (threadIdx.x == 0) ent[blockIdx.x] = acc;
 }
 
@@ -174,9 +160,6 @@ __global__ __launch_bounds__(GP_NT) void gauss_pyr_bwd_kernel(const GpArgs a, co
     gp_bwd_body<false>(s, b, d, e0, ge);
 }
 
-inline bool gp_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline bool gp_bs4(long bs, int B) { return B == 1 || bs % 4 == 0; }
-
 // sizes -> rows, chunk counts and the prefix table; the total chunk count in *total
 inline int gp_layout(const int* h, const int* w, int n, int B, GpArgs& a, long* total) {
   AF_REQUIRE_PTR(h);
@@ -196,7 +179,6 @@ inline int gp_layout(const int* h, const int* w, int n, int B, GpArgs& a, long* 
   *total = sum;
   return ARFLOW_OK;
 }
-inline bool gp_stride_ok(long bs, int B, long need) { return B == 1 || bs >= need; }
 
 }  // namespace
 
@@ -230,12 +212,12 @@ extern "C" int arflow_gauss_pyr_sample_fwd(const float* const* net, const long* 
     AF_REQUIRE_PTR(eps[i]);
     AF_REQUIRE_PTR(z[i]);
     GpScale& s = a.s[i];
-    AF_REQUIRE(gp_stride_ok(net_bs[i], B, 4 * s.row) && gp_stride_ok(eps_bs[i], B, 2 * s.row) &&
-                   gp_stride_ok(z_bs[i], B, 2 * s.row), ARFLOW_ESHAPE);
+    AF_REQUIRE(af_stride_ok(net_bs[i], B, 4 * s.row) && af_stride_ok(eps_bs[i], B, 2 * s.row) &&
+                   af_stride_ok(z_bs[i], B, 2 * s.row), ARFLOW_ESHAPE);
     s.net = net[i], s.eps = eps[i], s.gz = nullptr, s.out = z[i];
     s.net_bs = net_bs[i], s.eps_bs = eps_bs[i], s.gz_bs = 0, s.out_bs = z_bs[i];
-    s.vec = (s.row / 2) % 4 == 0 && gp_al16(net[i]) && gp_al16(eps[i]) && gp_al16(z[i]) && gp_bs4(net_bs[i], B) &&
-            gp_bs4(eps_bs[i], B) && gp_bs4(z_bs[i], B);
+    s.vec = (s.row / 2) % 4 == 0 && af_vec4_ok(net[i], net_bs[i], B) && af_vec4_ok(eps[i], eps_bs[i], B) &&
+            af_vec4_ok(z[i], z_bs[i], B);
     f.first[i] = s.first, f.nk[i] = s.nk;
   }
   hipLaunchKernelGGL(gauss_pyr_sample_kernel, dim3((unsigned)total), dim3(GP_NT), 0, (hipStream_t)stream, a, work);
@@ -266,12 +248,12 @@ extern "C" int arflow_gauss_pyr_sample_bwd(const float* const* gz, const long* g
     AF_REQUIRE_PTR(gnet[i]);
     GpScale& s = a.s[i];
     const float* g = gz ? gz[i] : nullptr;
-    AF_REQUIRE(gp_stride_ok(net_bs[i], B, 4 * s.row) && gp_stride_ok(eps_bs[i], B, 2 * s.row) &&
-                   gp_stride_ok(gnet_bs[i], B, 4 * s.row) && (!g || gp_stride_ok(gz_bs[i], B, 2 * s.row)), ARFLOW_ESHAPE);
+    AF_REQUIRE(af_stride_ok(net_bs[i], B, 4 * s.row) && af_stride_ok(eps_bs[i], B, 2 * s.row) &&
+                   af_stride_ok(gnet_bs[i], B, 4 * s.row) && (!g || af_stride_ok(gz_bs[i], B, 2 * s.row)), ARFLOW_ESHAPE);
     s.net = net[i], s.eps = eps[i], s.gz = g, s.out = gnet[i];
     s.net_bs = net_bs[i], s.eps_bs = eps_bs[i], s.gz_bs = g ? gz_bs[i] : 0, s.out_bs = gnet_bs[i];
-    s.vec = (s.row / 2) % 4 == 0 && gp_al16(net[i]) && gp_al16(eps[i]) && gp_al16(gnet[i]) && gp_bs4(net_bs[i], B) &&
-            gp_bs4(eps_bs[i], B) && gp_bs4(gnet_bs[i], B) && (!g || (gp_al16(g) && gp_bs4(gz_bs[i], B)));
+    s.vec = (s.row / 2) % 4 == 0 && af_vec4_ok(net[i], net_bs[i], B) && af_vec4_ok(eps[i], eps_bs[i], B) &&
+            af_vec4_ok(gnet[i], gnet_bs[i], B) && (!g || af_vec4_ok(g, gz_bs[i], B));
   }
   hipLaunchKernelGGL(gauss_pyr_bwd_kernel, dim3((unsigned)total), dim3(GP_NT), 0, (hipStream_t)stream, a, gent);
   return af_launch_status();

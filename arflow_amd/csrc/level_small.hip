@@ -139,7 +139,7 @@ __global__ __launch_bounds__(NT) void fwd_kernel(FwdArgs a) {
     }
   }
   double dm[4] = {(double)mom[0], (double)mom[1], (double)mom[2], (double)mom[3]};
-  featnorm::block_sum_f64<4, NT>(dm, dscratch);
+  af_block_sum_f64<4, NT>(dm, dscratch);
   if (tid == 0) tot[0] = dm[0], tot[1] = dm[1], tot[2] = dm[2], tot[3] = dm[3];
   // zero the halo tiles and the sign words while the totals settle
   for (int i = tid; i < 2 * CCH * MAXHALO / 4; i += NT) reinterpret_cast<float4*>(xw)[i] = make_float4(0.f, 0.f, 0.f, 0.f);

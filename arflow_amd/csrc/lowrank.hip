@@ -224,7 +224,6 @@ __global__ __launch_bounds__(AF_WAVE) void lowrank_factor_kernel(const double* _
   if (lane == 0) logdet[bc] = bad ? nan : (float)(2. * sumlog);
 }
 
-inline bool stride_ok(long stride, long count, long need) { return count <= 1 || stride >= need; }
 
 inline int check_dims(int B, int S, int R, int M, int N) {
   AF_REQUIRE(R >= 1 && R <= RMAX, ARFLOW_EPARAM);
@@ -246,7 +245,8 @@ extern "C" int arflow_lowrank_sample_fwd(const float* mean, long mean_bs, const 
   const int rc = check_dims(B, S, R, M, N);
   if (rc != ARFLOW_OK) return rc;
   const long plane = (long)M * N;
-  AF_REQUIRE(stride_ok(mean_bs, B, 2 * plane) && stride_ok(std_bs, B, 2L * R * plane) && stride_ok(z_bs, (long)S * B, 2 * plane),
+  AF_REQUIRE(af_stride_ok(mean_bs, B, 2 * plane) && af_stride_ok(std_bs, B, 2L * R * plane) &&
+                 af_stride_ok(z_bs, (long)S * B, 2 * plane),
              ARFLOW_ESHAPE);
   hipLaunchKernelGGL(lowrank_sample_kernel, dim3(af_cdiv(plane, NT), 2 * B), dim3(NT), 0, (hipStream_t)stream, mean, mean_bs,
                      std, std_bs, eps, Z, z_bs, B, S, R, plane);
@@ -269,9 +269,9 @@ extern "C" int arflow_lowrank_logdet_fwd(const float* std, long std_bs, double* 
   const int rc = check_dims(B, 1, R, M, N);
   if (rc != ARFLOW_OK) return rc;
   const long plane = (long)M * N;
-  AF_REQUIRE(stride_ok(std_bs, B, 2L * R * plane), ARFLOW_ESHAPE);
+  AF_REQUIRE(af_stride_ok(std_bs, B, 2L * R * plane), ARFLOW_ESHAPE);
   const int chunks = af_cdiv(plane, CHUNK);
-  const bool vec = plane % 4 == 0 && ((uintptr_t)std & 15) == 0 && (B == 1 || std_bs % 4 == 0);
+  const bool vec = plane % 4 == 0 && af_vec4_ok(std, std_bs, B);
   const dim3 grid(chunks, 2 * B);
   if (vec)
     hipLaunchKernelGGL(lowrank_gram_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, std, std_bs, work, R, plane);
@@ -293,8 +293,8 @@ extern "C" int arflow_lowrank_bwd(const float* std, long std_bs, const float* ep
   const int rc = check_dims(B, S, R, M, N);
   if (rc != ARFLOW_OK) return rc;
   const long plane = (long)M * N;
-  AF_REQUIRE(stride_ok(std_bs, B, 2L * R * plane) && stride_ok(gstd_bs, B, 2L * R * plane) &&
-                 (!gZ || stride_ok(gz_bs, (long)S * B, 2 * plane)) && (!gmean || stride_ok(gmean_bs, B, 2 * plane)),
+  AF_REQUIRE(af_stride_ok(std_bs, B, 2L * R * plane) && af_stride_ok(gstd_bs, B, 2L * R * plane) &&
+                 (!gZ || af_stride_ok(gz_bs, (long)S * B, 2 * plane)) && (!gmean || af_stride_ok(gmean_bs, B, 2 * plane)),
              ARFLOW_ESHAPE);
   hipLaunchKernelGGL(lowrank_bwd_kernel, dim3(af_cdiv(plane, NT), 2 * B), dim3(NT), 0, (hipStream_t)stream, std, std_bs, eps,
                      gZ, gz_bs, ginv, glogdet, gmean, gmean_bs, gstd, gstd_bs, B, S, R, plane);

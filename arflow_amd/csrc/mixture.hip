@@ -14,10 +14,10 @@
 //             glog_std[b,2k+c,p] = sum_s (lambda[n] resp[n,k] (d^2 - 1) + [z == k] G[n,c,p] std[b,2k+c,p] eps[n,c,p])
 // Sampler: a workgroup owns CHUNK consecutive pixels of one sample n; the sample is formed in fp32 (exp, one product, one
 // sum: -ffp-contract=off), every term of A in float64 from there on (the difference flow - mean_k is exact in float64, 1 / std
-// is the fp32 expf(-log_std)), summed per lane, then over the wave's lanes by a butterfly, then over the four waves in wave
-// order: one float64 partial per (n, chunk, k) in the work buffer.  A second, small launch adds the partials in chunk order
-// and forms logpdf, resp and q in float64, rounded once.  A is a sum of 2 P terms of order one and resp a softmax of
-// differences of such sums: nothing across lanes or chunks is fp32.
+// is the fp32 expf(-log_std)), summed per lane, then over the workgroup in the order of af_block_sum_f64 (common.hpp): one
+// float64 partial per (n, chunk, k) in the work buffer.  A second, small launch adds the partials in chunk order and forms
+// logpdf, resp and q in float64, rounded once.  A is a sum of 2 P terms of order one and resp a softmax of differences of such
+// sums: nothing across lanes or chunks is fp32.
 // Backward: a gather, one thread per pixel of item b, loops over s and k; it recomputes the sample from eps with the
 // sampler's own fp32 expression (the same bits), does the rest in float64 and rounds every gradient element once.
 // No atomics anywhere: the same code and the same bits in normal and deterministic mode.  Every element of every output is
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(NT) void mixture_sample_kernel(const float* __restr
                                                             const long* __restrict__ comp, float* __restrict__ flow,
                                                             long flow_bs, double* __restrict__ work, int B, int S, int K,
                                                             long plane) {
-  __shared__ double part[NT / AF_WAVE][KMAX];
+  __shared__ double part[KMAX * (NT / AF_WAVE)];
   const int n = blockIdx.y, s = n / B, b = n % B;
   const int z = comp_of(comp, (long)b * S + s, K);
   const float* mb = mean + b * mean_bs;
@@ -133,20 +133,12 @@ __global__ __launch_bounds__(NT) void mixture_sample_kernel(const float* __restr
       }
     }
   }
-  // the wave's lanes by a butterfly (a fixed tree), the four waves in wave order
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  af_block_sum_f64<KMAX, NT>(acc, part);
+  if (threadIdx.x == 0) {
+    double* row = work + ((long)n * gridDim.x + blockIdx.x) * K;
 #pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off, AF_WAVE);
-    if (lane == 0) part[wave][k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    double t = part[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < NT / AF_WAVE; ++w) t += part[w][threadIdx.x];
-    work[((long)n * gridDim.x + blockIdx.x) * K + threadIdx.x] = t;
+    for (int k = 0; k < KMAX; ++k)
+      if (k < K) row[k] = acc[k];
   }
 }
 
@@ -293,17 +285,11 @@ __global__ __launch_bounds__(NT) void mixture_entropy_kernel(const float* __rest
   out[(long)b * plane + p] = (float)(acc / (double)n);
 }
 
-inline bool stride_ok(long stride, long count, long need) { return count <= 1 || stride >= need; }
-
 inline int check_dims(int B, int S, int K, int M, int N) {
   AF_REQUIRE(K >= 1 && K <= KMAX, ARFLOW_EPARAM);
   AF_REQUIRE(B >= 1 && S >= 1 && M >= 1 && N >= 1, ARFLOW_ESHAPE);
   AF_REQUIRE((long)M * N <= 0x7fffffffL && (long)S * B <= 65535, ARFLOW_ESHAPE);  // gridDim.y of the sampler
   return ARFLOW_OK;
-}
-
-inline bool aligned4(const void* ptr, long stride, long count) {
-  return ((uintptr_t)ptr & 15) == 0 && (count <= 1 || stride % 4 == 0);
 }
 
 }  // namespace
@@ -327,11 +313,11 @@ extern "C" int arflow_mixture_sample_fwd(const float* mean, long mean_bs, const 
   const int rc = check_dims(B, S, K, M, N);
   if (rc != ARFLOW_OK) return rc;
   const long plane = (long)M * N, SB = (long)S * B;
-  AF_REQUIRE(stride_ok(mean_bs, B, 2L * K * plane) && stride_ok(ls_bs, B, 2L * K * plane) && stride_ok(eps_bs, SB, 2 * plane) &&
-                 stride_ok(flow_bs, SB, 2 * plane),
+  AF_REQUIRE(af_stride_ok(mean_bs, B, 2L * K * plane) && af_stride_ok(ls_bs, B, 2L * K * plane) &&
+                 af_stride_ok(eps_bs, SB, 2 * plane) && af_stride_ok(flow_bs, SB, 2 * plane),
              ARFLOW_ESHAPE);
-  const bool vec = plane % 4 == 0 && aligned4(mean, mean_bs, B) && aligned4(log_std, ls_bs, B) && aligned4(eps, eps_bs, SB) &&
-                   aligned4(flow, flow_bs, SB);
+  const bool vec = plane % 4 == 0 && af_vec4_ok(mean, mean_bs, B) && af_vec4_ok(log_std, ls_bs, B) &&
+                   af_vec4_ok(eps, eps_bs, SB) && af_vec4_ok(flow, flow_bs, SB);
   const dim3 grid(af_cdiv(plane, CHUNK), (unsigned)SB);
   if (vec)
     hipLaunchKernelGGL(mixture_sample_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, mean, mean_bs, log_std, ls_bs, eps,
@@ -373,9 +359,9 @@ extern "C" int arflow_mixture_bwd(const float* mean, long mean_bs, const float* 
   const int rc = check_dims(B, S, K, M, N);
   if (rc != ARFLOW_OK) return rc;
   const long plane = (long)M * N, SB = (long)S * B;
-  AF_REQUIRE(stride_ok(mean_bs, B, 2L * K * plane) && stride_ok(ls_bs, B, 2L * K * plane) && stride_ok(eps_bs, SB, 2 * plane) &&
-                 (!gZ || stride_ok(gz_bs, SB, 2 * plane)) && stride_ok(gmean_bs, B, 2L * K * plane) &&
-                 stride_ok(gls_bs, B, 2L * K * plane),
+  AF_REQUIRE(af_stride_ok(mean_bs, B, 2L * K * plane) && af_stride_ok(ls_bs, B, 2L * K * plane) &&
+                 af_stride_ok(eps_bs, SB, 2 * plane) && (!gZ || af_stride_ok(gz_bs, SB, 2 * plane)) &&
+                 af_stride_ok(gmean_bs, B, 2L * K * plane) && af_stride_ok(gls_bs, B, 2L * K * plane),
              ARFLOW_ESHAPE);
   hipLaunchKernelGGL(mixture_bwd_kernel, dim3(af_cdiv(plane, NT), B), dim3(NT), 0, (hipStream_t)stream, mean, mean_bs, log_std,
                      ls_bs, eps, eps_bs, comp, resp, glogpdf, gZ, gz_bs, gmean, gmean_bs, glog_std, gls_bs, B, S, K, plane);
@@ -395,8 +381,8 @@ extern "C" int arflow_mixture_entropy_map(const float* mean, long mean_bs, const
   const int rc = check_dims(B, n, K, M, N);
   if (rc != ARFLOW_OK) return rc;
   const long plane = (long)M * N;
-  AF_REQUIRE(stride_ok(mean_bs, B, 2L * K * plane) && stride_ok(ls_bs, B, 2L * K * plane) &&
-                 stride_ok(eps_bs, (long)n * B, 2 * plane),
+  AF_REQUIRE(af_stride_ok(mean_bs, B, 2L * K * plane) && af_stride_ok(ls_bs, B, 2L * K * plane) &&
+                 af_stride_ok(eps_bs, (long)n * B, 2 * plane),
              ARFLOW_ESHAPE);
   hipLaunchKernelGGL(mixture_entropy_kernel, dim3(af_cdiv(plane, NT), B), dim3(NT), 0, (hipStream_t)stream, mean, mean_bs,
                      log_std, ls_bs, weights, comp, eps, eps_bs, out, B, n, K, plane);

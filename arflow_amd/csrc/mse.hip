@@ -12,8 +12,8 @@
 //             given z:   gz stored [S B][2][h][w];  gnet: 0:2 zero, 2:4 ge, 4:6 cl left, 6:8 co over (zero in the column / row
 //                        the slices leave out), channels 8.. zero
 // One lane takes one pixel (b, y, x) and both channels, lanes along x; it forms gt once, loads mean and log_diag once and
-// loops over the samples.  Sums: per lane in (sample, channel) order, by wave butterfly, the waves in wave order, ONE row of
-// four float64 partials per workgroup in `work`; a second one-wave launch of the same call folds the rows lane-strided in
+// loops over the samples.  Sums: per lane in (sample, channel) order, over the workgroup by af_block_sum_f64 (common.hpp), ONE
+// row of four float64 partials per workgroup in `work`; a second one-wave launch of the same call folds the rows lane-strided in
 // index order and by butterfly.  No atomics, no zero-fill: the same code and bits in normal and deterministic mode.  Every
 // element of every output is stored.
 #include "common.hpp"
@@ -33,17 +33,11 @@ struct MsArgs {
   int B, S, C, h, w, H, W, mode, align;
 };
 
-__device__ __forceinline__ double ms_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, AF_WAVE);
-  return v;
-}
-
 // the standard deviation, stated once: forward and backward must agree bit for bit
 __device__ __forceinline__ float ms_std(float log_diag, int mode) { return expf(mode == MS_INV ? -log_diag : log_diag); }
 
 __global__ __launch_bounds__(MS_NT) void mse_fwd_kernel(const MsArgs a, double* __restrict__ work) {
-  __shared__ double part[4][MS_NT / AF_WAVE];
+  __shared__ double part[4 * (MS_NT / AF_WAVE)];
   const long hw = (long)a.h * a.w;
   const long p = (long)blockIdx.x * MS_NT + threadIdx.x;
   const int b = blockIdx.y;
@@ -83,19 +77,11 @@ __global__ __launch_bounds__(MS_NT) void mse_fwd_kernel(const MsArgs a, double* 
       }
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  af_block_sum_f64<4, MS_NT>(acc, part);
+  if (threadIdx.x == 0) {
+    double* row = work + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 4;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double v = ms_wave_sum(acc[k]);
-    if (lane == 0) part[k][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    const int k = threadIdx.x;
-    double t = part[k][0];
-#pragma unroll
-    for (int wv = 1; wv < MS_NT / AF_WAVE; ++wv) t += part[k][wv];
-    work[((long)blockIdx.y * gridDim.x + blockIdx.x) * 4 + k] = t;
+    for (int k = 0; k < 4; ++k) row[k] = acc[k];
   }
 }
 
@@ -108,7 +94,7 @@ __global__ __launch_bounds__(AF_WAVE) void mse_fold_kernel(const double* __restr
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const double v = ms_wave_sum(acc[k]);
+    const double v = af_wave_sum(acc[k]);
     if (threadIdx.x == 0) sums[k] = v;
   }
 }

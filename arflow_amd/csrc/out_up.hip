@@ -287,7 +287,6 @@ int out_up_check(const void* a, long a_bs, const void* o, long o_bs, int B, int 
   AF_REQUIRE(B == 1 || (a_bs >= plane * a_scale && o_bs >= plane * o_scale), ARFLOW_ESHAPE);
   return ARFLOW_OK;
 }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace
 
 extern "C" int arflow_out_up2_fwd(const float* in, long in_bstride, float* out, long out_bstride, int B, int C, int h, int w,
@@ -296,7 +295,7 @@ extern "C" int arflow_out_up2_fwd(const float* in, long in_bstride, float* out, 
   const int rc = out_up_check(in, in_bstride, out, out_bstride, B, C, h, w, n_flow, n_diag, 1, 4);
   if (rc != ARFLOW_OK) return rc;
   const long n = (long)B * C * 4 * h * w;
-  if (w % 2 == 0 && aligned16(out) && (B == 1 || out_bstride % 4 == 0)) {
+  if (w % 2 == 0 && af_vec4_ok(out, out_bstride, B)) {
     hipLaunchKernelGGL(out_up2_fwd_kernel<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in,
                        in_bstride, out, out_bstride, B, C, h, w, n_flow, n_diag, diag_bias);
   } else {
@@ -328,7 +327,7 @@ extern "C" int arflow_out_tail_fwd(const float* in, long in_bstride, float* out1
   const long T = (long)ntx * nty * B * C;
   AF_REQUIRE(T <= (1L << 30), ARFLOW_ESHAPE);
   const dim3 grid(af_grid_for_tiles(T));
-  if (w % 2 == 0 && aligned16(out1) && aligned16(out0)) {
+  if (w % 2 == 0 && af_aligned16(out1) && af_aligned16(out0)) {
     hipLaunchKernelGGL(out_tail_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, in, in_bstride, out1, out0, B, C, h,
                        w, n_flow, n_diag, diag_bias, ntx, nty);
   } else {
@@ -346,7 +345,7 @@ extern "C" int arflow_prob_up_fwd(const float* in, long in_bstride, float* out, 
   if (rc != ARFLOW_OK) return rc;
   AF_REQUIRE(h <= 2048 && w <= 2048, ARFLOW_ESHAPE);
   const long n = (long)B * C * factor * factor * h * w;
-  if (((long)factor * w) % 4 == 0 && aligned16(out) && (B == 1 || out_bstride % 4 == 0)) {
+  if (((long)factor * w) % 4 == 0 && af_vec4_ok(out, out_bstride, B)) {
     hipLaunchKernelGGL(prob_up_fwd_kernel<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in,
                        in_bstride, out, out_bstride, B, C, h, w, factor, n_flow, n_diag, diag_bias);
   } else {

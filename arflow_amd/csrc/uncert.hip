@@ -16,7 +16,6 @@
 // launch, the same bits from every call in either mode.  Partials are fp32 per thread over at most 8 pixels and double from
 // the wave reduction on; the histogram is double from the first addition.
 #include "common.hpp"
-#include "featnorm_stats.hpp"
 #include "taps.hpp"
 
 namespace {
@@ -24,7 +23,7 @@ namespace {
 constexpr int NT = 256;            // threads per workgroup
 constexpr int NW = NT / 64;        // waves per workgroup
 constexpr int TW = 64, TH = 32;    // tile of full-resolution pixels (prep, sparsify)
-constexpr int CPT = 4;             // consecutive columns per thread (one float4)
+constexpr int CPT = 4;             // consecutive columns per thread (one float4: af_ld_cols4 / af_st_cols4)
 constexpr int RSTEP = NT / (TW / CPT);  // tile rows per pass of the workgroup: 16
 constexpr int RPT = TH / RSTEP;    // rows per thread: 2
 constexpr int PPT = CPT * RPT;     // pixels per thread: 8
@@ -32,19 +31,6 @@ constexpr int MAX_DIM = 16384;
 constexpr int MAX_K = 32;          // thresholds per field and launch
 constexpr int MAX_NB = 128;        // histogram edges
 constexpr int CHUNK = NT * PPT;    // elements of one plane per histogram workgroup: 2048
-
-// four consecutive floats of a plane row starting at column X0 (`fill` beyond W); VEC: W % 4 == 0 and the plane 16-byte
-// aligned, so X0 < W implies X0 + 3 < W and the address is aligned
-template <bool VEC>
-__device__ __forceinline__ void ld_cols(const float* __restrict__ row, int X0, int W, float fill, float (&v)[CPT]) {
-  if (VEC) {
-    const float4 t = X0 < W ? *reinterpret_cast<const float4*>(row + X0) : make_float4(fill, fill, fill, fill);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < CPT; ++j) v[j] = X0 + j < W ? row[X0 + j] : fill;
-  }
-}
 
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
@@ -90,9 +76,9 @@ __global__ __launch_bounds__(NT) void uncert_prep_kernel(const float* __restrict
     float wy0, wy1;
     up_source(Y, h, H, fh / fH, false, ya, yb, wy0, wy1);
     float pe[CPT], g[CPT], out[CPT];
-    ld_cols<VEC>(ep + (long)Y * W, X0, W, 0.f, pe);
+    af_ld_cols4<VEC>(ep + (long)Y * W, X0, W, 0.f, pe);
     if (va) {
-      ld_cols<VEC>(va + (long)Y * W, X0, W, 0.f, g);
+      af_ld_cols4<VEC>(va + (long)Y * W, X0, W, 0.f, g);
     } else {
 #pragma unroll
       for (int j = 0; j < CPT; ++j) g[j] = X0 + j < W ? 1.f : 0.f;
@@ -115,18 +101,10 @@ __global__ __launch_bounds__(NT) void uncert_prep_kernel(const float* __restrict
         sv += g[j];
       }
     }
-    if (VEC) {
-      if (X0 < W) *reinterpret_cast<float4*>(om + (long)Y * W + X0) = make_float4(out[0], out[1], out[2], out[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < CPT; ++j)
-        if (X0 + j < W) om[(long)Y * W + X0 + j] = out[j];
-    }
+    af_st_cols4<VEC>(om + (long)Y * W, X0, W, out);
   }
   // sum valid: at most 8 values of a mask per thread in fp32, double from here on; min / max are exact in fp32
-  double dv = (double)sv;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) dv += __shfl_xor(dv, off, 64);
+  const double dv = af_wave_sum((double)sv);
   mn_e = wave_min(mn_e), mx_e = wave_max(mx_e), mn_p = wave_min(mn_p), mx_p = wave_max(mx_p);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
@@ -172,19 +150,19 @@ __global__ __launch_bounds__(NT) void sparsify_sums_kernel(const float* __restri
     float t[CPT];
     if (Y < H) {  // (not a break: the wave reductions below need every lane)
       const long o = HW * b + (long)Y * W;
-      ld_cols<VEC>(err + o, X0, W, 0.f, t);
+      af_ld_cols4<VEC>(err + o, X0, W, 0.f, t);
 #pragma unroll
       for (int j = 0; j < CPT; ++j) er[k * CPT + j] = t[j];
-      ld_cols<VEC>(field0 + o, X0, W, 0.f, t);
+      af_ld_cols4<VEC>(field0 + o, X0, W, 0.f, t);
 #pragma unroll
       for (int j = 0; j < CPT; ++j) fd[0][k * CPT + j] = (double)t[j];
       if (F == 2) {
-        ld_cols<VEC>(field1 + o, X0, W, 0.f, t);
+        af_ld_cols4<VEC>(field1 + o, X0, W, 0.f, t);
 #pragma unroll
         for (int j = 0; j < CPT; ++j) fd[F - 1][k * CPT + j] = (double)t[j];
       }
       if (va) {
-        ld_cols<VEC>(va + (long)Y * W, X0, W, 0.f, t);
+        af_ld_cols4<VEC>(va + (long)Y * W, X0, W, 0.f, t);
 #pragma unroll
         for (int j = 0; j < CPT; ++j) g[k * CPT + j] = t[j];
       } else {
@@ -217,11 +195,7 @@ __global__ __launch_bounds__(NT) void sparsify_sums_kernel(const float* __restri
         s1 += mg;
         s2 += er[p] * mg;
       }
-      double d0 = (double)s0, d1 = (double)s1, d2 = (double)s2;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        d0 += __shfl_xor(d0, off, 64), d1 += __shfl_xor(d1, off, 64), d2 += __shfl_xor(d2, off, 64);
-      }
+      const double d0 = af_wave_sum((double)s0), d1 = af_wave_sum((double)s1), d2 = af_wave_sum((double)s2);
       if (lane == 0) {
         double* q = part + ((wave * F + f) * MAX_K + k) * 3;
         q[0] = d0, q[1] = d1, q[2] = d2;
@@ -304,9 +278,7 @@ __global__ __launch_bounds__(NT) void calib_hist_kernel(const float* __restrict_
         const int cur = __builtin_amdgcn_readlane(bin, first);
         const bool mine = in && bin == cur;
         const unsigned long long m = __ballot(mine);
-        double v1 = mine ? de : 0.0, v2 = mine ? de2 : 0.0;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v1 += __shfl_xor(v1, off, 64), v2 += __shfl_xor(v2, off, 64);
+        const double v1 = af_wave_sum(mine ? de : 0.0), v2 = af_wave_sum(mine ? de2 : 0.0);
         if (lane == first) {
           double* hb = hw_ + cur * 3;
           hb[0] += (double)__popcll(m), hb[1] += v1, hb[2] += v2;
@@ -323,8 +295,6 @@ __global__ __launch_bounds__(NT) void calib_hist_kernel(const float* __restrict_
     r[i] = t;
   }
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -345,7 +315,7 @@ extern "C" int arflow_uncert_prep(const float* ent, const float* epe_map, const 
   AF_REQUIRE(B <= 65535 && h <= MAX_DIM && w <= MAX_DIM && H <= MAX_DIM && W <= MAX_DIM, ARFLOW_ESHAPE);
   AF_REQUIRE(valid == nullptr || valid_bstride >= (long)H * W, ARFLOW_ESHAPE);
   const dim3 grid(af_cdiv(W, TW), af_cdiv(H, TH), B);
-  const bool vec = W % 4 == 0 && aligned16(epe_map) && aligned16(ent_map) && aligned16(valid) &&
+  const bool vec = W % 4 == 0 && af_aligned16(epe_map) && af_aligned16(ent_map) && af_aligned16(valid) &&
                    (valid == nullptr || valid_bstride % 4 == 0);
   if (vec)
     hipLaunchKernelGGL(uncert_prep_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, ent, epe_map, valid, valid_bstride,
@@ -369,7 +339,7 @@ extern "C" int arflow_sparsify_sums(const float* err, const float* field0, const
   AF_REQUIRE(valid == nullptr || valid_bstride >= (long)H * W, ARFLOW_ESHAPE);
   AF_REQUIRE(K >= 1 && K <= MAX_K, ARFLOW_EPARAM);
   const dim3 grid(af_cdiv(W, TW), af_cdiv(H, TH), B);
-  const bool vec = W % 4 == 0 && aligned16(err) && aligned16(field0) && aligned16(field1) && aligned16(valid) &&
+  const bool vec = W % 4 == 0 && af_aligned16(err) && af_aligned16(field0) && af_aligned16(field1) && af_aligned16(valid) &&
                    (valid == nullptr || valid_bstride % 4 == 0);
 #define AF_SPARSIFY(VEC, F)                                                                                              \
   hipLaunchKernelGGL((sparsify_sums_kernel<VEC, F>), grid, dim3(NT), 0, (hipStream_t)stream, err, field0, field1, valid, \
@@ -405,7 +375,7 @@ extern "C" int arflow_calib_hist(const float* pred, const float* gt, const float
   const long HW = (long)H * W;
   const dim3 grid(af_cdiv(HW, CHUNK), 2, B);
   // float4 pieces of the flattened planes: every plane starts 16-byte aligned when H * W % 4 == 0
-  const bool vec = HW % 4 == 0 && aligned16(pred) && aligned16(gt) && aligned16(ent);
+  const bool vec = HW % 4 == 0 && af_aligned16(pred) && af_aligned16(gt) && af_aligned16(ent);
   if (vec)
     hipLaunchKernelGGL(calib_hist_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, pred, gt, ent, edges, rows, C, H, W,
                        nb);

@@ -364,7 +364,7 @@ __global__ __launch_bounds__(256) void level_warp_fwd_kernel(const float* __rest
     }
   }
   double dm[4] = {(double)mom[0], (double)mom[1], (double)mom[2], (double)mom[3]};
-  featnorm::block_sum_f64<4, NT>(dm, dscratch);
+  af_block_sum_f64<4, NT>(dm, dscratch);
   if (threadIdx.x == 0) {
     const int rows = ntx * nty * gridDim.y;
     double* row = acc + 4 * ((long)b * rows + (long)(bty * ntx + btx) * gridDim.y + blockIdx.y);

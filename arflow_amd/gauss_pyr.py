@@ -11,12 +11,13 @@ ValueError naming the argument.  Each net / eps may be a channel slice of a wide
 batch stride): it is passed to the kernels in place.  1 <= n <= 6 scales of one batch size.
 """
 import ctypes
+from functools import partial
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from ._planes import check_planes, plane_dense, work_buffer
 from .functional import _call, _p, _stream
 
 __all__ = ['reparam_pyramid', 'NMAX']
@@ -24,22 +25,7 @@ __all__ = ['reparam_pyramid', 'NMAX']
 NMAX = 6
 
 
-def _check(name, t, shape):
-    """A [B,C,h,w] fp32 GPU tensor whose items are dense (any batch stride) -> its batch stride."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError('%s must be a tensor (got %s)' % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise _lib.ArflowHipError('arflow_amd.gauss_pyr runs on the GPU only (%s is a %s tensor); there is no CPU fallback'
-                                  % (name, t.device))
-    if t.dtype != torch.float32:
-        raise ValueError('%s must be float32 (got %s)' % (name, t.dtype))
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError('%s must be %s (got %s)' % (name, tuple(shape), tuple(t.shape)))
-    B, C, h, w = shape
-    st = t.stride()
-    if (w > 1 and st[3] != 1) or (h > 1 and st[2] != w) or (C > 1 and st[1] != h * w) or (B > 1 and st[0] < C * h * w):
-        raise ValueError('%s must be contiguous or a channel slice of a contiguous tensor' % name)
-    return st[0] if B > 1 else C * h * w
+_check = partial(check_planes, __name__)  # the plane-layout rule (_planes.py) under this module's name
 
 
 def _ptrs(ts):
@@ -89,9 +75,7 @@ def _sample_fwd(nets, eps, zs=None, ent=None):
         if t.device != dev:
             raise ValueError('%s[%d] is on %s, nets[0] on %s' % ('nets' if i < n else 'eps', i % n, t.device, dev))
     hs, ws = _ints([s[0] for s in sizes]), _ints([s[1] for s in sizes])
-    nw = _lib.load().arflow_gauss_pyr_work_size(hs, ws, n, B)
-    _lib.check(min(nw, 0), 'arflow_gauss_pyr_work_size')
-    work = torch.empty(nw, device=dev, dtype=torch.float64)
+    work = work_buffer('arflow_gauss_pyr_work_size', (hs, ws, n, B), dev)
     if ent is None:
         ent = torch.empty(n, 2, device=dev, dtype=torch.float64)
     with torch.cuda.device_of(nets[0]):
@@ -120,9 +104,7 @@ def _sample_bwd(nets, eps, gzs, gent, gnets=None):
                 zbs.append(0)
                 continue
             h, w = sizes[i]
-            st = g.stride()
-            if st[3] != 1 or st[2] != w or st[1] != h * w or (B > 1 and st[0] < 4 * h * w):
-                g = gzs[i] = g.contiguous()  # also a gradient expanded along an axis (stride 0)
+            g = gzs[i] = plane_dense(g, (B, 4, h, w))
             zbs.append(_check('gz[%d]' % i, g, (B, 4, h, w)))
         gz_arr, gz_bs = _ptrs(gzs), _longs(zbs)
     if gent is not None:

@@ -10,11 +10,13 @@ the argument.  mean and std may be channel slices of one wider tensor (rows, pla
 are passed to the kernels in place.  h w < R raises ValueError: the Gram matrix is then singular by construction.  A Gram matrix
 that is singular to working precision gives NaN for its log-determinant (the reference's torch.logdet: -inf / NaN).
 """
+from functools import partial
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from ._planes import check_planes, load_optional, plane_dense, save_optional, work_buffer
 from .functional import _call, _p, _stream
 
 __all__ = ['reparam_lowrank', 'gram_logdet', 'reparam_lowrank_pair', 'RMAX']
@@ -22,22 +24,7 @@ __all__ = ['reparam_lowrank', 'gram_logdet', 'reparam_lowrank_pair', 'RMAX']
 RMAX = 16
 
 
-def _check(name, t, shape):
-    """A [n,C,M,N] fp32 GPU tensor whose items are dense (any batch stride) -> its batch stride."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError('%s must be a tensor (got %s)' % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise _lib.ArflowHipError('arflow_amd.lowrank runs on the GPU only (%s is a %s tensor); there is no CPU fallback'
-                                  % (name, t.device))
-    if t.dtype != torch.float32:
-        raise ValueError('%s must be float32 (got %s)' % (name, t.dtype))
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError('%s must be %s (got %s)' % (name, tuple(shape), tuple(t.shape)))
-    n, C, M, N = shape
-    st = t.stride()
-    if (N > 1 and st[3] != 1) or (M > 1 and st[2] != N) or (C > 1 and st[1] != M * N) or (n > 1 and st[0] < C * M * N):
-        raise ValueError('%s must be contiguous or a channel slice of a contiguous tensor' % name)
-    return st[0] if n > 1 else C * M * N
+_check = partial(check_planes, __name__)  # the plane-layout rule (_planes.py) under this module's name
 
 
 def _std_dims(std):
@@ -80,9 +67,7 @@ def _logdet_fwd(std, logdet=None, ginv=None):
     s_bs = _check('std', std, (B, 2 * R, M, N))
     if M * N < R:
         raise ValueError('std: %d pixels cannot carry %d independent columns (the Gram matrix is singular)' % (M * N, R))
-    n = _lib.load().arflow_lowrank_work_size(B, R, M, N)
-    _lib.check(min(n, 0), 'arflow_lowrank_work_size')
-    work = torch.empty(n, device=std.device, dtype=torch.float64)
+    work = work_buffer('arflow_lowrank_work_size', (B, R, M, N), std.device)
     if logdet is None:
         logdet = torch.empty(B, 2, device=std.device, dtype=torch.float32)
     if ginv is None:
@@ -100,9 +85,7 @@ def _bwd(std, eps, gZ, ginv, glogdet, S, want_gmean, gmean=None, gstd=None):
     s_bs = _check('std', std, (B, 2 * R, M, N))
     g_bs = 0
     if gZ is not None:
-        st = gZ.stride()
-        if st[3] != 1 or st[2] != N or st[1] != M * N or (S * B > 1 and st[0] < 2 * M * N):
-            gZ = gZ.contiguous()  # also a gradient expanded along the batch (stride 0)
+        gZ = plane_dense(gZ, (S * B, 2, M, N))
         g_bs = _check('gZ', gZ, (S * B, 2, M, N))
         eps = _eps_check(eps, S, B, R, std)
     if glogdet is not None:
@@ -153,8 +136,7 @@ class _LowRank(Function):
                 _sample_fwd(mean, std, eps, S, Z[:, 2 * d:2 * d + 2])
             if logdet:
                 ginvs.append(_logdet_fwd(std, logdet=ld[d])[1])
-        ctx.save_for_backward(*[x for x in t if x is not None], *ginvs)
-        ctx.none = [x is None for x in t]
+        save_optional(ctx, t, ginvs)
         ctx.cfg = (S, ndir, bool(sample), bool(logdet))
         ctx.set_materialize_grads(False)
         return Z, ld
@@ -163,9 +145,7 @@ class _LowRank(Function):
     @once_differentiable
     def backward(ctx, gZ, gld):
         S, ndir, sample, logdet = ctx.cfg
-        saved = list(ctx.saved_tensors)
-        t = [None if is_none else saved.pop(0) for is_none in ctx.none]
-        ginvs = saved
+        t, ginvs = load_optional(ctx)
         grads = []
         for d in range(ndir):
             mean, std, eps = t[3 * d:3 * d + 3]

@@ -14,25 +14,22 @@ Everything is fp32 and on the GPU: a CPU tensor raises ArflowHipError, a wrong d
 the argument.  mean and log_std may be channel slices of one wider tensor (rows, planes and channels dense, any batch stride):
 they are passed to the kernels in place.  A value of comp outside 0..K-1 is clamped into the range by the kernels.
 """
+from functools import partial
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from ._planes import check_planes, check_small, load_optional, plane_dense, save_optional, work_buffer
 from .functional import _call, _p, _stream
-from .lowrank import _check as _check_lowrank
 
 __all__ = ['reparam_gmm', 'gaussian_mixture_log_pdf', 'reparam_gmm_pair', 'mixture_entropy', 'KMAX']
 
 KMAX = 4
 
 
-def _check(name, t, shape):
-    """A [n,C,M,N] fp32 GPU tensor whose items are dense (any batch stride) -> its batch stride."""
-    if isinstance(t, torch.Tensor) and not t.is_cuda:
-        raise _lib.ArflowHipError('arflow_amd.mixture runs on the GPU only (%s is a %s tensor); there is no CPU fallback'
-                                  % (name, t.device))
-    return _check_lowrank(name, t, shape)
+_check = partial(check_planes, __name__)  # the plane-layout rule and the small-tensor check (_planes.py) under this
+_small = partial(check_small, __name__)   # module's name
 
 
 def _dims(mean):
@@ -45,22 +42,6 @@ def _dims(mean):
     if B < 1 or M < 1 or N < 1:
         raise ValueError('mean must not be empty (got %s)' % (tuple(mean.shape),))
     return B, C // 2, M, N
-
-
-def _small(name, t, shape, dtype, like):
-    """A small dense tensor (weights, comp, logpdf gradients) on `like`'s device -> contiguous."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError('%s must be a tensor (got %s)' % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise _lib.ArflowHipError('arflow_amd.mixture runs on the GPU only (%s is a %s tensor); there is no CPU fallback'
-                                  % (name, t.device))
-    if t.dtype != dtype:
-        raise ValueError('%s must be %s (got %s)' % (name, dtype, t.dtype))
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError('%s must be %s (got %s)' % (name, tuple(shape), tuple(t.shape)))
-    if t.device != like.device:
-        raise ValueError('%s is on %s, mean on %s' % (name, t.device, like.device))
-    return t.contiguous()
 
 
 def _inputs(mean, log_std, comp, eps, S):
@@ -83,10 +64,8 @@ def _sample_fwd(mean, log_std, weights, comp, eps, S, out, logpdf=None):
     B, K, M, N, m_bs, l_bs, comp, e_bs = _inputs(mean, log_std, comp, eps, S)
     weights = _small('weights', weights, (B, K), torch.float32, mean)
     z_bs = _check('out', out, (S * B, 2, M, N))
-    n = _lib.load().arflow_mixture_work_size(B, S, K, M, N)
-    _lib.check(min(n, 0), 'arflow_mixture_work_size')
     dev = mean.device
-    work = torch.empty(n, device=dev, dtype=torch.float64)
+    work = work_buffer('arflow_mixture_work_size', (B, S, K, M, N), dev)
     if logpdf is None:
         logpdf = torch.empty(S * B, device=dev, dtype=torch.float32)
     resp = torch.empty(S * B, K, device=dev, dtype=torch.float32)
@@ -105,9 +84,7 @@ def _bwd(mean, log_std, comp, eps, resp, glogpdf, gZ, S, gmean=None, glog_std=No
     B, K, M, N, m_bs, l_bs, comp, e_bs = _inputs(mean, log_std, comp, eps, S)
     g_bs = 0
     if gZ is not None:
-        st = gZ.stride()
-        if st[3] != 1 or st[2] != N or st[1] != M * N or (S * B > 1 and st[0] < 2 * M * N):
-            gZ = gZ.contiguous()  # also a gradient expanded along the batch (stride 0)
+        gZ = plane_dense(gZ, (S * B, 2, M, N))
         g_bs = _check('gZ', gZ, (S * B, 2, M, N))
     if glogpdf is not None:
         glogpdf = _small('glogpdf', glogpdf, (S * B,), torch.float32, mean)
@@ -151,8 +128,7 @@ class _Mixture(Function):
                 raise ValueError('mean of direction %d must be %s (got %s)' % (d, (B, 2 * K, M, N), tuple(mean.shape)))
             _, resp, q = _sample_fwd(mean, log_std, weights, comp, eps, S, Z[:, 2 * d:2 * d + 2], logpdf=lp[d])
             keep += [resp, q]
-        ctx.save_for_backward(*[x for x in t if x is not None], *keep)
-        ctx.none = [x is None for x in t]
+        save_optional(ctx, t, keep)
         ctx.cfg = (S, ndir)
         ctx.set_materialize_grads(False)
         return Z, lp
@@ -170,8 +146,7 @@ class _Mixture(Function):
     @once_differentiable
     def backward(ctx, gZ, glp):
         S, ndir = ctx.cfg
-        saved = list(ctx.saved_tensors)
-        t = [None if is_none else saved.pop(0) for is_none in ctx.none]
+        t, saved = load_optional(ctx)
         grads = []
         for d in range(ndir):
             joint = t[5 * d + 1] is None

@@ -9,18 +9,22 @@ Everything is fp32 (sums float64) and on the GPU: a CPU tensor raises ArflowHipE
 ValueError naming the argument.  net, target, eps and z may be channel slices of wider tensors (rows, planes and channels
 dense, any batch stride): they are passed to the kernels in place.
 """
+from functools import partial
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from ._planes import check_planes, work_buffer
 from .functional import _call, _p, _stream
-from .gauss_pyr import _check
 
 __all__ = ['mse_sums', 'resize_flow', 'MODE_COV', 'MODE_INV', 'MODE_GIVEN']
 
 MODE_COV, MODE_INV, MODE_GIVEN = 0, 1, 2
 MAX_SAMPLES = 65535  # S B
+
+# the plane-layout rule (_planes.py); this module's checks have always reported under the pyramid sampler's name
+_check = partial(check_planes, 'arflow_amd.gauss_pyr')
 
 
 def _dims(net, target, ez, S, mode):
@@ -56,9 +60,7 @@ def _dims(net, target, ez, S, mode):
 def _fwd(net, target, ez, S, mode, align_corners, sums=None):
     """One call (map launch + fold launch) -> sums float64 [4]."""
     B, C, h, w, H, W, nb, tb, eb = _dims(net, target, ez, S, mode)
-    nw = _lib.load().arflow_mse_work_size(B, h, w)
-    _lib.check(min(nw, 0), 'arflow_mse_work_size')
-    work = torch.empty(nw, device=net.device, dtype=torch.float64)
+    work = work_buffer('arflow_mse_work_size', (B, h, w), net.device)
     if sums is None:
         sums = torch.empty(4, device=net.device, dtype=torch.float64)
     with torch.cuda.device_of(net):

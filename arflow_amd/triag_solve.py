@@ -12,12 +12,15 @@ The banded operator of the sparse-covariance family (utils/triag_solve.py:29-43,
 Their tensors may be channel slices of wider tensors (rows, planes and channels dense, any batch stride): they are passed to
 the kernels in place.
 """
+from functools import partial
+
 import torch
 import torch.nn.functional as F
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._planes import check_planes, load_optional, plane_dense, save_optional
 from .functional import _call, _p, _stream
 
 __all__ = ['forward_substitution', 'backward_substitution', 'ForwardSubst', 'BackwardSubst', 'inverse_diagonal',
@@ -159,22 +162,7 @@ def reparam_triag_inv(mean, diag, left, over, leftover, nsamples=1, eps=None):
 
 
 # ---- the banded operator (csrc/band.hip) --------------------------------------------------------------------------
-def _band_check(name, t, shape):
-    """A [n,C,M,N] fp32 GPU tensor whose items are dense (any batch stride) -> its batch stride."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError('%s must be a tensor (got %s)' % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise _lib.ArflowHipError('arflow_amd.triag_solve runs on the GPU only (%s is a %s tensor); there is no CPU '
-                                  'fallback' % (name, t.device))
-    if t.dtype != torch.float32:
-        raise ValueError('%s must be float32 (got %s)' % (name, t.dtype))
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError('%s must be %s (got %s)' % (name, tuple(shape), tuple(t.shape)))
-    n, C, M, N = shape
-    st = t.stride()
-    if (N > 1 and st[3] != 1) or (M > 1 and st[2] != N) or (C > 1 and st[1] != M * N) or (n > 1 and st[0] < C * M * N):
-        raise ValueError('%s must be contiguous or a channel slice of a contiguous tensor' % name)
-    return st[0] if n > 1 else C * M * N
+_check_band = partial(check_planes, __name__)  # the plane-layout rule (_planes.py) under this module's name
 
 
 def _band_args(k, nsamples, mean, diag, off, X):
@@ -187,10 +175,10 @@ def _band_args(k, nsamples, mean, diag, off, X):
     if not isinstance(diag, torch.Tensor) or diag.dim() != 4:
         raise ValueError('diag must be a [B,2,M,N] tensor')
     B, _, M, N = diag.shape
-    d_bs = _band_check('diag', diag, (B, 2, M, N))
-    o_bs = _band_check('offdiag', off, (B, 2 * ((k + 1) ** 2 - 1), M, N)) if k > 0 else 0
-    m_bs = 0 if mean is None else _band_check('mean', mean, (B, 2, M, N))
-    x_bs = _band_check('X', X, (S * B, 2, M, N))
+    d_bs = _check_band('diag', diag, (B, 2, M, N))
+    o_bs = _check_band('offdiag', off, (B, 2 * ((k + 1) ** 2 - 1), M, N)) if k > 0 else 0
+    m_bs = 0 if mean is None else _check_band('mean', mean, (B, 2, M, N))
+    x_bs = _check_band('X', X, (S * B, 2, M, N))
     for name, t in (('offdiag', off if k > 0 else None), ('mean', mean), ('X', X)):
         if t is not None and t.device != diag.device:
             raise ValueError('%s is on %s, diag on %s' % (name, t.device, diag.device))
@@ -199,7 +187,7 @@ def _band_args(k, nsamples, mean, diag, off, X):
 
 def _band_fwd(k, S, transpose, mean, diag, off, X, Y):
     B, S, M, N, m_bs, d_bs, o_bs, x_bs = _band_args(k, S, mean, diag, off, X)
-    y_bs = _band_check('out', Y, (S * B, 2, M, N))
+    y_bs = _check_band('out', Y, (S * B, 2, M, N))
     off = off if k > 0 else None
     with torch.cuda.device_of(diag):
         _call('arflow_band_mv_fwd', _p(mean), m_bs, _p(diag), d_bs, _p(off), o_bs, _p(X), x_bs, _p(Y), y_bs, B, S, M, N, int(k),
@@ -210,9 +198,8 @@ def _band_bwd(k, S, transpose, diag, off, X, gY, want_gx, want_gmean, gA=None):
     """-> gmean (or None), gdiag, goff (None for k = 0), gX (or None).  gA: a [B,2(k+1)^2,M,N] tensor to store gdiag and goff
     into (its channels 0:2 and 2:), so that a whole-A gradient needs no cat."""
     B, S, M, N, _, d_bs, o_bs, x_bs = _band_args(k, S, None, diag, off, X)
-    if gY.stride(3) != 1 or gY.stride(2) != N or gY.stride(1) != M * N or (S * B > 1 and gY.stride(0) < 2 * M * N):
-        gY = gY.contiguous()  # also a gradient expanded along the batch (stride 0), as a sum over the samples sends
-    g_bs = _band_check('gY', gY, (S * B, 2, M, N))
+    gY = plane_dense(gY, (S * B, 2, M, N))
+    g_bs = _check_band('gY', gY, (S * B, 2, M, N))
     new = lambda n, c: torch.empty(n, c, M, N, device=diag.device, dtype=torch.float32)  # noqa: E731
     if gA is not None:
         gdiag, goff = gA[:, :2], (gA[:, 2:] if k > 0 else None)
@@ -240,8 +227,8 @@ class _BandProduct(Function):
             raise ValueError('k must be 0..3 (got %r)' % (k,))
         if not isinstance(A, torch.Tensor) or A.dim() != 4 or A.shape[1] != 2 * (k + 1) ** 2:
             raise ValueError('A must be a [K,%d,M,N] tensor for k = %d (got %s)' % (2 * (k + 1) ** 2, k, tuple(getattr(A, 'shape', ()))))
-        _band_check('A', A, A.shape)
-        _band_check('X', X, (A.shape[0], 2, A.shape[2], A.shape[3]))
+        _check_band('A', A, A.shape)
+        _check_band('X', X, (A.shape[0], 2, A.shape[2], A.shape[3]))
         Y = torch.empty(X.shape, device=X.device, dtype=torch.float32)
         _band_fwd(k, 1, transpose, None, A[:, :2], A[:, 2:], X, Y)
         ctx.save_for_backward(A, X)
@@ -281,8 +268,7 @@ class _Reparam(Function):
         for d in range(ndir):
             mean, diag, off, eps = t[4 * d:4 * d + 4]
             _band_fwd(k, S, 0, mean, diag, off, eps, out[:, 2 * d:2 * d + 2])
-        ctx.save_for_backward(*[x for x in t if x is not None])
-        ctx.none = [x is None for x in t]
+        save_optional(ctx, t)
         ctx.cfg = (int(k), int(S), int(ndir))
         return out
 
@@ -290,8 +276,7 @@ class _Reparam(Function):
     @once_differentiable
     def backward(ctx, gout):
         k, S, ndir = ctx.cfg
-        saved = list(ctx.saved_tensors)
-        t = [None if is_none else saved.pop(0) for is_none in ctx.none]
+        t = load_optional(ctx)[0]
         grads = []
         for d in range(ndir):
             mean, diag, off, eps = t[4 * d:4 * d + 4]
