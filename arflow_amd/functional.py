@@ -739,23 +739,75 @@ def splitconv(x, w, transpose_flip=False):
     return y
 
 
+_SPLITCONV_WGRAD = __import__('os').environ.get('ARFLOW_SPLITCONV_WGRAD', '1') != '0'  # A/B switch: 0 = MIOpen's weight gradients
+
+
+def splitconv_wgrad_takes(N, C, K, H, W):
+    """Whether the WEIGHT GRADIENT of the layer x: [N,C,H,W] -> y: [N,K,H,W] (3x3, stride 1, padding 1) goes to
+    csrc/splitconv_wgrad.hip.  Asked by ConvAct and by DenseEstimatorFunction.backward with the same arguments, so the fused
+    and the composed path run the same kernel for the same layer.  Off with ARFLOW_SPLITCONV_WGRAD=0 and with ARFLOW_SPLITCONV=0.
+    The rule is read off profiles/splitconv_wgrad_kbench.log."""
+    if not (_SPLITCONV and _SPLITCONV_WGRAD):
+        return False
+    return _splitconv_wgrad_rule(int(N), int(C), int(K), int(H), int(W))
+
+
+def _splitconv_wgrad_rule(N, C, K, H, W):
+    # never below N H W = 16 x 48 x 80 (the shapes of the existing tests keep MIOpen's dw); measured at N = 16 over the seven
+    # (C, K) of section 17 and four map sizes: ahead of MIOpen's solver plus its layout copies by more than the spread of both
+    # only at 96x160 with many input channels -- 499->64 1.09x, 563->32 1.40x, 597->128 1.06x (403->96 1.02x, 147 / 275->128
+    # 0.93x / 0.97x are not) -- and on no call at 48x80 (0.75x .. 1.04x), 24x40 or 12x20
+    if N * H * W < 16 * 48 * 80:
+        return False
+    return H * W >= 96 * 160 and N * H * W >= 16 * 96 * 160 and 448 <= C <= 640 and 32 <= K <= 128
+
+
+def _batch_strided(t):
+    """t if its planes, rows and channels are dense (only the batch stride is free: a channel slice of a larger tensor),
+    else a contiguous copy; and the batch stride in elements."""
+    _, C, H, W = t.shape
+    if t.stride(3) != 1 or t.stride(2) != W or t.stride(1) != H * W or (t.shape[0] > 1 and t.stride(0) < C * H * W):
+        t = t.contiguous()
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else C * H * W)
+
+
+def splitconv_wgrad(x, gy):
+    """dw [K,C,3,3] of conv2d(x, w, padding=1) for the output gradient gy, through arflow_splitconv_wgrad (no autograd).
+    x: [N,C,H,W], gy: [N,K,H,W]; either may be a channel slice of a larger tensor (read in place)."""
+    _need_gpu(x, gy)
+    if x.dim() != 4 or gy.dim() != 4 or x.shape[0] != gy.shape[0] or x.shape[2:] != gy.shape[2:]:
+        raise ValueError('splitconv_wgrad expects x [N,C,H,W] and gy [N,K,H,W]')
+    x, x_bs = _batch_strided(x)
+    gy, gy_bs = _batch_strided(gy)
+    N, C, H, W = x.shape
+    K = int(gy.shape[1])
+    nbytes = _lib.load().arflow_splitconv_wgrad_ws_bytes(N, C, K, H, W)
+    if nbytes < 0:
+        _lib.check(int(nbytes), 'arflow_splitconv_wgrad_ws_bytes')
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    dw = torch.empty(K, C, 3, 3, device=x.device, dtype=torch.float32)
+    with torch.cuda.device_of(x):
+        _call('arflow_splitconv_wgrad', _p(x), x_bs, _p(gy), gy_bs, _p(dw), _p(ws), N, C, K, H, W, _stream())
+    return dw
+
+
 def _conv_args():
     return [1, 1], [1, 1], [1, 1], False, [0, 0], 1  # stride, padding, dilation, transposed, output_padding, groups
 
 
 class Conv3x3Function(torch.autograd.Function):
-    """y = conv2d(x, w, None, 1, 1) for a 3x3 kernel as one autograd node.  `fwd` / `dgrad` say which of the forward and the
-    data gradient run the split-bf16 kernel; the other one, and always the weight gradient, are the calls F.conv2d and its
+    """y = conv2d(x, w, None, 1, 1) for a 3x3 kernel as one autograd node.  `fwd` / `dgrad` / `wgrad` say which of the
+    forward, the data gradient and the weight gradient run the split-bf16 kernels; the others are the calls F.conv2d and its
     autograd make (aten.convolution / aten.convolution_backward: the same MIOpen problem keys as before)."""
 
     @staticmethod
-    def forward(ctx, x, w, fwd, dgrad):
+    def forward(ctx, x, w, fwd, dgrad, wgrad=False):
         if fwd:
             y = splitconv(x, w)
         else:
             y = torch.ops.aten.convolution(x, w, None, *_conv_args())
         ctx.save_for_backward(x, w)
-        ctx.dgrad = bool(dgrad)
+        ctx.dgrad, ctx.wgrad = bool(dgrad), bool(wgrad)
         return y
 
     @staticmethod
@@ -768,19 +820,22 @@ class Conv3x3Function(torch.autograd.Function):
         if ctx.dgrad and want_dx:
             dx = splitconv(gy, w, transpose_flip=True)
             want_dx = False
+        if ctx.wgrad and want_dw:
+            dw = splitconv_wgrad(x, gy)
+            want_dw = False
         if want_dx or want_dw:
-            dx_m, dw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, *_conv_args(), [want_dx, want_dw, False])
+            dx_m, dw_m, _ = torch.ops.aten.convolution_backward(gy, x, w, None, *_conv_args(), [want_dx, want_dw, False])
             if want_dx:
                 dx = dx_m
-            if not want_dw:
-                dw = None
-        return dx, dw, None, None
+            if want_dw:
+                dw = dw_m
+        return dx, dw, None, None, None
 
 
-def conv3x3(x, w, fwd=True, dgrad=True):
-    """conv2d(x, w, padding=1), 3x3: forward and data gradient on the split-bf16 kernel (each can be left to MIOpen), weight
-    gradient MIOpen's."""
-    return Conv3x3Function.apply(x, w, bool(fwd), bool(dgrad))
+def conv3x3(x, w, fwd=True, dgrad=True, wgrad=False):
+    """conv2d(x, w, padding=1), 3x3: forward, data gradient and (wgrad) weight gradient on the split-bf16 kernels; each can
+    be left to MIOpen."""
+    return Conv3x3Function.apply(x, w, bool(fwd), bool(dgrad), bool(wgrad))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -951,13 +1006,21 @@ class DenseEstimatorFunction(torch.autograd.Function):
             want_dx = m > lowest
             dx = dw = None
             xm = xs[m - 1]
-            if want_dx and splitconv_takes(B, ocs[m - 1], xm.shape[1], H, W):  # as Conv3x3Function.backward: dx here, dw MIOpen's
+            # as Conv3x3Function.backward: dx and dw each on the split-bf16 kernel where ConvAct's predicates route them,
+            # what is left in ONE MIOpen call (a layer of which only the bias is trained needs neither)
+            ask_dx, ask_dw = want_dx, bool(need[2 * m])
+            if ask_dx and splitconv_takes(B, ocs[m - 1], xm.shape[1], H, W):
                 dx = splitconv(gy, ws[m - 1], transpose_flip=True)
-                if need[2 * m]:
-                    dw = torch.ops.aten.convolution_backward(gy, xm, ws[m - 1], None, *_conv_args(), [False, True, False])[1]
-            elif want_dx or need[2 * m]:  # (a layer of which only the bias is trained needs neither)
-                dx, dw, _ = torch.ops.aten.convolution_backward(gy, xm, ws[m - 1], None, *_conv_args(),
-                                                                [want_dx, bool(need[2 * m]), False])
+                ask_dx = False
+            if ask_dw and splitconv_wgrad_takes(B, xm.shape[1], ocs[m - 1], H, W):
+                dw = splitconv_wgrad(xm, gy)
+                ask_dw = False
+            if ask_dx or ask_dw:
+                dx_m, dw_m, _ = torch.ops.aten.convolution_backward(gy, xm, ws[m - 1], None, *_conv_args(), [ask_dx, ask_dw, False])
+                if ask_dx:
+                    dx = dx_m
+                if ask_dw:
+                    dw = dw_m
             grads[2 * m], grads[2 * m + 1] = (dw if need[2 * m] else None), gb
             if want_dx:
                 dxs.append((dx, m))

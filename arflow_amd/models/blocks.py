@@ -22,19 +22,32 @@ class ConvAct(nn.Sequential):
         """(forward, data gradient) on the split-bf16 kernel (AF.conv3x3): a CUDA fp32 4-D input of a 3x3 / stride 1 / padding 1 /
         dilation 1 layer under the package's own bias_act -- the conditions HeadConv.native spells out -- at a shape
         AF.splitconv_takes routes; the data gradient asks with the channel counts swapped, which is the call the kernel sees."""
-        c = self[0]
-        if not (AF.splitconv_enabled() and bias_act is AF.bias_leaky_relu and x.is_cuda and x.dtype == torch.float32 and
-                x.dim() == 4 and c.weight.dtype == torch.float32 and c.kernel_size == (3, 3) and c.stride == (1, 1) and
-                c.padding == (1, 1) and c.dilation == (1, 1) and c.groups == 1 and c.padding_mode == 'zeros'):
+        if not self._split_kind(x):
             return False, False
+        c = self[0]
         N, C, H, W = x.shape
         return AF.splitconv_takes(N, C, c.out_channels, H, W), AF.splitconv_takes(N, c.out_channels, C, H, W)
+
+    def split_wgrad_route(self, x):
+        """The weight gradient on the split-bf16 kernel: the same kind of layer and input, at a shape
+        AF.splitconv_wgrad_takes routes (asked with the layer's own (C, K))."""
+        if not self._split_kind(x):
+            return False
+        N, C, H, W = x.shape
+        return AF.splitconv_wgrad_takes(N, C, self[0].out_channels, H, W)
+
+    def _split_kind(self, x):
+        c = self[0]
+        return (AF.splitconv_enabled() and bias_act is AF.bias_leaky_relu and x.is_cuda and x.dtype == torch.float32 and
+                x.dim() == 4 and c.weight.dtype == torch.float32 and c.kernel_size == (3, 3) and c.stride == (1, 1) and
+                c.padding == (1, 1) and c.dilation == (1, 1) and c.groups == 1 and c.padding_mode == 'zeros')
 
     def forward(self, x):
         c, act = self[0], self[1]
         fwd, dgrad = self.split_route(x)
-        if fwd or dgrad:
-            y = AF.conv3x3(x, c.weight, fwd, dgrad)
+        wgrad = self.split_wgrad_route(x)
+        if fwd or dgrad or wgrad:
+            y = AF.conv3x3(x, c.weight, fwd, dgrad, wgrad)
         else:
             y = F.conv2d(x, c.weight, None, c.stride, c.padding, c.dilation, c.groups)
         if self.want_moments and y.is_cuda and bias_act is AF.bias_leaky_relu:

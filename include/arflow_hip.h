@@ -310,6 +310,18 @@ int arflow_splitconv_pack(const float* w, void* packed, int K, int C, int transp
 int arflow_splitconv_fwd(const float* x, const void* packed, float* y, int N, int C, int K, int H, int W,
                          arflow_stream_t stream);
 
+/* The weight gradient of the same convolution, dw[k,c,r,s] = sum_{n,h,w} dy[n,k,h,w] * x[n,c,h+r-1,w+s-1] (zero outside the
+ * image), with the same split of both operands and the same six products; the reduction runs over pixels, which NCHW keeps
+ * contiguous per channel, so nothing is transposed.  x: [N,C,H,W] and dy: [N,K,H,W] with dense planes (H*W apart) and batch
+ * strides x_bstride >= C*H*W, dy_bstride >= K*H*W floats (else ARFLOW_ESHAPE); dw: [K,C,3,3] packed, every element written
+ * (no accumulate-into).  The pixel range is cut into chunks whose partial sums go to `ws`
+ * (arflow_splitconv_wgrad_ws_bytes() bytes, 16-byte aligned, need not be initialised; < 0 = ARFLOW_ESHAPE) and are added in
+ * ascending order in float64 by a second kernel: fixed order, no atomics, two calls are bitwise equal.  ARFLOW_ESHAPE also
+ * where N*C*H*W, N*K*H*W or 9*K*C exceeds INT_MAX; ARFLOW_EPARAM for x, dy or dw off a 4-byte or ws off a 16-byte boundary. */
+long arflow_splitconv_wgrad_ws_bytes(int N, int C, int K, int H, int W);
+int arflow_splitconv_wgrad(const float* x, long x_bstride, const float* dy, long dy_bstride, float* dw, void* ws, int N, int C,
+                           int K, int H, int W, arflow_stream_t stream);
+
 /* ---- dense flow estimator: concatenating epilogue and gradient gather ---------------------------
  * FlowEstimatorDense (models/pwclite.py:48-66) runs five times x = cat([lrelu(conv(x) + bias), x], 1).
  *

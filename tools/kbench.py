@@ -784,6 +784,46 @@ def main():
         for Cl, Kl in layers:
             print('splitconv error %4d->%-4d at 1x%dx%d: fwd %6.2f / %6.2f u   dgrad %6.2f / %6.2f u   (kernel / MIOpen, u = 2^-24)' % (
                 (Cl, Kl, h, w) + err_vs_float64(Cl, Kl, h, w)), flush=True)
+    if want('splitconv_wgrad'):  # the wide layers' weight gradient (csrc/splitconv_wgrad.hip) next to MIOpen's call, same buffers
+        conv_args = ([1, 1], [1, 1], [1, 1], False, [0, 0], 1)
+        layers = ((147, 128), (275, 128), (403, 96), (499, 64), (563, 32), (597, 128), (64, 32))
+        U = 2.0 ** -24
+
+        def wg_spread(fn):  # three rounds of --iters: (median, min, max) in us
+            ts = sorted(timeit(fn, args.iters) for _ in range(3))
+            MANIFEST[-1].update(name='splitconv_wgrad', shape=[], us=ts[1])
+            return ts[1], ts[0], ts[2]
+
+        def wg_call(x, gy, dw, ws):
+            N, C, h, w = x.shape
+            return lib.arflow_splitconv_wgrad(p(x), C * h * w, p(gy), gy.shape[1] * h * w, p(dw), p(ws), N, C, gy.shape[1], h, w, s)
+
+        print('splitconv_wgrad: time in us as median (min .. max) of 3 x %d calls; kernel = partial sums + finish; MIOpen = '
+              'aten.convolution_backward [False, True, False] with the layout copies it launches; TF = fp32-equivalent TFLOP/s of the kernel' % args.iters)
+        for _, h, w in levels[::-1]:
+            for Cl, Kl in layers:
+                x = 3.0 + torch.randn(B2, Cl, h, w, device=dev, generator=g)
+                gy = 3.0 + torch.randn(B2, Kl, h, w, device=dev, generator=g)
+                wt = torch.empty(Kl, Cl, 3, 3, device=dev)
+                dw = torch.empty_like(wt)
+                ws = torch.empty(lib.arflow_splitconv_wgrad_ws_bytes(B2, Cl, Kl, h, w), device=dev, dtype=torch.uint8)
+                assert wg_call(x, gy, dw, ws) == 0
+                flop = 2.0 * B2 * h * w * Cl * Kl * 9
+                a = wg_spread(lambda: wg_call(x, gy, dw, ws))
+                b = wg_spread(lambda: torch.ops.aten.convolution_backward(gy, x, wt, None, *conv_args, [False, True, False]))
+                print('splitconv_wgrad %-24s kernel %8.1f (%8.1f .. %8.1f)  MIOpen %8.1f (%8.1f .. %8.1f)  %5.2fx  %6.1f TF' % (
+                    [B2, Cl, Kl, h, w], a[0], a[1], a[2], b[0], b[1], b[2], b[0] / a[0], flop / a[0] / 1e6), flush=True)
+                if (h, w) == (levels[-1][1], levels[-1][2]):  # the full reduction, once: e against float64 on the CPU
+                    # over the first 8 x 8 channel pairs: the same reduction length at 1/1000 of the float64 work
+                    xd, gd = x[:, :8].double().cpu(), gy[:, :8].double().cpu()
+                    w0 = torch.zeros(8, 8, 3, 3, dtype=torch.float64, requires_grad=True)
+                    ref = torch.autograd.grad(torch.nn.functional.conv2d(xd, w0, None, 1, 1), w0, gd)[0]
+                    sc = torch.autograd.grad(torch.nn.functional.conv2d(xd.abs(), w0, None, 1, 1), w0, gd.abs())[0]
+                    e = lambda t: float(((t[:8, :8].double().cpu() - ref).abs() / sc).max()) / U
+                    lib_e = max(e(torch.ops.aten.convolution_backward(gy, x, wt, None, *conv_args, [False, True, False])[1]) for _ in range(2))
+                    print('splitconv_wgrad error %4d->%-4d at %dx%dx%d (%d terms): dw %6.2f / %6.2f u   (kernel / MIOpen, u = 2^-24)' % (
+                        Cl, Kl, B2, h, w, B2 * h * w, e(dw), lib_e), flush=True)
+                del x, gy, ws
     if want('dense'):  # the dense estimator's concatenating epilogue and gradient gather (csrc/dense.hip), five layers x four levels
         import ctypes
         from arflow_amd.functional import _DenseSrc
