@@ -73,6 +73,7 @@ PROTOTYPES = {
     'arflow_splitconv_pack_bytes': [c_i, c_i],
     'arflow_splitconv_pack': [c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'arflow_splitconv_fwd': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_splitconv_fwd_ex': [c_fp, c_l, c_fp, c_fp, c_l, c_fp, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_splitconv_wgrad_ws_bytes': [c_i, c_i, c_i, c_i, c_i],
     'arflow_splitconv_wgrad': [c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_dense_cat_fwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_l, c_f, c_fp],

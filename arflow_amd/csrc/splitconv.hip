@@ -30,6 +30,11 @@
 // that, 13 u for fp32 partial sums of 16, 4.7 u with the per-block restart, and with the small products first as well
 // the figure in tests/test_splitconv_cpu.py.)  No atomics, no split of the reduction: two calls are bitwise equal, in
 // every mode.
+//
+// Batch strides of x and y are arguments (planes, rows and columns dense): a channel slice of a larger tensor is read, and a
+// channel slot of one written, in place.  The store can apply bias + LeakyReLU (a runtime branch; the loop above it is the
+// same code).  The dense flow estimator runs its five layers that way inside the one tensor x6:
+// layer k reads x6[:, off:] and writes x6[:, off - K:off]; no element is both read and written, which __restrict__ needs.
 #include <climits>
 #include <cstdint>
 
@@ -89,9 +94,10 @@ __global__ __launch_bounds__(NT) void splitconv_pack_kernel(const float* __restr
 }
 
 template <int KT, int PW>
-__global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restrict__ x, const bf16x8* __restrict__ packed,
-                                                          float* __restrict__ y, int C, int K, int H, int W, int nkt, int ncs,
-                                                          int kt_first, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restrict__ x, long x_bs, const bf16x8* __restrict__ packed,
+                                                          float* __restrict__ y, long y_bs, const float* __restrict__ bias, int act,
+                                                          float slope, int C, int K, int H, int W, int nkt, int ncs, int kt_first,
+                                                          int tiles_x, int tiles_y) {
   using G = Geo<PW>;
   extern __shared__ __align__(16) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -118,7 +124,7 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
     prow[pt] = (2 * wv + pt) * G::PR + r / PW;
     pbase[pt] = (prow[pt] * G::HW + pcol) * PIX_BYTES + hh * 16;
   }
-  const float* xn = x + (long)n * C * H * W;
+  const float* xn = x + (long)n * x_bs;  // the sample's planes are dense; the batch stride is the caller's
   const long HWl = (long)H * W;
 
   for (int cb = 0; cb < C; cb += CB) {
@@ -198,7 +204,25 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
       for (int kt = 0; kt < KT; ++kt) tot[pt][kt] = tot[pt][kt] + acc[pt][kt];
   }
   // ---- store: accumulator register i of lane (r, hh) is output channel (i & 3) + 8 (i >> 2) + 4 hh of its tile, pixel r
-  float* yn = y + (long)n * K * HWl;
+  // act: the dense estimator's epilogue, bias_act_fwd_kernel's arithmetic (v += b; v > 0 ? v : v * slope), applied to the
+  // totals in registers under ONE uniform branch, the bias index clamped so that the lane's 16 KT loads need no guard and go
+  // out together.  (One branch and one guarded load per store cost every call 1.7 %, with or without the epilogue.)
+  if (act) {
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int k = 32 * (kt0 + kt) + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        const float b = bias ? bias[k < K ? k : K - 1] : 0.f;
+#pragma unroll
+        for (int pt = 0; pt < 2; ++pt) {
+          float v = tot[pt][kt][i];
+          v += b;
+          tot[pt][kt][i] = v > 0.f ? v : v * slope;
+        }
+      }
+  }
+  float* yn = y + (long)n * y_bs;
   const int gw = w0 + pcol;
 #pragma unroll
   for (int pt = 0; pt < 2; ++pt) {
@@ -219,9 +243,18 @@ inline bool pack_shape_ok(int K, int C) {
   return K > 0 && C > 0 && (long)K * C * 9 <= INT_MAX && (long)9 * tiles32(K) * 2 * tiles32(C) * 64 <= INT_MAX / 8;
 }
 
+struct Ends {  // where the input and the output live, and what the store does
+  const float* x;
+  long x_bs;
+  float* y;
+  long y_bs;
+  const float* bias;
+  int act;
+  float slope;
+};
+
 template <int KT, int PW>
-int launch(const float* x, const bf16x8* packed, float* y, int N, int C, int K, int H, int W, int kt_first, int chunks,
-           hipStream_t st) {
+int launch(const Ends& ends, const bf16x8* packed, int N, int C, int K, int H, int W, int kt_first, int chunks, hipStream_t st) {
   using G = Geo<PW>;
   static bool attr_set = false;  // more than 64 KB of dynamic LDS has to be asked for once per kernel
   if (!attr_set) {
@@ -232,16 +265,16 @@ int launch(const float* x, const bf16x8* packed, float* y, int N, int C, int K, 
   }
   const int tx = (W + PW - 1) / PW, ty = (H + G::TH - 1) / G::TH;
   const dim3 grid((unsigned)((long)N * tx * ty), (unsigned)chunks);
-  hipLaunchKernelGGL((splitconv_kernel<KT, PW>), grid, dim3(NT), G::LDS_BYTES, st, x, packed, y, C, K, H, W, tiles32(K),
-                     2 * tiles32(C), kt_first, tx, ty);
+  hipLaunchKernelGGL((splitconv_kernel<KT, PW>), grid, dim3(NT), G::LDS_BYTES, st, ends.x, ends.x_bs, packed, ends.y, ends.y_bs, ends.bias,
+                     ends.act, ends.slope, C, K, H, W, tiles32(K), 2 * tiles32(C), kt_first, tx, ty);
   return af_launch_status();
 }
 
 template <int PW>
-int launch_kt(int KT, const float* x, const bf16x8* packed, float* y, int N, int C, int K, int H, int W, int kt_first, int chunks,
+int launch_kt(int KT, const Ends& e, const bf16x8* packed, int N, int C, int K, int H, int W, int kt_first, int chunks,
               hipStream_t st) {
-  return KT == 1 ? launch<1, PW>(x, packed, y, N, C, K, H, W, kt_first, chunks, st)
-                 : launch<2, PW>(x, packed, y, N, C, K, H, W, kt_first, chunks, st);
+  return KT == 1 ? launch<1, PW>(e, packed, N, C, K, H, W, kt_first, chunks, st)
+                 : launch<2, PW>(e, packed, N, C, K, H, W, kt_first, chunks, st);
 }
 }  // namespace
 
@@ -265,15 +298,21 @@ extern "C" int arflow_splitconv_pack(const float* w, void* packed, int K, int C,
   return af_launch_status();
 }
 
-extern "C" int arflow_splitconv_fwd(const float* x, const void* packed, float* y, int N, int C, int K, int H, int W,
-                                    arflow_stream_t stream) {
+extern "C" int arflow_splitconv_fwd_ex(const float* x, long x_bstride, const void* packed, float* y, long y_bstride,
+                                       const float* bias, int act, float negative_slope, int N, int C, int K, int H, int W,
+                                       arflow_stream_t stream) {
   af_clear_stale_error();
   AF_REQUIRE_PTR(x);
   AF_REQUIRE_PTR(packed);
   AF_REQUIRE_PTR(y);
   AF_REQUIRE(N > 0 && C > 0 && K > 0 && H > 0 && W > 0, ARFLOW_ESHAPE);
   AF_REQUIRE((long)N * C * H * W <= INT_MAX && (long)N * K * H * W <= INT_MAX && pack_shape_ok(K, C), ARFLOW_ESHAPE);
+  AF_REQUIRE(x_bstride >= (long)C * H * W && y_bstride >= (long)K * H * W, ARFLOW_ESHAPE);
+  AF_REQUIRE(x_bstride <= INT_MAX / N && y_bstride <= INT_MAX / N, ARFLOW_ESHAPE);  // N * stride within INT_MAX
+  AF_REQUIRE(act == 0 || act == 1, ARFLOW_EPARAM);
+  AF_REQUIRE(act == 1 || bias == nullptr, ARFLOW_EPARAM);
   AF_REQUIRE(((uintptr_t)packed & 15) == 0, ARFLOW_EPARAM);
+  const Ends ends{x, x_bstride, y, y_bstride, bias, act, negative_slope};
   // pixel tile: 32 x 1 where the rows are long enough, else 16 x 2 or 8 x 4 (fewer columns of padding at W = 80, 40, 20)
   const auto waste = [&](int pw) {
     const int th = 8 * (32 / pw);
@@ -290,10 +329,16 @@ extern "C" int arflow_splitconv_fwd(const float* x, const void* packed, float* y
     const int kt = part == 0 ? base + 1 : base, cnt = part == 0 ? extra : chunks - extra, first = part == 0 ? 0 : extra * (base + 1);
     if (cnt == 0) continue;
     int rc;
-    if (PW == 32) rc = launch_kt<32>(kt, x, pk, y, N, C, K, H, W, first, cnt, st);
-    else if (PW == 16) rc = launch_kt<16>(kt, x, pk, y, N, C, K, H, W, first, cnt, st);
-    else rc = launch_kt<8>(kt, x, pk, y, N, C, K, H, W, first, cnt, st);
+    if (PW == 32) rc = launch_kt<32>(kt, ends, pk, N, C, K, H, W, first, cnt, st);
+    else if (PW == 16) rc = launch_kt<16>(kt, ends, pk, N, C, K, H, W, first, cnt, st);
+    else rc = launch_kt<8>(kt, ends, pk, N, C, K, H, W, first, cnt, st);
     if (rc != ARFLOW_OK) return rc;
   }
   return ARFLOW_OK;
+}
+
+extern "C" int arflow_splitconv_fwd(const float* x, const void* packed, float* y, int N, int C, int K, int H, int W,
+                                    arflow_stream_t stream) {
+  // packed strides, plain store
+  return arflow_splitconv_fwd_ex(x, (long)C * H * W, packed, y, (long)K * H * W, nullptr, 0, 0.f, N, C, K, H, W, stream);
 }

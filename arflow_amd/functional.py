@@ -719,24 +719,52 @@ def _splitconv_rule(N, C, K, H, W):
     return False
 
 
-def splitconv(x, w, transpose_flip=False):
-    """conv2d(x, w, padding=1) through arflow_splitconv_pack + arflow_splitconv_fwd (no autograd); transpose_flip: the data
-    gradient of that convolution for x = dy, i.e. conv2d(x, w.transpose(0, 1).flip(2, 3), padding=1)."""
-    _need_gpu(x, w)
+def splitconv(x, w, transpose_flip=False, out=None, bias=None, slope=None):
+    """conv2d(x, w, padding=1) through arflow_splitconv_pack + arflow_splitconv_fwd_ex (no autograd); transpose_flip: the data
+    gradient of that convolution for x = dy, i.e. conv2d(x, w.transpose(0, 1).flip(2, 3), padding=1).
+    x may be a channel slice of a larger tensor (dense planes, free batch stride: read in place).  out: an [N,K,H,W] view with
+    dense planes, e.g. a channel slot of a larger tensor, written in place and returned; it may share x's buffer but must not
+    overlap x.  slope selects the epilogue: the result is leaky_relu(conv + bias, slope), bias [K] or None (bias needs slope)."""
+    _need_gpu(x, w, out, bias)
     if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or x.shape[1] != w.shape[0 if transpose_flip else 1]:
         raise ValueError('splitconv expects x [N,C,H,W] and w [K,C,3,3] (transpose_flip: x [N,K,H,W])')
-    x, w = x.contiguous(), w.contiguous()
+    x, x_bs = _batch_strided(x)
+    w = w.contiguous()
     N, C, H, W = x.shape
     K = int(w.shape[1 if transpose_flip else 0])
+    if bias is not None and (slope is None or bias.numel() != K):
+        raise ValueError('splitconv: bias holds one value per output channel and needs slope (the epilogue is bias + LeakyReLU)')
     nbytes = _lib.load().arflow_splitconv_pack_bytes(K, C)
     if nbytes < 0:
         _lib.check(int(nbytes), 'arflow_splitconv_pack_bytes')
     packed = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-    y = torch.empty(N, K, H, W, device=x.device, dtype=torch.float32)
+    if out is None:
+        y, y_bs = torch.empty(N, K, H, W, device=x.device, dtype=torch.float32), K * H * W
+    else:
+        y, y_bs = out, (int(out.stride(0)) if N > 1 else K * H * W)
+        if tuple(y.shape) != (N, K, H, W) or _batch_strided(y)[0] is not y:
+            raise ValueError('splitconv: out must be an [N,K,H,W] view with dense planes (a channel slot of a larger tensor)')
+        if not _disjoint(x, x_bs, y, y_bs):
+            raise ValueError('splitconv: out overlaps x')
+    bias = None if bias is None else bias.contiguous()
     with torch.cuda.device_of(x):
         _call('arflow_splitconv_pack', _p(w), _p(packed), int(w.shape[0]), int(w.shape[1]), int(bool(transpose_flip)), _stream())
-        _call('arflow_splitconv_fwd', _p(x), _p(packed), _p(y), N, C, K, H, W, _stream())
+        _call('arflow_splitconv_fwd_ex', _p(x), x_bs, _p(packed), _p(y), y_bs, _p(bias), int(slope is not None),
+              float(slope or 0.0), N, C, K, H, W, _stream())
     return y
+
+
+def _disjoint(x, x_bs, y, y_bs):
+    """Whether the batch-strided [N,C,H,W] views x and y share no element (byte ranges; conservative where the strides differ)."""
+    N, hw = x.shape[0], x.shape[2] * x.shape[3]
+    cx, cy = x.shape[1] * hw, y.shape[1] * hw
+    d = (y.data_ptr() - x.data_ptr()) // 4  # y's first element, in floats from x's
+    if d >= (N - 1) * x_bs + cx or d + (N - 1) * y_bs + cy <= 0:
+        return True
+    if x_bs != y_bs:
+        return False
+    r = d % x_bs  # same lattice of samples: y's channels must fall in the gap x leaves in every period
+    return r >= cx and r + cy <= x_bs
 
 
 _SPLITCONV_WGRAD = __import__('os').environ.get('ARFLOW_SPLITCONV_WGRAD', '1') != '0'  # A/B switch: 0 = MIOpen's weight gradients
@@ -908,9 +936,13 @@ def dense_grad_gather(sources, oc, act=None, slope=0.1, want_bias=False):
     act_bs = 0
     if act is not None:
         _need_gpu(act)
-        if act.dim() != 4 or act.shape[0] != B or tuple(act.shape[2:]) != (H, W) or act.shape[1] < oc or not act.is_contiguous():
+        ok = act.dim() == 4 and act.shape[0] == B and tuple(act.shape[2:]) == (H, W) and act.shape[1] >= oc
+        if ok and act.is_contiguous():
+            act_bs = act.shape[1] * hw
+        elif ok and _batch_strided(act)[0] is act:  # a channel slice of a larger tensor (the in-place estimator's x6), read in place
+            act_bs = int(act.stride(0)) if B > 1 else act.shape[1] * hw
+        else:
             raise ValueError('dense_grad_gather: act must be a contiguous [B,>=oc,H,W] tensor')
-        act_bs = act.shape[1] * hw
     gy = torch.empty(B, oc, H, W, device=t0.device, dtype=torch.float32)
     rows = None
     if want_bias:
@@ -922,6 +954,30 @@ def dense_grad_gather(sources, oc, act=None, slope=0.1, want_bias=False):
         _call('arflow_dense_grad_gather', ctypes.cast(arr, ctypes.c_void_p), len(sources), _p(act), act_bs, _p(gy), _p(rows), B,
               oc, hw, float(slope), _stream(), key=(B, oc, hw, len(sources), int(act is not None)))
     return gy, (None if rows is None else rows.sum(0))
+
+
+_DENSE_INPLACE = __import__('os').environ.get('ARFLOW_DENSE_INPLACE', '1') != '0'  # A/B switch: 0 = dense_cat into fresh tensors
+
+
+def dense_inplace_enabled():
+    return _DENSE_INPLACE
+
+
+def _inplace_wgrad_takes(N, C, K, H, W):
+    """splitconv_wgrad_takes on the in-place path of DenseEstimatorFunction, where x_k is a channel slice of x_6: our kernel
+    reads the slice in place, MIOpen's weight gradient would have ATen copy it contiguous first.  Measured per layer with the
+    copy included (profiles/dense_inplace_kbench.log)."""
+    if splitconv_wgrad_takes(N, C, K, H, W):
+        return True
+    return _SPLITCONV and _SPLITCONV_WGRAD and _inplace_wgrad_rule(int(N), int(C), int(K), int(H), int(W))
+
+
+def _inplace_wgrad_rule(N, C, K, H, W):
+    # the three layers _splitconv_wgrad_rule leaves to MIOpen at 96x160, measured at N = 16 against MIOpen's call on the slice
+    # (solver + layout copies + ATen's contiguous copy of x_k): 275->128 -103 us and 403->96 -230 us, ranges apart; 147->128 -24 us,
+    # ranges apart in one job and touching in three others -- a tie in time, taken for the 144 MB copy it does not allocate.
+    # Never below that size.
+    return H * W >= 96 * 160 and N * H * W >= 16 * 96 * 160 and 128 <= C < 448 and 96 <= K <= 128
 
 
 class DenseEstimatorFunction(torch.autograd.Function):
@@ -936,7 +992,12 @@ class DenseEstimatorFunction(torch.autograd.Function):
     m's activation is gathered by ONE launch from every tensor that holds a slice of it -- the gradient of x_6, the head's
     data gradient and the data gradients of the layers above -- in the nesting autograd's accumulation has, so the values
     MIOpen's backward kernels receive are bit-identical to the composed path's.  Saves x_1 .. x_6 (the activations live
-    inside them) and the weights."""
+    inside them) and the weights.
+
+    In place: where splitconv_takes routes all five layers' forwards, x_6 is allocated once, x copied
+    into its tail, and layer k reads x_6[:, off_k:] and writes lrelu(conv + b_k) into x_6[:, off_k - oc_k:off_k] through the
+    kernel's epilogue -- the positions torch.cat gives them; no dense_cat launch, x_1 .. x_5 are views of the one saved x_6.
+    ARFLOW_DENSE_INPLACE=0 keeps the path above everywhere."""
 
     @staticmethod
     def forward(ctx, x, slope, *params):
@@ -946,29 +1007,49 @@ class DenseEstimatorFunction(torch.autograd.Function):
         slope = float(slope)
         ws, bs = params[0:10:2], params[1:10:2]
         w_head, b_head = params[10], params[11]
-        xs = [x.contiguous()]
-        for w, b in zip(ws, bs):
-            xk = xs[-1]
-            if splitconv_takes(xk.shape[0], xk.shape[1], w.shape[0], xk.shape[2], xk.shape[3]):  # ConvAct's routing, same kernel
-                y = splitconv(xk, w)
-            else:
-                y = torch.nn.functional.conv2d(xk, w, None, 1, 1)
-            xs.append(dense_cat(y, b, xk, slope))
-        x6 = xs[-1]
+        ocs = [int(w.shape[0]) for w in ws]
+        B, C1, H, W = x.shape
+        cins = [C1 + sum(ocs[:k]) for k in range(5)]
+        inplace = _DENSE_INPLACE and all(splitconv_takes(B, c, oc, H, W) for c, oc in zip(cins, ocs))
+        if inplace:
+            off = sum(ocs)
+            x6 = torch.empty(B, C1 + off, H, W, device=x.device, dtype=torch.float32)
+            x6[:, off:].copy_(x)  # the only copy left: x_k = x6[:, off_k:] from here on
+            for w, b, oc in zip(ws, bs, ocs):
+                splitconv(x6[:, off:], w, out=x6[:, off - oc:off], bias=b, slope=slope)
+                off -= oc
+        else:
+            xs = [x.contiguous()]
+            for w, b in zip(ws, bs):
+                xk = xs[-1]
+                if splitconv_takes(xk.shape[0], xk.shape[1], w.shape[0], xk.shape[2], xk.shape[3]):  # ConvAct's routing, same kernel
+                    y = splitconv(xk, w)
+                else:
+                    y = torch.nn.functional.conv2d(xk, w, None, 1, 1)
+                xs.append(dense_cat(y, b, xk, slope))
+            x6 = xs[-1]
         B, C6, H, W = x6.shape
         w_head = w_head.contiguous()
         flow = torch.empty(B, 2, H, W, device=x.device, dtype=torch.float32)
         with torch.cuda.device_of(x6):
             _call('arflow_headconv_fwd', _p(x6), _p(w_head), _p(b_head.contiguous()), _p(flow), B, C6, H, W, _stream())
-        ctx.save_for_backward(*xs, *ws, w_head)
-        ctx.slope = slope
+        if inplace:
+            ctx.save_for_backward(x6, *ws, w_head)
+        else:
+            ctx.save_for_backward(*xs, *ws, w_head)
+        ctx.slope, ctx.inplace = slope, inplace
         ctx.set_materialize_grads(False)
         return x6, flow
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gx6, gflow):
-        xs, ws, w_head = ctx.saved_tensors[:6], ctx.saved_tensors[6:11], ctx.saved_tensors[11]
+        if ctx.inplace:  # x_1 .. x_5 are channel suffixes of the one saved x_6
+            x6, ws, w_head = ctx.saved_tensors[0], ctx.saved_tensors[1:6], ctx.saved_tensors[6]
+            tail = [int(w.shape[0]) for w in ws]
+            xs = [x6[:, sum(tail[m:]):] for m in range(5)] + [x6]
+        else:
+            xs, ws, w_head = ctx.saved_tensors[:6], ctx.saved_tensors[6:11], ctx.saved_tensors[11]
         need = ctx.needs_input_grad
         grads = [None] * 14
         if gx6 is None and gflow is None:
@@ -1012,7 +1093,7 @@ class DenseEstimatorFunction(torch.autograd.Function):
             if ask_dx and splitconv_takes(B, ocs[m - 1], xm.shape[1], H, W):
                 dx = splitconv(gy, ws[m - 1], transpose_flip=True)
                 ask_dx = False
-            if ask_dw and splitconv_wgrad_takes(B, xm.shape[1], ocs[m - 1], H, W):
+            if ask_dw and (_inplace_wgrad_takes if ctx.inplace else splitconv_wgrad_takes)(B, xm.shape[1], ocs[m - 1], H, W):
                 dw = splitconv_wgrad(xm, gy)
                 ask_dw = False
             if ask_dx or ask_dw:

@@ -310,6 +310,20 @@ int arflow_splitconv_pack(const float* w, void* packed, int K, int C, int transp
 int arflow_splitconv_fwd(const float* x, const void* packed, float* y, int N, int C, int K, int H, int W,
                          arflow_stream_t stream);
 
+/* arflow_splitconv_fwd with free batch strides and an optional epilogue at the store; arflow_splitconv_fwd is this call with
+ * x_bstride = C*H*W, y_bstride = K*H*W, bias = NULL, act = 0.  x: [N,C,H,W] and y: [N,K,H,W] with dense planes, rows and
+ * columns and batch strides x_bstride >= C*H*W, y_bstride >= K*H*W floats (else ARFLOW_ESHAPE; also where N*x_bstride or
+ * N*y_bstride exceeds INT_MAX): a channel slice of a larger tensor is read, and a channel slot of one written, in place.  The
+ * loads and stores are scalar: no alignment beyond 4 bytes is asked of x and y.  PRECONDITION: no element is both read and
+ * written.  x and y may be DISJOINT channel ranges of one buffer -- the dense estimator's layer reads x6[:, off:] and writes
+ * x6[:, off-K:off] -- but must not overlap.
+ * act = 0 stores the sum as arflow_splitconv_fwd does; bias must then be NULL (ARFLOW_EPARAM).  act = 1 stores
+ * lrelu(sum + bias[k]) with arflow_bias_act_fwd's arithmetic (v += b; v > 0 ? v : v * negative_slope), b = 0.f for a NULL
+ * bias (the add is kept: -0 becomes +0, as in arflow_dense_cat_fwd).  Any other act: ARFLOW_EPARAM.  The sums, their order
+ * and so their bits are arflow_splitconv_fwd's. */
+int arflow_splitconv_fwd_ex(const float* x, long x_bstride, const void* packed, float* y, long y_bstride, const float* bias,
+                            int act, float negative_slope, int N, int C, int K, int H, int W, arflow_stream_t stream);
+
 /* The weight gradient of the same convolution, dw[k,c,r,s] = sum_{n,h,w} dy[n,k,h,w] * x[n,c,h+r-1,w+s-1] (zero outside the
  * image), with the same split of both operands and the same six products; the reduction runs over pixels, which NCHW keeps
  * contiguous per channel, so nothing is transposed.  x: [N,C,H,W] and dy: [N,K,H,W] with dense planes (H*W apart) and batch

@@ -784,6 +784,61 @@ def main():
         for Cl, Kl in layers:
             print('splitconv error %4d->%-4d at 1x%dx%d: fwd %6.2f / %6.2f u   dgrad %6.2f / %6.2f u   (kernel / MIOpen, u = 2^-24)' % (
                 (Cl, Kl, h, w) + err_vs_float64(Cl, Kl, h, w)), flush=True)
+    if want('dense_inplace'):  # the five dense layers at the top level as the in-place estimator calls them
+        conv_args = ([1, 1], [1, 1], [1, 1], False, [0, 0], 1)
+        _, h, w = levels[-1]
+        hw = h * w
+
+        def di_spread(fn):  # three rounds of --iters: (median, min, max) in us
+            ts = sorted(timeit(fn, args.iters) for _ in range(3))
+            MANIFEST[-1].update(name='dense_inplace', shape=[], us=ts[1])
+            return ts[1], ts[0], ts[2]
+        print('dense_inplace: time in us as median (min .. max) of 3 x %d calls.  fwd = arflow_splitconv_pack + arflow_splitconv_fwd on packed '
+              'tensors; fwd_ex = pack + arflow_splitconv_fwd_ex reading x6[:, K:] and writing lrelu(conv + b) into x6[:, :K]; wgrad: our '
+              'kernel reading the slice in place | MIOpen on the slice (ATen copies it contiguous first) | MIOpen on a packed x' % args.iters)
+        for Cl, Kl in ((147, 128), (275, 128), (403, 96), (499, 64), (563, 32)):
+            x6 = torch.randn(B2, Kl + Cl, h, w, device=dev, generator=g)
+            xs = x6[:, Kl:]
+            x = xs.contiguous()
+            gy = 3.0 + torch.randn(B2, Kl, h, w, device=dev, generator=g)
+            wt = 0.05 * torch.randn(Kl, Cl, 3, 3, device=dev, generator=g)
+            bias = torch.randn(Kl, device=dev, generator=g)
+            y, dw = torch.empty_like(gy), torch.empty_like(wt)
+            pk = torch.empty(lib.arflow_splitconv_pack_bytes(Kl, Cl), device=dev, dtype=torch.uint8)
+            ws = torch.empty(lib.arflow_splitconv_wgrad_ws_bytes(B2, Cl, Kl, h, w), device=dev, dtype=torch.uint8)
+            bs = (Kl + Cl) * hw
+
+            def plain():
+                lib.arflow_splitconv_pack(p(wt), p(pk), Kl, Cl, 0, s)
+                return lib.arflow_splitconv_fwd(p(x), p(pk), p(y), B2, Cl, Kl, h, w, s)
+
+            def ex():
+                lib.arflow_splitconv_pack(p(wt), p(pk), Kl, Cl, 0, s)
+                return lib.arflow_splitconv_fwd_ex(p(xs), bs, p(pk), p(x6), bs, p(bias), 1, 0.1, B2, Cl, Kl, h, w, s)
+
+            def ex_packed():  # the epilogue alone: packed tensors
+                lib.arflow_splitconv_pack(p(wt), p(pk), Kl, Cl, 0, s)
+                return lib.arflow_splitconv_fwd_ex(p(x), Cl * hw, p(pk), p(y), Kl * hw, p(bias), 1, 0.1, B2, Cl, Kl, h, w, s)
+
+            def ex_plain():  # the strides alone: slice in, slot out, plain store
+                lib.arflow_splitconv_pack(p(wt), p(pk), Kl, Cl, 0, s)
+                return lib.arflow_splitconv_fwd_ex(p(xs), bs, p(pk), p(x6), bs, None, 0, 0.0, B2, Cl, Kl, h, w, s)
+
+            def wg():
+                return lib.arflow_splitconv_wgrad(p(xs), bs, p(gy), Kl * hw, p(dw), p(ws), B2, Cl, Kl, h, w, s)
+            assert plain() == 0 and ex() == 0 and ex_packed() == 0 and ex_plain() == 0 and wg() == 0
+            a, b, b1, b2 = di_spread(plain), di_spread(ex), di_spread(ex_packed), di_spread(ex_plain)
+            tag = '%-24s' % [B2, Cl, Kl, h, w]
+            print('dense_inplace fwd    %s %8.1f (%8.1f .. %8.1f)' % ((tag,) + a), flush=True)
+            print('dense_inplace fwd_ex %s %8.1f (%8.1f .. %8.1f)   %+6.1f us against fwd' % ((tag,) + b + (b[0] - a[0],)), flush=True)
+            print('dense_inplace fwd_ex %s %8.1f (%8.1f .. %8.1f)   %+6.1f us  packed tensors, epilogue on' % ((tag,) + b1 + (b1[0] - a[0],)), flush=True)
+            print('dense_inplace fwd_ex %s %8.1f (%8.1f .. %8.1f)   %+6.1f us  slice in, slot out, plain store' % ((tag,) + b2 + (b2[0] - a[0],)), flush=True)
+            c = di_spread(wg)
+            d = di_spread(lambda: torch.ops.aten.convolution_backward(gy, xs, wt, None, *conv_args, [False, True, False]))
+            e = di_spread(lambda: torch.ops.aten.convolution_backward(gy, x, wt, None, *conv_args, [False, True, False]))
+            print('dense_inplace wgrad  %s kernel %8.1f (%8.1f .. %8.1f) | MIOpen + copy %8.1f (%8.1f .. %8.1f) | MIOpen packed %8.1f '
+                  '(%8.1f .. %8.1f) | kernel - (MIOpen + copy) %+7.1f us' % ((tag,) + c + d + e + (c[0] - d[0],)), flush=True)
+            del x6, xs, x, gy, ws
     if want('splitconv_wgrad'):  # the wide layers' weight gradient (csrc/splitconv_wgrad.hip) next to MIOpen's call, same buffers
         conv_args = ([1, 1], [1, 1], [1, 1], False, [0, 0], 1)
         layers = ((147, 128), (275, 128), (403, 96), (499, 64), (563, 32), (597, 128), (64, 32))
