@@ -21,6 +21,11 @@
 // stages its next block while the other multiplies.  More than 64 output channels go over gridDim.y in chunks of equal
 // size (+-1 tile: no tile of zeros is multiplied).
 //
+// Operand fetch is software-pipelined: the weight and pixel fragments of a unit -- one (tap, step) in
+// pass 0, three of them in pass 1 -- are requested while the unit before it multiplies, into the second of two register
+// buffers (2 x 24 registers each at KT = 2: 251..253 in all), through both passes and across the block boundary; the
+// staging loads of three items go out together.  Which products are formed, and in which order, is untouched.
+//
 // Summation order is fixed.  Within a block of 32 input channels one MFMA accumulator chain starts from zero and takes, over
 // taps row-major and 16-channel steps ascending, FIRST the five small products of every step -- (w2,x0) (w1,x1) (w0,x2)
 // (w1,x0) (w0,x1), together 2^-8 of the block's sum, so that their 90 roundings are negligible -- and THEN the 18 (w0,x0)
@@ -126,36 +131,85 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
   }
   const float* xn = x + (long)n * x_bs;  // the sample's planes are dense; the batch stride is the caller's
   const long HWl = (long)H * W;
+  const unsigned HWu = (unsigned)(H * W);
+
+  // Weight fragments travel one unit ahead of the MFMAs that take them: two register buffers of three
+  // fragments per channel tile; while a unit multiplies out of one, the next unit's loads fill the other, and the wait before
+  // the MFMAs retires the older loads only.  The chain runs through both passes and from block to block: the first unit of a
+  // block does not depend on LDS and is in flight across the barriers and the staging.  The loads stand between two
+  // scheduling barriers that only plain ALU work may cross, so the compiler neither sinks them to their use
+  // nor hoists later ones until registers spill.
+  constexpr int SCHED_FREE = 0x2 | 0x4;  // VALU, SALU
+  const long tap_frags = (long)nkt * ncs * 64;  // fragments from a tap to the next
+  bf16x8 wq[2][KT][3];
+  const auto wload = [&](bf16x8 (&d)[KT][3], const bf16x8* base, long o0, long o1, long o2) __attribute__((always_inline)) {
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+      d[kt][0] = base[o0 + (long)kt * ncs * 64];
+      d[kt][1] = base[o1 + (long)kt * ncs * 64];
+      d[kt][2] = base[o2 + (long)kt * ncs * 64];
+    }
+  };
+  const bf16x8* wblk = packed + (long)kt0 * ncs * 64 + lane;  // the block's (tap 0, tile kt0, step 0) fragment of plane 0
+  wload(wq[0], wblk, 0, plane_frags, 2 * plane_frags);
+  // The pixel fragments likewise, out of LDS: byte offsets from the lane's pixel of tap (0, 0).
+  bf16x8 bq[2][2][3];
+  const auto bload = [&](bf16x8 (&d)[2][3], int o0, int o1, int o2) __attribute__((always_inline)) {
+#pragma unroll
+    for (int pt = 0; pt < 2; ++pt) {
+      d[pt][0] = *reinterpret_cast<const bf16x8*>(lds + pbase[pt] + o0);
+      d[pt][1] = *reinterpret_cast<const bf16x8*>(lds + pbase[pt] + o1);
+      d[pt][2] = *reinterpret_cast<const bf16x8*>(lds + pbase[pt] + o2);
+    }
+  };
 
   for (int cb = 0; cb < C; cb += CB) {
     if (cb) __syncthreads();  // every wave is done with the previous block's planes
     // ---- stage: 8 channels of one halo pixel per item, split, one 16-byte store per plane
-#pragma unroll 3  // 24 loads of a lane in flight together (all 48: spills at KT = 2)
-    for (int it = 0; it < (4 * G::NPIX + NT - 1) / NT; ++it) {
-      const int i = tid + it * NT;
-      if (i >= 4 * G::NPIX) break;
-      const int g = i / G::NPIX, pix = i - g * G::NPIX;
-      const int row = pix / G::HW, col = pix - row * G::HW;
-      const int gh = h0 - 1 + row, gw = w0 - 1 + col;
-      const bool inb = gh >= 0 && gh < H && gw >= 0 && gw < W;
-      const int c0 = cb + 8 * g;
-      const float* src = xn + (long)c0 * HWl + (inb ? gh * W + gw : 0);
-      float v[8];
+    // Three items at a time: their 24 loads go out together, ahead of a scheduling barrier, and are split and stored behind
+    // it (all 48: spills at KT = 2).  The loads are unconditional: the channel is clamped to C - 1 and the pixel to the
+    // plane's first, so every address lies inside x, and zero is selected afterwards (a guarded load is a branch of its own).
+    // Items past the last one (the final trip's tail) load item 0's addresses and store nothing.  Offsets within a sample
+    // fit 32 bits (C H W <= INT_MAX, host-checked).
+    constexpr int NIT = (4 * G::NPIX + NT - 1) / NT, GRP = 3;
+    static_assert(NIT % GRP == 0, "staging items per thread come in whole groups");
+#pragma unroll 1
+    for (int it0 = 0; it0 < NIT; it0 += GRP) {
+      float v[GRP][8];
+      int at[GRP], cfirst[GRP];  // LDS byte offset of the item (-1: store nothing) and its first channel (C: all zeros)
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = (inb && c0 + e < C) ? src[e * HWl] : 0.f;
-      bf16x8 o[3];
+      for (int u = 0; u < GRP; ++u) {
+        const int i_raw = tid + (it0 + u) * NT;
+        const bool live = i_raw < 4 * G::NPIX;
+        const int i = live ? i_raw : 0;
+        const int g = i / G::NPIX, pix = i - g * G::NPIX;
+        const int row = pix / G::HW, col = pix - row * G::HW;
+        const int gh = h0 - 1 + row, gw = w0 - 1 + col;
+        const bool inb = gh >= 0 && gh < H && gw >= 0 && gw < W;
+        const int c0 = cb + 8 * g;
+        const unsigned poff = inb ? gh * W + gw : 0;
+        at[u] = live ? pix * PIX_BYTES + g * 16 : -1;
+        cfirst[u] = inb ? c0 : C;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const Split s(v[e]);
-        o[0][e] = s.p[0], o[1][e] = s.p[1], o[2][e] = s.p[2];
+        for (int e = 0; e < 8; ++e) v[u][e] = xn[(unsigned)min(c0 + e, C - 1) * HWu + poff];
       }
-      unsigned char* dst = lds + pix * PIX_BYTES + g * 16;
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(dst + p * PLANE_BYTES) = o[p];
+      for (int u = 0; u < GRP; ++u) {
+        bf16x8 o[3];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const Split s(cfirst[u] + e < C ? v[u][e] : 0.f);
+          o[0][e] = s.p[0], o[1][e] = s.p[1], o[2][e] = s.p[2];
+        }
+        if (at[u] >= 0) {
+#pragma unroll
+          for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(lds + at[u] + p * PLANE_BYTES) = o[p];
+        }
+      }
     }
     __syncthreads();
     // ---- multiply: two passes of 9 taps x 2 k-steps; weight fragments from L2, pixel fragments from LDS, 12 KT MFMAs per step
-    const bf16x8* wblk = packed + ((long)kt0 * ncs + cb / 16) * 64 + lane;
     f32x16 acc[2][KT];
 #pragma unroll
     for (int pt = 0; pt < 2; ++pt)
@@ -163,41 +217,92 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
       for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[pt][kt][i] = 0.f;
+    // The block after this one, whose first unit the last trip requests.  After the last block there is none: the pointer is
+    // CLAMPED to this block, whose first unit is loaded once more and dropped -- no address outside `packed` is formed.
+    const bf16x8* const wnext = cb + CB < C ? wblk + 2 * 64 : wblk;
+    bload(bq[0], 0, PLANE_BYTES, 2 * PLANE_BYTES);  // the first unit's pixel fragments: the one LDS fetch that nothing covers
     // pass 0: the five small products of every tap and step, while the accumulator is small (their roundings are 2^-8 of the
-    // block's sum); pass 1: the (w0, x0) products on top -- 18 roundings at the block's magnitude instead of 108
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-      constexpr int NP[2] = {3, 1}, Q0[2] = {0, 5}, Q1[2] = {5, 6};
+    // block's sum).  A unit is one (tap, step): three planes of weights per channel tile and of pixels per pixel tile, 10 KT
+    // MFMAs.  The next unit's weights are requested before the unit's first MFMAs, its pixels behind them.
 #pragma unroll 1  // a row of taps per trip: unrolled further, the scheduler hoists pass 1's loads until registers spill
-      for (int trow = 0; trow < 3; ++trow)
+    for (int trow = 0; trow < 3; ++trow) {
+      const long wrow = 3 * trow * tap_frags;
+      const int brow = trow * G::HW * PIX_BYTES;
 #pragma unroll
-      for (int tcol = 0; tcol < 3; ++tcol) {
-        const int tap = 3 * trow + tcol;
-        const int toff = (trow * G::HW + tcol) * PIX_BYTES;
+      for (int j = 0; j < 6; ++j) {
+        constexpr int PA[5] = {2, 1, 0, 1, 0}, PB[5] = {0, 1, 2, 0, 1};  // (weight plane, input plane), smallest product first
+        const bool more = trow < 2;  // j == 5: the next row's first unit, else pass 1's first three (plane 0 of units 0..2)
+        __builtin_amdgcn_sched_barrier(SCHED_FREE);
+        if (j < 5) {
+          const long o = wrow + ((j + 1) >> 1) * tap_frags + ((j + 1) & 1) * 64;
+          wload(wq[(j + 1) & 1], wblk, o, o + plane_frags, o + 2 * plane_frags);
+        } else {
+          const long o = wrow + 3 * tap_frags;
+          wload(wq[0], wblk, more ? o : 0, more ? o + plane_frags : 64, more ? o + 2 * plane_frags : tap_frags);
+        }
+        __builtin_amdgcn_sched_barrier(SCHED_FREE);
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          bf16x8 a[KT][3], b[2][3];
+        for (int pt = 0; pt < 2; ++pt)
 #pragma unroll
           for (int kt = 0; kt < KT; ++kt)
+            acc[pt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[j & 1][kt][PA[0]], bq[j & 1][pt][PB[0]], acc[pt][kt], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(SCHED_FREE);
+        if (j < 5) {
+          const int o = brow + ((j + 1) >> 1) * PIX_BYTES + ((j + 1) & 1) * 32;
+          bload(bq[(j + 1) & 1], o, o + PLANE_BYTES, o + 2 * PLANE_BYTES);
+        } else {
+          const int o = brow + G::HW * PIX_BYTES;
+          bload(bq[0], more ? o : 0, more ? o + PLANE_BYTES : 32, more ? o + 2 * PLANE_BYTES : PIX_BYTES);
+        }
+        __builtin_amdgcn_sched_barrier(SCHED_FREE);
 #pragma unroll
-            for (int p = 0; p < NP[pass]; ++p) a[kt][p] = wblk[p * plane_frags + ((long)(tap * nkt + kt) * ncs + s) * 64];
+        for (int q = 1; q < 5; ++q)
 #pragma unroll
           for (int pt = 0; pt < 2; ++pt)
 #pragma unroll
-            for (int p = 0; p < NP[pass]; ++p)
-              b[pt][p] = *reinterpret_cast<const bf16x8*>(lds + pbase[pt] + toff + p * PLANE_BYTES + s * 32);
+            for (int kt = 0; kt < KT; ++kt)
+              acc[pt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[j & 1][kt][PA[q]], bq[j & 1][pt][PB[q]], acc[pt][kt], 0, 0, 0);
+      }
+    }
+    // pass 1: the (w0, x0) products on top -- 18 roundings at the block's magnitude instead of 108.  A unit is 2 KT MFMAs,
+    // shorter than a load takes: the units are requested three at a time (a buffer holds plane 0 of three consecutive units),
+    // so that three to six are in flight.
+#pragma unroll 1
+    for (int trow = 0; trow < 3; ++trow) {
+      const long wrow = 3 * trow * tap_frags;
+      const int brow = trow * G::HW * PIX_BYTES;
 #pragma unroll
-          for (int q = Q0[pass]; q < Q1[pass]; ++q) {  // (weight plane, input plane), smallest product first
-            constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+      for (int g = 0; g < 2; ++g) {
+        const bool more = trow < 2;  // g == 1: units 0..2 of the next row, else the next block's first unit of pass 0 (wnext)
+        __builtin_amdgcn_sched_barrier(SCHED_FREE);
+        if (g == 0) {  // units 3..5 of this row: (tap 1, step 1), (2, 0), (2, 1)
+          wload(wq[1], wblk, wrow + tap_frags + 64, wrow + 2 * tap_frags, wrow + 2 * tap_frags + 64);
+        } else {
+          const long o = wrow + 3 * tap_frags;
+          wload(wq[0], more ? wblk : wnext, more ? o : 0, more ? o + 64 : plane_frags, more ? o + tap_frags : 2 * plane_frags);
+        }
+        __builtin_amdgcn_sched_barrier(SCHED_FREE);
 #pragma unroll
-            for (int pt = 0; pt < 2; ++pt)
+        for (int p = 0; p < 3; ++p) {
 #pragma unroll
-              for (int kt = 0; kt < KT; ++kt)
-                acc[pt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kt][PA[q]], b[pt][PB[q]], acc[pt][kt], 0, 0, 0);
+          for (int pt = 0; pt < 2; ++pt)
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt)
+              acc[pt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[g][kt][p], bq[g][pt][p], acc[pt][kt], 0, 0, 0);
+          if (p == 0) {
+            __builtin_amdgcn_sched_barrier(SCHED_FREE);
+            if (g == 0) {
+              bload(bq[1], brow + PIX_BYTES + 32, brow + 2 * PIX_BYTES, brow + 2 * PIX_BYTES + 32);
+            } else {  // after the last row the next block is not staged yet: this row's fragments are read again and dropped
+              const int o = more ? brow + G::HW * PIX_BYTES : brow;
+              bload(bq[0], o, o + 32, o + PIX_BYTES);
+            }
+            __builtin_amdgcn_sched_barrier(SCHED_FREE);
           }
         }
       }
     }
+    wblk = wnext;
 #pragma unroll
     for (int pt = 0; pt < 2; ++pt)
 #pragma unroll
