@@ -2,10 +2,9 @@
 // gfx950: the dense flow estimators' 147..563 -> 128..32 layers and the context network's 597 -> 128, forward and -- with
 // the roles of the channel axes swapped and the taps flipped by the packer -- data gradient.
 //
-// Arithmetic.  An fp32 number splits EXACTLY into three bf16 numbers, b0 = bf16(x), b1 = bf16(x - b0), b2 = bf16(x - b0 - b1)
-// (round to nearest even; both subtractions are exact, b0 + b1 + b2 == x bit for bit).  A product x * w is then nine bf16
-// products, each exact in the MFMA's fp32 accumulator; the three smallest (b1 w2, b2 w1, b2 w2) are below 2^-24 of the
-// product and dropped, the other six are accumulated: (w2,x0) (w1,x1) (w0,x2) (w1,x0) (w0,x1) and (w0,x0).
+// Arithmetic.  An fp32 number splits EXACTLY into three bf16 numbers, b0 + b1 + b2 == x bit for bit (splitbf16.hpp: Split).
+// A product x * w is then nine bf16 products, each exact in the MFMA's fp32 accumulator; the three smallest (b1 w2, b2 w1,
+// b2 w2) are below 2^-24 of the product and dropped, the other six are accumulated: (w2,x0) (w1,x1) (w0,x2) (w1,x0) (w0,x1) (w0,x0).
 // Six v_mfma_f32_32x32x16_bf16 per 32x32x16 block of fp32-accurate products: 1/6 of the bf16 rate, 2.7x the fp32 MFMA's.
 //
 // GEMM view: D[k][pixel] = sum over (tap, c) of A[k][(tap, c)] * B[(tap, c)][pixel].  A = weights, packed once per call by
@@ -43,18 +42,16 @@
 #include <climits>
 #include <cstdint>
 
-#include "common.hpp"
+#include "splitbf16.hpp"
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace splitbf16;
 
 constexpr int NT = 256;                       // 4 waves
 constexpr int CB = 32;                        // input channels per LDS block (two MFMA k-steps)
 constexpr int PLANE_BYTES = CB * 2;           // one pixel's channels of one plane
 constexpr int PIX_BYTES = 3 * PLANE_BYTES + 16;  // 208: see the header
 constexpr int FRAG = 64 * 8;                  // bf16 per wave fragment (32 rows x 16 k)
-constexpr int MAX_KT = 2;                     // output-channel tiles per workgroup (template KT: 1 or 2)
 
 template <int PW>
 struct Geo {
@@ -66,16 +63,6 @@ struct Geo {
   static constexpr int LDS_BYTES = NPIX * PIX_BYTES;
 };
 
-struct Split {
-  __bf16 p[3];
-  __device__ __forceinline__ explicit Split(float v) {
-    p[0] = (__bf16)v;
-    const float r1 = v - (float)p[0];
-    p[1] = (__bf16)r1;
-    p[2] = (__bf16)(r1 - (float)p[1]);
-  }
-};
-
 // packed: [plane 3][tap 9][nkt = ceil(K / 32)][ncs = 2 ceil(C / 32)][lane 64][8], element j of lane (r = lane & 31, h = lane >> 5)
 // = plane of W[k = 32 kt + r][c = 16 cs + 8 h + j][tap], zero where k >= K or c >= C.  transpose_flip: W = w'[c][k][8 - tap].
 __global__ __launch_bounds__(NT) void splitconv_pack_kernel(const float* __restrict__ w, bf16x8* __restrict__ packed, int wK, int wC,
@@ -85,15 +72,14 @@ __global__ __launch_bounds__(NT) void splitconv_pack_kernel(const float* __restr
   if (f >= nfrag) return;
   const int lane = f & 63, cs = (f >> 6) % ncs, kt = ((f >> 6) / ncs) % nkt, tap = (f >> 6) / (ncs * nkt);
   const int k = 32 * kt + (lane & 31), c0 = 16 * cs + 8 * (lane >> 5);
-  bf16x8 o[3];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
+  const auto weight = [&](int j) {
     const int c = c0 + j;
     float v = 0.f;
     if (k < Kout && c < Cin) v = transpose_flip ? w[((long)c * wC + k) * 9 + (8 - tap)] : w[((long)k * wC + c) * 9 + tap];
-    const Split s(v);
-    o[0][j] = s.p[0], o[1][j] = s.p[1], o[2][j] = s.p[2];
-  }
+    return v;
+  };
+  bf16x8 o[3];
+  split8(weight, o);
 #pragma unroll
   for (int p = 0; p < 3; ++p) packed[(long)p * nfrag + f] = o[p];
 }
@@ -114,12 +100,7 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
   const long plane_frags = (long)9 * nkt * ncs * 64;  // fragments (of 8 bf16) per plane
 
   f32x16 tot[2][KT];  // running totals; every block of 32 input channels is summed in fresh accumulators first
-#pragma unroll
-  for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) tot[pt][kt][i] = 0.f;
+  acc_zero(tot);
 
   // the lane's pixel in each of the wave's two pixel tiles: halo-tile byte offset of tap (0, 0), plus its k half
   int pbase[2], prow[2], pcol;
@@ -197,11 +178,7 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
 #pragma unroll
       for (int u = 0; u < GRP; ++u) {
         bf16x8 o[3];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const Split s(cfirst[u] + e < C ? v[u][e] : 0.f);
-          o[0][e] = s.p[0], o[1][e] = s.p[1], o[2][e] = s.p[2];
-        }
+        split8([&](int e) { return cfirst[u] + e < C ? v[u][e] : 0.f; }, o);
         if (at[u] >= 0) {
 #pragma unroll
           for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(lds + at[u] + p * PLANE_BYTES) = o[p];
@@ -211,12 +188,7 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
     __syncthreads();
     // ---- multiply: two passes of 9 taps x 2 k-steps; weight fragments from L2, pixel fragments from LDS, 12 KT MFMAs per step
     f32x16 acc[2][KT];
-#pragma unroll
-    for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[pt][kt][i] = 0.f;
+    acc_zero(acc);
     // The block after this one, whose first unit the last trip requests.  After the last block there is none: the pointer is
     // CLAMPED to this block, whose first unit is loaded once more and dropped -- no address outside `packed` is formed.
     const bf16x8* const wnext = cb + CB < C ? wblk + 2 * 64 : wblk;
@@ -308,7 +280,7 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) tot[pt][kt] = tot[pt][kt] + acc[pt][kt];
   }
-  // ---- store: accumulator register i of lane (r, hh) is output channel (i & 3) + 8 (i >> 2) + 4 hh of its tile, pixel r
+  // ---- store: accumulator register i of lane (r, hh) is output channel acc_channel(i, hh) of its tile, pixel r
   // act: the dense estimator's epilogue, bias_act_fwd_kernel's arithmetic (v += b; v > 0 ? v : v * slope), applied to the
   // totals in registers under ONE uniform branch, the bias index clamped so that the lane's 16 KT loads need no guard and go
   // out together.  (One branch and one guarded load per store cost every call 1.7 %, with or without the epilogue.)
@@ -317,7 +289,7 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
     for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int k = 32 * (kt0 + kt) + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        const int k = 32 * (kt0 + kt) + acc_channel(i, hh);
         const float b = bias ? bias[k < K ? k : K - 1] : 0.f;
 #pragma unroll
         for (int pt = 0; pt < 2; ++pt) {
@@ -337,13 +309,12 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
     for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int k = 32 * (kt0 + kt) + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        const int k = 32 * (kt0 + kt) + acc_channel(i, hh);
         if (k < K) yn[(long)k * HWl + gh * W + gw] = tot[pt][kt][i];
       }
   }
 }
 
-inline int tiles32(int n) { return (n + 31) / 32; }
 inline bool pack_shape_ok(int K, int C) {
   return K > 0 && C > 0 && (long)K * C * 9 <= INT_MAX && (long)9 * tiles32(K) * 2 * tiles32(C) * 64 <= INT_MAX / 8;
 }
@@ -361,13 +332,7 @@ struct Ends {  // where the input and the output live, and what the store does
 template <int KT, int PW>
 int launch(const Ends& ends, const bf16x8* packed, int N, int C, int K, int H, int W, int kt_first, int chunks, hipStream_t st) {
   using G = Geo<PW>;
-  static bool attr_set = false;  // more than 64 KB of dynamic LDS has to be asked for once per kernel
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&splitconv_kernel<KT, PW>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-    if (e != hipSuccess) return af_hip_status(e);
-    attr_set = true;
-  }
+  if (const int rc = allow_dynamic_lds<&splitconv_kernel<KT, PW>>(G::LDS_BYTES)) return rc;
   const int tx = (W + PW - 1) / PW, ty = (H + G::TH - 1) / G::TH;
   const dim3 grid((unsigned)((long)N * tx * ty), (unsigned)chunks);
   hipLaunchKernelGGL((splitconv_kernel<KT, PW>), grid, dim3(NT), G::LDS_BYTES, st, ends.x, ends.x_bs, packed, ends.y, ends.y_bs, ends.bias,
@@ -426,17 +391,14 @@ extern "C" int arflow_splitconv_fwd_ex(const float* x, long x_bstride, const voi
   int PW = 32;
   if (waste(16) < waste(PW)) PW = 16;
   if (waste(8) < waste(PW)) PW = 8;
-  // output-channel tiles in chunks of at most MAX_KT: `extra` chunks of base + 1 tiles, then the rest of base tiles
-  const int nkt = tiles32(K), chunks = (nkt + MAX_KT - 1) / MAX_KT, base = nkt / chunks, extra = nkt % chunks;
   const bf16x8* pk = (const bf16x8*)packed;
   hipStream_t st = (hipStream_t)stream;
-  for (int part = 0; part < 2; ++part) {
-    const int kt = part == 0 ? base + 1 : base, cnt = part == 0 ? extra : chunks - extra, first = part == 0 ? 0 : extra * (base + 1);
-    if (cnt == 0) continue;
+  for (const TilePart& p : split_tiles(tiles32(K), MAX_KT)) {  // one launch per part: chunks over gridDim.y
+    if (p.count == 0) continue;
     int rc;
-    if (PW == 32) rc = launch_kt<32>(kt, ends, pk, N, C, K, H, W, first, cnt, st);
-    else if (PW == 16) rc = launch_kt<16>(kt, ends, pk, N, C, K, H, W, first, cnt, st);
-    else rc = launch_kt<8>(kt, ends, pk, N, C, K, H, W, first, cnt, st);
+    if (PW == 32) rc = launch_kt<32>(p.kt, ends, pk, N, C, K, H, W, p.first, p.count, st);
+    else if (PW == 16) rc = launch_kt<16>(p.kt, ends, pk, N, C, K, H, W, p.first, p.count, st);
+    else rc = launch_kt<8>(p.kt, ends, pk, N, C, K, H, W, p.first, p.count, st);
     if (rc != ARFLOW_OK) return rc;
   }
   return ARFLOW_OK;

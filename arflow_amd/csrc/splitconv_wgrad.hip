@@ -5,7 +5,7 @@
 //
 // GEMM view, per tap: D[k][c] = sum over pixels of A[k][pixel] * B[pixel][c], A = dy, B = x shifted by the tap, the reduction
 // over PIXELS -- which are contiguous per channel in NCHW, so nothing is transposed.  Both operands are split into their three
-// bf16 planes in registers on the way to LDS (splitconv.hip's header: b0 + b1 + b2 == x bit for bit) and the same six plane
+// bf16 planes in registers on the way to LDS (splitbf16.hpp, Split: b0 + b1 + b2 == x bit for bit) and the same six plane
 // products are accumulated by v_mfma_f32_32x32x16_bf16, the three smallest dropped.
 //
 // Work split.  The map is cut into strips of at most 8 groups of 8 pixels (64 columns) and into blocks of rows; a CHUNK is
@@ -36,11 +36,10 @@
 #include <climits>
 #include <cstdint>
 
-#include "common.hpp"
+#include "splitbf16.hpp"
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace splitbf16;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int G = 8;               // groups of 8 pixels per staged row: 4 MFMA steps
@@ -50,7 +49,6 @@ constexpr int XH_CS = 9 * G + 1;   // dwords per x channel of the neighbour pair
 constexpr int MAX_ROWS = 128;      // rows per chunk: the length of the running total's chain
 constexpr int MIN_ROWS = 4;        // below that the two extra x rows a chunk stages dominate
 constexpr int WANT_WG = 1024;      // 256 CUs x 2 workgroups, twice over
-constexpr int MAX_KT = 2;
 
 template <int KT>
 struct Lds {
@@ -60,15 +58,6 @@ struct Lds {
   static constexpr int BYTES = XH + 32 * XH_CS * 4;  // 59 520 / 72 320 for KT = 1 / 2
 };
 
-struct Split {
-  __bf16 p[3];
-  __device__ __forceinline__ explicit Split(float v) {
-    p[0] = (__bf16)v;
-    const float r1 = v - (float)p[0];
-    p[1] = (__bf16)r1;
-    p[2] = (__bf16)(r1 - (float)p[1]);
-  }
-};
 __device__ __forceinline__ unsigned bf16_bits(__bf16 b) { return (unsigned)__builtin_bit_cast(unsigned short, b); }
 
 // Eight consecutive floats of a row from column col0 (a multiple of 8): zero where !valid or beyond W.  Every load is
@@ -103,7 +92,6 @@ struct Plan {
   int GW, SG, nstrips, RPC, nrb, nct, nkt, kchunks;
   long chunks;
 };
-inline int tiles32(int n) { return (n + 31) / 32; }
 inline bool shape_ok(int N, int C, int K, int H, int W) {
   return N > 0 && C > 0 && K > 0 && H > 0 && W > 0 && (long)N * C * H * W <= INT_MAX && (long)N * K * H * W <= INT_MAX &&
          (long)9 * K * C <= INT_MAX;
@@ -191,7 +179,7 @@ __global__ __launch_bounds__(192 * KT, VEC && KT == 2 ? 3 : 2) void splitconv_wg
         const float v[8] = {pf[j].a.x, pf[j].a.y, pf[j].a.z, pf[j].a.w, pf[j].b.x, pf[j].b.y, pf[j].b.z, pf[j].b.w};
         bf16x8 o[3];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
+        for (int e = 0; e < 8; ++e) {  // split8's loop in its own text, here and below: through split8 this kernel measured 2 % slower
           const Split s(v[e]);
           o[0][e] = s.p[0], o[1][e] = s.p[1], o[2][e] = s.p[2];
         }
@@ -218,10 +206,7 @@ __global__ __launch_bounds__(192 * KT, VEC && KT == 2 ? 3 : 2) void splitconv_wg
   };
 
   f32x16 tot[3];
-#pragma unroll
-  for (int s = 0; s < 3; ++s)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) tot[s][i] = 0.f;
+  acc_zero(tot);
 
   const unsigned char* const a_base = lds + L::DY + ((ktl * 32 + r32) * DY_CS + hh) * 16;
   fetch(h0 - 1, -1);
@@ -238,10 +223,7 @@ __global__ __launch_bounds__(192 * KT, VEC && KT == 2 ? 3 : 2) void splitconv_wg
     const unsigned char* const b_base = lds + L::X + (r32 * X_CS + slot * 3 * G + hh) * 16;
     const unsigned* const bh_base = xh + r32 * XH_CS + slot * 3 * G + hh;
     f32x16 acc[3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[s][i] = 0.f;
+    acc_zero(acc);
     // the x fragments of plane p for the three tap columns: the aligned run and the two runs shifted by one pixel
     const auto x_frags = [&](int p, int t, bf16x8 (&bs)[3]) __attribute__((always_inline)) {
       const u32x4 d = *reinterpret_cast<const u32x4*>(b_base + (p * G + 2 * t) * 16);
@@ -282,7 +264,7 @@ __global__ __launch_bounds__(192 * KT, VEC && KT == 2 ? 3 : 2) void splitconv_wg
 #pragma unroll
     for (int s = 0; s < 3; ++s) tot[s] = tot[s] + acc[s];
   }
-  // accumulator register i of lane (r32, hh) is output channel (i & 3) + 8 (i >> 2) + 4 hh of the tile, input channel r32
+  // accumulator register i of lane (r32, hh) is output channel acc_channel(i, hh) of the tile, input channel r32
   const int c = ct * 32 + r32;
   if (c < C) {
 #pragma unroll
@@ -290,7 +272,7 @@ __global__ __launch_bounds__(192 * KT, VEC && KT == 2 ? 3 : 2) void splitconv_wg
       float* const wt = ws + ((long)chunk * 9 + (tr * 3 + s)) * K * C;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int k = 32 * (kt0 + ktl) + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        const int k = 32 * (kt0 + ktl) + acc_channel(i, hh);
         if (k < K) wt[(long)k * C + c] = tot[s][i];
       }
     }
@@ -312,13 +294,7 @@ template <int KT, bool VEC>
 int launch(const float* x, long x_bs, const float* dy, long dy_bs, float* ws, int C, int K, int H, int W, int kt_first, int kcnt,
            const Plan& p, hipStream_t st) {
   using L = Lds<KT>;
-  static bool attr_set = false;  // more than 64 KB of dynamic LDS has to be asked for once per kernel
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&splitconv_wgrad_kernel<KT, VEC>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES);
-    if (e != hipSuccess) return af_hip_status(e);
-    attr_set = true;
-  }
+  if (const int rc = allow_dynamic_lds<&splitconv_wgrad_kernel<KT, VEC>>(L::BYTES)) return rc;
   const long grid = p.chunks * kcnt * p.nct;
   if (grid > INT_MAX) return ARFLOW_ESHAPE;
   hipLaunchKernelGGL((splitconv_wgrad_kernel<KT, VEC>), dim3((unsigned)grid), dim3(192 * KT), L::BYTES, st, x, x_bs, dy, dy_bs, ws, C, K,
@@ -350,16 +326,13 @@ extern "C" int arflow_splitconv_wgrad(const float* x, long x_bstride, const floa
   hipStream_t st = (hipStream_t)stream;
   // float4 loads where every row starts on a 16-byte boundary
   const bool vec = W % 4 == 0 && af_vec4_ok(x, x_bstride, N) && af_vec4_ok(dy, dy_bstride, N);
-  // output-channel tiles in chunks of at most MAX_KT: `extra` chunks of base + 1 tiles, then the rest of base tiles
-  const int base = p.nkt / p.kchunks, extra = p.nkt % p.kchunks;
-  for (int part = 0; part < 2; ++part) {
-    const int kt = part == 0 ? base + 1 : base, cnt = part == 0 ? extra : p.kchunks - extra, first = part == 0 ? 0 : extra * (base + 1);
-    if (cnt == 0) continue;
+  for (const TilePart& t : split_tiles(p.nkt, MAX_KT)) {  // one launch per part
+    if (t.count == 0) continue;
     const auto go = [&](auto kt_c, auto vec_c) {
-      return launch<decltype(kt_c)::value, decltype(vec_c)::value>(x, x_bstride, dy, dy_bstride, (float*)ws, C, K, H, W, first, cnt, p, st);
+      return launch<decltype(kt_c)::value, decltype(vec_c)::value>(x, x_bstride, dy, dy_bstride, (float*)ws, C, K, H, W, t.first, t.count, p, st);
     };
     using std::integral_constant;
-    const int rc = kt == 1 ? (vec ? go(integral_constant<int, 1>{}, std::true_type{}) : go(integral_constant<int, 1>{}, std::false_type{}))
+    const int rc = t.kt == 1 ? (vec ? go(integral_constant<int, 1>{}, std::true_type{}) : go(integral_constant<int, 1>{}, std::false_type{}))
                            : (vec ? go(integral_constant<int, 2>{}, std::true_type{}) : go(integral_constant<int, 2>{}, std::false_type{}));
     if (rc != ARFLOW_OK) return rc;
   }

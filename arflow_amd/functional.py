@@ -107,6 +107,14 @@ def _call(name, *args, key=None):
     _lib.poll_stale_error(lib, name)
 
 
+def _workspace(name, *args, device):
+    """A uint8 tensor of the size the query `name`(*args) answers; a negative answer (an error) raises BEFORE any allocation."""
+    nbytes = getattr(_lib.load(), name)(*args)
+    if nbytes < 0:
+        _lib.check(int(nbytes), name)
+    return torch.empty(nbytes, device=device, dtype=torch.uint8)
+
+
 # ---- deterministic mode (DESIGN.md section 14) ------------------------------------------------------
 def set_deterministic(on):
     """Switch the library's process-wide deterministic mode (initial value: ARFLOW_DETERMINISTIC=1); returns the previous
@@ -647,10 +655,7 @@ class HeadConvFunction(torch.autograd.Function):
         x, weight = x.contiguous(), weight.contiguous()
         if bias is not None:
             bias = bias.contiguous()
-        B, C, H, W = x.shape
-        y = torch.empty(B, 2, H, W, device=x.device, dtype=torch.float32)
-        with torch.cuda.device_of(x):
-            _call('arflow_headconv_fwd', _p(x), _p(weight), _p(bias), _p(y), B, C, H, W, _stream())
+        y = _headconv_fwd(x, weight, bias)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         return y
@@ -658,25 +663,42 @@ class HeadConvFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        B, C, H, W = x.shape
         dy = dy.contiguous()
-        dx = dw = db = None
-        with torch.cuda.device_of(x):
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _call('arflow_headconv_bwd_data', _p(dy), _p(weight), _p(dx), B, C, H, W, _stream())
-            want_b = ctx.has_bias and ctx.needs_input_grad[2]
-            if ctx.needs_input_grad[1] or want_b:
-                nbytes = _lib.load().arflow_headconv_bwd_weight_ws_bytes(B, C, H, W)
-                if nbytes < 0:
-                    _lib.check(int(nbytes), 'arflow_headconv_bwd_weight_ws_bytes')
-                ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-                dw = torch.empty_like(weight)
-                db = torch.empty(2, device=x.device, dtype=torch.float32) if want_b else None
-                _call('arflow_headconv_bwd_weight', _p(x), _p(dy), _p(dw), _p(db), _p(ws), B, C, H, W, _stream())
-                if not ctx.needs_input_grad[1]:
-                    dw = None
+        dx = _headconv_dgrad(dy, weight, x) if ctx.needs_input_grad[0] else None
+        dw, db = _headconv_wgrad(x, dy, weight, ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
         return dx, dw, db
+
+
+# The three launches of csrc/headconv.hip without autograd, for HeadConvFunction and the head of DenseEstimatorFunction
+def _headconv_fwd(x, w, b):
+    """y [B,2,H,W] = conv2d(x, w, b, padding=1); every tensor contiguous (here and below), b may be None."""
+    B, C, H, W = x.shape
+    y = torch.empty(B, 2, H, W, device=x.device, dtype=torch.float32)
+    with torch.cuda.device_of(x):
+        _call('arflow_headconv_fwd', _p(x), _p(w), _p(b), _p(y), B, C, H, W, _stream())
+    return y
+
+
+def _headconv_dgrad(gy, w, like):
+    """dx of that convolution, shaped like its input `like`."""
+    B, C, H, W = like.shape
+    dx = torch.empty_like(like)
+    with torch.cuda.device_of(like):
+        _call('arflow_headconv_bwd_data', _p(gy), _p(w), _p(dx), B, C, H, W, _stream())
+    return dx
+
+
+def _headconv_wgrad(x, gy, w, want_w, want_b):
+    """(dw, db) in one pass over x, or (None, None); the kernel always forms dw, so where only the bias is wanted it is dropped."""
+    if not (want_w or want_b):
+        return None, None
+    B, C, H, W = x.shape
+    ws = _workspace('arflow_headconv_bwd_weight_ws_bytes', B, C, H, W, device=x.device)
+    dw = torch.empty_like(w)
+    db = torch.empty(2, device=x.device, dtype=torch.float32) if want_b else None
+    with torch.cuda.device_of(x):
+        _call('arflow_headconv_bwd_weight', _p(x), _p(gy), _p(dw), _p(db), _p(ws), B, C, H, W, _stream())
+    return (dw if want_w else None), db
 
 
 def head_conv(x, weight, bias):
@@ -706,15 +728,20 @@ def splitconv_takes(N, C, K, H, W):
     return _splitconv_rule(int(N), int(C), int(K), int(H), int(W))
 
 
+def _size_floor(N, H, W, h, w):
+    """The routing rules' floor: maps of at least h x w and 16 of them in the batch (they were measured at N = 16)."""
+    return H * W >= h * w and N * H * W >= 16 * h * w
+
+
 def _splitconv_rule(N, C, K, H, W):
     # measured at N = 16, channels 32 .. 597: faster on every call at 96x160 (1.13x .. 1.45x); at 48x80 on the calls with 128
     # output channels or at most 128 input channels (1.16x .. 1.50x; 403->96, 499->64, 563->32 forward and 64<->32 are not);
     # at 24x40 and 12x20 on none (the tiles do not fill the chip)
     if min(C, K) < 32 or not 64 <= max(C, K) <= 640:
         return False
-    if H * W >= 96 * 160 and N * H * W >= 16 * 96 * 160:
+    if _size_floor(N, H, W, 96, 160):
         return True
-    if H * W >= 48 * 80 and N * H * W >= 16 * 48 * 80:
+    if _size_floor(N, H, W, 48, 80):
         return max(C, K) >= 128 and (K >= 128 or C <= 128)
     return False
 
@@ -734,10 +761,7 @@ def splitconv(x, w, transpose_flip=False, out=None, bias=None, slope=None):
     K = int(w.shape[1 if transpose_flip else 0])
     if bias is not None and (slope is None or bias.numel() != K):
         raise ValueError('splitconv: bias holds one value per output channel and needs slope (the epilogue is bias + LeakyReLU)')
-    nbytes = _lib.load().arflow_splitconv_pack_bytes(K, C)
-    if nbytes < 0:
-        _lib.check(int(nbytes), 'arflow_splitconv_pack_bytes')
-    packed = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    packed = _workspace('arflow_splitconv_pack_bytes', K, C, device=x.device)
     if out is None:
         y, y_bs = torch.empty(N, K, H, W, device=x.device, dtype=torch.float32), K * H * W
     else:
@@ -787,7 +811,7 @@ def _splitconv_wgrad_rule(N, C, K, H, W):
     # 0.93x / 0.97x are not) -- and on no call at 48x80 (0.75x .. 1.04x), 24x40 or 12x20
     if N * H * W < 16 * 48 * 80:
         return False
-    return H * W >= 96 * 160 and N * H * W >= 16 * 96 * 160 and 448 <= C <= 640 and 32 <= K <= 128
+    return _size_floor(N, H, W, 96, 160) and 448 <= C <= 640 and 32 <= K <= 128
 
 
 def _batch_strided(t):
@@ -809,10 +833,7 @@ def splitconv_wgrad(x, gy):
     gy, gy_bs = _batch_strided(gy)
     N, C, H, W = x.shape
     K = int(gy.shape[1])
-    nbytes = _lib.load().arflow_splitconv_wgrad_ws_bytes(N, C, K, H, W)
-    if nbytes < 0:
-        _lib.check(int(nbytes), 'arflow_splitconv_wgrad_ws_bytes')
-    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    ws = _workspace('arflow_splitconv_wgrad_ws_bytes', N, C, K, H, W, device=x.device)
     dw = torch.empty(K, C, 3, 3, device=x.device, dtype=torch.float32)
     with torch.cuda.device_of(x):
         _call('arflow_splitconv_wgrad', _p(x), x_bs, _p(gy), gy_bs, _p(dw), _p(ws), N, C, K, H, W, _stream())
@@ -842,22 +863,20 @@ class Conv3x3Function(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gy = gy.contiguous()
-        want_dx, want_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        dx = dw = None
-        if ctx.dgrad and want_dx:
-            dx = splitconv(gy, w, transpose_flip=True)
-            want_dx = False
-        if ctx.wgrad and want_dw:
-            dw = splitconv_wgrad(x, gy)
-            want_dw = False
-        if want_dx or want_dw:
-            dx_m, dw_m, _ = torch.ops.aten.convolution_backward(gy, x, w, None, *_conv_args(), [want_dx, want_dw, False])
-            if want_dx:
-                dx = dx_m
-            if want_dw:
-                dw = dw_m
+        dx, dw = _conv3x3_grads(x, w, gy.contiguous(), ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.dgrad, ctx.wgrad)
         return dx, dw, None, None, None
+
+
+def _conv3x3_grads(x, w, gy, want_dx, want_dw, dx_native, dw_native):
+    """(dx, dw) of conv2d(x, w, padding=1) for Conv3x3Function and the layers of DenseEstimatorFunction (no autograd): each on
+    the split-bf16 kernel where dx_native / dw_native say so, what is left in ONE MIOpen call; an unwanted one is None."""
+    dx = splitconv(gy, w, transpose_flip=True) if want_dx and dx_native else None
+    dw = splitconv_wgrad(x, gy) if want_dw and dw_native else None
+    left = [bool(want_dx and dx is None), bool(want_dw and dw is None), False]
+    if any(left):
+        dx_m, dw_m, _ = torch.ops.aten.convolution_backward(gy, x, w, None, *_conv_args(), left)
+        dx, dw = (dx_m if left[0] else dx), (dw_m if left[1] else dw)
+    return dx, dw
 
 
 def conv3x3(x, w, fwd=True, dgrad=True, wgrad=False):
@@ -977,7 +996,7 @@ def _inplace_wgrad_rule(N, C, K, H, W):
     # (solver + layout copies + ATen's contiguous copy of x_k): 275->128 -103 us and 403->96 -230 us, ranges apart; 147->128 -24 us,
     # ranges apart in one job and touching in three others -- a tie in time, taken for the 144 MB copy it does not allocate.
     # Never below that size.
-    return H * W >= 96 * 160 and N * H * W >= 16 * 96 * 160 and 128 <= C < 448 and 96 <= K <= 128
+    return _size_floor(N, H, W, 96, 160) and 128 <= C < 448 and 96 <= K <= 128
 
 
 class DenseEstimatorFunction(torch.autograd.Function):
@@ -1028,11 +1047,8 @@ class DenseEstimatorFunction(torch.autograd.Function):
                     y = torch.nn.functional.conv2d(xk, w, None, 1, 1)
                 xs.append(dense_cat(y, b, xk, slope))
             x6 = xs[-1]
-        B, C6, H, W = x6.shape
         w_head = w_head.contiguous()
-        flow = torch.empty(B, 2, H, W, device=x.device, dtype=torch.float32)
-        with torch.cuda.device_of(x6):
-            _call('arflow_headconv_fwd', _p(x6), _p(w_head), _p(b_head.contiguous()), _p(flow), B, C6, H, W, _stream())
+        flow = _headconv_fwd(x6, w_head, b_head.contiguous())
         if inplace:
             ctx.save_for_backward(x6, *ws, w_head)
         else:
@@ -1060,21 +1076,11 @@ class DenseEstimatorFunction(torch.autograd.Function):
         # the lowest layer whose gradient chain has to be followed: 0 = down to the estimator's input
         lowest = 0 if need[0] else next((m for m in range(1, 6) if need[2 * m] or need[2 * m + 1]), 6)
         dx_head = None
-        with torch.cuda.device_of(x6):
-            if gflow is not None:
-                gflow = gflow.contiguous()
-                if lowest < 6:
-                    dx_head = torch.empty_like(x6)
-                    _call('arflow_headconv_bwd_data', _p(gflow), _p(w_head), _p(dx_head), B, C6, H, W, _stream())
-                if need[12] or need[13]:
-                    nbytes = _lib.load().arflow_headconv_bwd_weight_ws_bytes(B, C6, H, W)
-                    if nbytes < 0:
-                        _lib.check(int(nbytes), 'arflow_headconv_bwd_weight_ws_bytes')
-                    wsb = torch.empty(nbytes, device=x6.device, dtype=torch.uint8)
-                    dw = torch.empty_like(w_head)
-                    db = torch.empty(2, device=x6.device, dtype=torch.float32) if need[13] else None
-                    _call('arflow_headconv_bwd_weight', _p(x6), _p(gflow), _p(dw), _p(db), _p(wsb), B, C6, H, W, _stream())
-                    grads[12], grads[13] = (dw if need[12] else None), db
+        if gflow is not None:
+            gflow = gflow.contiguous()
+            if lowest < 6:
+                dx_head = _headconv_dgrad(gflow, w_head, x6)
+            grads[12], grads[13] = _headconv_wgrad(x6, gflow, w_head, need[12], need[13])
         if lowest == 6:
             return tuple(grads)
         # sources in the order autograd adds them: x_6's own gradient, the head's, then the layers' from the top down
@@ -1084,25 +1090,13 @@ class DenseEstimatorFunction(torch.autograd.Function):
             # x_k = [a_{k-1}, ..., a_1, x_1]: a_m starts at sum(oc_j, m < j < k)
             srcs = [(t, sum(ocs[m:5]), None) for t in top] + [(dx, sum(ocs[m:k - 1]), None) for dx, k in dxs]
             gy, gb = dense_grad_gather(srcs, ocs[m - 1], act=xs[m], slope=ctx.slope, want_bias=need[2 * m + 1])
-            want_dx = m > lowest
-            dx = dw = None
+            want_dx, want_dw = m > lowest, bool(need[2 * m])
             xm = xs[m - 1]
-            # as Conv3x3Function.backward: dx and dw each on the split-bf16 kernel where ConvAct's predicates route them,
-            # what is left in ONE MIOpen call (a layer of which only the bias is trained needs neither)
-            ask_dx, ask_dw = want_dx, bool(need[2 * m])
-            if ask_dx and splitconv_takes(B, ocs[m - 1], xm.shape[1], H, W):
-                dx = splitconv(gy, ws[m - 1], transpose_flip=True)
-                ask_dx = False
-            if ask_dw and (_inplace_wgrad_takes if ctx.inplace else splitconv_wgrad_takes)(B, xm.shape[1], ocs[m - 1], H, W):
-                dw = splitconv_wgrad(xm, gy)
-                ask_dw = False
-            if ask_dx or ask_dw:
-                dx_m, dw_m, _ = torch.ops.aten.convolution_backward(gy, xm, ws[m - 1], None, *_conv_args(), [ask_dx, ask_dw, False])
-                if ask_dx:
-                    dx = dx_m
-                if ask_dw:
-                    dw = dw_m
-            grads[2 * m], grads[2 * m + 1] = (dw if need[2 * m] else None), gb
+            # ConvAct's predicates, asked only for what is wanted (a layer of which only the bias is trained needs neither)
+            dx_native = want_dx and splitconv_takes(B, ocs[m - 1], xm.shape[1], H, W)
+            dw_native = want_dw and (_inplace_wgrad_takes if ctx.inplace else splitconv_wgrad_takes)(B, xm.shape[1], ocs[m - 1], H, W)
+            dx, dw = _conv3x3_grads(xm, ws[m - 1], gy, want_dx, want_dw, dx_native, dw_native)
+            grads[2 * m], grads[2 * m + 1] = dw, gb
             if want_dx:
                 dxs.append((dx, m))
         if need[0]:
@@ -2217,12 +2211,8 @@ def area_pyramid(frames, sizes):
     n = len(sizes)
     arr = (ctypes.c_int * (2 * n))(*[v for s in sizes for v in s])
     host = ctypes.cast(arr, ctypes.c_void_p)
-    lib = _lib.load()
-    nbytes = lib.arflow_area_pyramid_ws_bytes(B * C, H, W, host, n)
-    if nbytes < 0:
-        _lib.check(nbytes, 'arflow_area_pyramid_ws_bytes')
-    buf = torch.empty(nbytes // 4, device=frames.device, dtype=torch.float32)
-    if nbytes:
+    buf = _workspace('arflow_area_pyramid_ws_bytes', B * C, H, W, host, n, device=frames.device).view(torch.float32)
+    if buf.numel():
         with torch.cuda.device_of(frames):
             _call('arflow_area_pyramid', _p(frames), _p(buf), B * C, H, W, host, n, _stream(), key=(B * C, H, W, n))
     out, off = [], 0
