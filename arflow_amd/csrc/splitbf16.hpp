@@ -5,6 +5,7 @@
 #include <array>
 
 #include "common.hpp"
+#include "split_tiles.hpp"
 
 namespace splitbf16 {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -48,16 +49,7 @@ __device__ __forceinline__ void acc_zero(T (&a)[N]) {  // an array of accumulato
   for (int s = 0; s < N; ++s) acc_zero(a[s]);
 }
 
-inline int tiles32(int n) { return (n + 31) / 32; }
-constexpr int MAX_KT = 2;  // tiles of 32 output channels per workgroup, in both kernels (their template KT: 1 or 2)
-
-// nkt tiles of 32 output channels go to the kernels in chunks of at most max_kt tiles, of equal size +-1 (no tile of zeros
-// is multiplied): `extra` chunks of base + 1 tiles, then the rest of base tiles.  A part is one launch; count 0: none.
-struct TilePart { int kt, count, first; };  // tiles per chunk, chunks, the first chunk's first tile
-inline std::array<TilePart, 2> split_tiles(int nkt, int max_kt) {
-  const int chunks = (nkt + max_kt - 1) / max_kt, base = nkt / chunks, extra = nkt % chunks;
-  return {{{base + 1, extra, 0}, {base, chunks - extra, extra * (base + 1)}}};
-}
+// tiles32, MAX_KT, TilePart, split_tiles -- the cut of the output channels into launches -- are in split_tiles.hpp (host C++)
 
 // more than 64 KB of dynamic LDS has to be asked for once per kernel: one flag per instantiation, i.e. per KERNEL
 template <auto KERNEL>

@@ -9,18 +9,21 @@
 // products are accumulated by v_mfma_f32_32x32x16_bf16, the three smallest dropped.
 //
 // Work split.  The map is cut into strips of at most 8 groups of 8 pixels (64 columns) and into blocks of rows; a CHUNK is
-// (sample, strip, row block).  A workgroup owns one chunk, one tile of 32 input channels and KT <= 2 tiles of 32 output
-// channels, and walks down the chunk's rows.  Per row it stages the dy row (KT * 32 channels) and the NEXT x row (32 channels)
-// as bf16 planes -- the x rows h - 1, h, h + 1 live in a ring of three -- with zero fill for rows outside the image, columns
-// outside it, the groups past the strip and the channel tails; no global address is formed for any of them.  A lane's MFMA
+// (sample, strip, row block).  A workgroup owns one chunk, CT <= 2 tiles of 32 input channels and KT <= 2 tiles of 32 output
+// channels, and walks down the chunk's rows.  Per row it stages the dy row (KT * 32 channels) and the
+// NEXT x row (CT * 32 channels) as bf16 planes -- the x rows h - 1, h, h + 1 live in a ring of three -- with zero fill for
+// rows outside the image, columns outside it, the groups past the strip, the channel tails and the tiles a part does not
+// have; no global address is formed for any of them.  A lane's MFMA
 // fragment is 8 consecutive pixels of one channel: one ds_read_b128.  The +-1 column taps are the same run shifted by ONE
 // element, i.e. off the 16-byte boundary: instead of three copies in LDS, the two neighbours of every group (pixel 8g - 1 and
 // 8g + 8, zero at the image's edge) are stored as one dword next to it and the shifted fragments are made in registers with
 // five v_alignbit_b32 per plane.  Channel strides are an odd number of 16-byte slots (25 for dy, 73 for x), so the 16 lanes a
 // ds_read_b128 phase serves fall on 16 different slots of the bank row.
-// A wave is (output-channel tile, tap row r): it reads dy row h and x row h + r - 1 and holds the three taps (r, 0..2) of
-// its 32 x 32 tile: 48 accumulator registers for the current row plus 48 running totals.  3 KT waves per workgroup, two
-// workgroups per CU at KT = 2 (2 x 70.5 KB of LDS, <= 168 registers): one stages while the other multiplies.
+// A wave is (output-channel tile, input-channel tile, tap row r): it reads dy row h and x row h + r - 1 and holds the three
+// taps (r, 0..2) of its 32 x 32 tile: 48 accumulator registers for the current row plus 48 running totals.  3 KT CT waves per
+// workgroup: at KT = CT = 2 twelve waves, three per SIMD (<= 168 registers), 116 KB of LDS, one workgroup per CU; a staged
+// dy row then serves two x tiles and a staged x row two dy tiles.  The plan -- strips, row blocks, the parts of both channel
+// axes, the block-id decode with its XCD remap -- is splitconv_wgrad_plan.hpp, which tests/wgrad_plan_check.cpp walks on the CPU.
 //
 // The global loads of a staged row are unconditional (addresses clamped into the row, zeros selected afterwards; float4 where
 // every row starts on a 16-byte boundary), held in registers, and issued one row ahead: they are in flight while the current
@@ -37,25 +40,23 @@
 #include <cstdint>
 
 #include "splitbf16.hpp"
+#include "splitconv_wgrad_plan.hpp"
 
 namespace {
 using namespace splitbf16;
+using namespace wgrad_plan;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int G = 8;               // groups of 8 pixels per staged row: 4 MFMA steps
 constexpr int DY_CS = 3 * G + 1;   // 16-byte slots per dy channel, [plane][group]; odd
 constexpr int X_CS = 9 * G + 1;    // 16-byte slots per x channel, [ring row][plane][group]; odd
 constexpr int XH_CS = 9 * G + 1;   // dwords per x channel of the neighbour pairs, same order; odd
-constexpr int MAX_ROWS = 128;      // rows per chunk: the length of the running total's chain
-constexpr int MIN_ROWS = 4;        // below that the two extra x rows a chunk stages dominate
-constexpr int WANT_WG = 1024;      // 256 CUs x 2 workgroups, twice over
 
-template <int KT>
+template <int KT, int CT>
 struct Lds {
   static constexpr int DY = 0;
   static constexpr int X = KT * 32 * DY_CS * 16;
-  static constexpr int XH = X + 32 * X_CS * 16;
-  static constexpr int BYTES = XH + 32 * XH_CS * 4;  // 59 520 / 72 320 for KT = 1 / 2
+  static constexpr int XH = X + CT * 32 * X_CS * 16;
+  static constexpr int BYTES = XH + CT * 32 * XH_CS * 4;  // CT = 1: 59 520 / 72 320 for KT = 1 / 2; CT = 2: 106 240 / 119 040
 };
 
 __device__ __forceinline__ unsigned bf16_bits(__bf16 b) { return (unsigned)__builtin_bit_cast(unsigned short, b); }
@@ -88,62 +89,34 @@ __device__ __forceinline__ void load_run(const float* __restrict__ row, int col0
   }
 }
 
-struct Plan {
-  int GW, SG, nstrips, RPC, nrb, nct, nkt, kchunks;
-  long chunks;
-};
-inline bool shape_ok(int N, int C, int K, int H, int W) {
-  return N > 0 && C > 0 && K > 0 && H > 0 && W > 0 && (long)N * C * H * W <= INT_MAX && (long)N * K * H * W <= INT_MAX &&
-         (long)9 * K * C <= INT_MAX;
-}
-inline Plan make_plan(int N, int C, int K, int H, int W) {
-  Plan p;
-  p.GW = (W + 7) / 8;
-  const int ns = (p.GW + G - 1) / G;
-  p.SG = 2 * ((p.GW + 2 * ns - 1) / (2 * ns));  // strips of equal, even width (a step is two groups), at most G
-  p.nstrips = (p.GW + p.SG - 1) / p.SG;
-  p.nct = tiles32(C), p.nkt = tiles32(K), p.kchunks = (p.nkt + MAX_KT - 1) / MAX_KT;
-  const long units = (long)p.nct * p.kchunks * N * p.nstrips;
-  const long want = (WANT_WG + units - 1) / units;  // row blocks that fill the chip
-  int rpc = (int)((H + want - 1) / want);
-  if (rpc < MIN_ROWS) rpc = MIN_ROWS;
-  if (rpc > MAX_ROWS) rpc = MAX_ROWS;
-  if (rpc > H) rpc = H;
-  p.RPC = rpc;
-  p.nrb = (H + rpc - 1) / rpc;
-  p.chunks = (long)N * p.nstrips * p.nrb;
-  return p;
-}
-
-// grid: x = (chunk, output-channel chunk, input-channel tile), the tile fastest: the workgroups that share a chunk's dy rows
-// and an x tile run together.  ws: [chunk][tap][K][C] partial sums.
-template <int KT, bool VEC>
-__global__ __launch_bounds__(192 * KT, VEC && KT == 2 ? 3 : 2) void splitconv_wgrad_kernel(const float* __restrict__ x, long x_bs,
-                                                                             const float* __restrict__ dy, long dy_bs,
-                                                                             float* __restrict__ ws, int C, int K, int H, int W,
-                                                                             int kt_first, int kcnt, int nct, int nstrips, int SG,
-                                                                             int nrb, int RPC) {
-  constexpr int NT = 192 * KT;
-  using L = Lds<KT>;
+// grid: decode_block(blockIdx.x): (chunk, output-channel part, input-channel part), the latter fastest, behind the XCD remap:
+// the workgroups that share a chunk's dy rows and x tiles run together on one L2.  ws: [chunk][tap][K][C] partial sums.
+// Three waves per SIMD where two workgroups of <2, 1> or the twelve waves of one <2, 2> share a CU (float4 loads only).
+template <int KT, int CT, bool VEC>
+__global__ __launch_bounds__(192 * KT * CT, VEC && KT == 2 ? 3 : 2) void splitconv_wgrad_kernel(
+    const float* __restrict__ x, long x_bs, const float* __restrict__ dy, long dy_bs, float* __restrict__ ws, int C, int K, int H,
+    int W, const Launch l, int SG, int RPC) {
+  constexpr int NT = 192 * KT * CT;
+  using L = Lds<KT, CT>;
   extern __shared__ __align__(16) unsigned char lds[];
   unsigned* const xh = reinterpret_cast<unsigned*>(lds + L::XH);
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, hh = lane >> 5;
-  const int ktl = wv / 3, tr = wv - 3 * ktl;
-  const int b = blockIdx.x;
-  const int ct = b % nct, kc = (b / nct) % kcnt, chunk = b / (nct * kcnt);
-  const int rb = chunk % nrb, strip = (chunk / nrb) % nstrips, n = chunk / (nrb * nstrips);
-  const int kt0 = kt_first + kc * KT;
-  const int h0 = rb * RPC, h1 = min(H, h0 + RPC);
+  const int tile = wv / 3, tr = wv - 3 * tile, ctl = tile / KT, ktl = tile - KT * ctl;
+  const Block blk = decode_block(blockIdx.x, gridDim.x, l);
+  const int chunk = blk.chunk, strip = blk.strip, n = blk.n, kt0 = blk.kt0, ct0 = blk.ct0;
+  // one past the workgroup's last input / output channel: a part may be one tile short of CT / KT
+  const int cend = min(C, (ct0 + blk.ctn) * 32), kend = min(K, (kt0 + blk.ktn) * 32);
+  const int h0 = blk.rb * RPC, h1 = min(H, h0 + RPC);
   const int GW = (W + 7) >> 3, g0 = strip * SG, gcount = min(SG, GW - g0), nsteps = (gcount + 1) >> 1;
   const long HWl = (long)H * W;
   const float* const xn = x + (long)n * x_bs;
   const float* const dyn = dy + (long)n * dy_bs;
 
-  // Staging items: (x channel, group) for the tile's 32 channels, then (dy channel, group); item j of a thread is number
-  // tid + j NT (256 x items: whole waves take one kind).  fetch() issues an item's global loads into registers, commit() splits
+  // Staging items: (x channel, group) for the CT tiles' channels, then (dy channel, group); item j of a thread is number
+  // tid + j NT (256 CT x items: whole waves take one kind).  fetch() issues an item's global loads into registers, commit() splits
   // the values and stores the planes: the loads of row h + 1 are in flight while row h is multiplied.
-  constexpr int NX = 32 * G, NITEM = NX + KT * 32 * G, NSLOT = (NITEM + NT - 1) / NT;
+  constexpr int NX = CT * 32 * G, NITEM = NX + KT * 32 * G, NSLOT = (NITEM + NT - 1) / NT;
   Run pf[NSLOT];
   // yx: the x row (any row: outside the image it is zeros); ydy: the dy row, a row of the image, or -1 for none
   const auto fetch = [&](int yx, int ydy) __attribute__((always_inline)) {
@@ -152,8 +125,8 @@ __global__ __launch_bounds__(192 * KT, VEC && KT == 2 ? 3 : 2) void splitconv_wg
       const int i = tid + j * NT;
       if (i < NX) {
         const int cl = i / G, g = i - cl * G;
-        const int c = ct * 32 + cl, col0 = (g0 + g) * 8;
-        const bool valid = yx >= 0 && yx < H && c < C && g < gcount;
+        const int c = ct0 * 32 + cl, col0 = (g0 + g) * 8;
+        const bool valid = yx >= 0 && yx < H && c < cend && g < gcount;
         const float* row = xn + (valid ? (long)c * HWl + (long)yx * W : 0);
         load_run<VEC>(row, col0, W, valid, pf[j]);
         // the two neighbours: clamped to the row so that the load needs no branch, zero outside it
@@ -163,7 +136,7 @@ __global__ __launch_bounds__(192 * KT, VEC && KT == 2 ? 3 : 2) void splitconv_wg
       } else if (i < NITEM && ydy >= 0) {
         const int kl = (i - NX) / G, g = (i - NX) - kl * G;
         const int k = kt0 * 32 + kl, col0 = (g0 + g) * 8;
-        const bool valid = k < K && g < gcount;
+        const bool valid = k < kend && g < gcount;
         const float* row = dyn + (valid ? (long)k * HWl + (long)ydy * W : 0);
         load_run<VEC>(row, col0, W, valid, pf[j]);
       }
@@ -220,8 +193,9 @@ __global__ __launch_bounds__(192 * KT, VEC && KT == 2 ? 3 : 2) void splitconv_wg
     __syncthreads();
     fetch(h + 2, h + 1 < h1 ? h + 1 : -1);  // (past the chunk: the x row is loaded for nothing, once)
     const int slot = (h + tr + 2) % 3;  // x row h + tr - 1
-    const unsigned char* const b_base = lds + L::X + (r32 * X_CS + slot * 3 * G + hh) * 16;
-    const unsigned* const bh_base = xh + r32 * XH_CS + slot * 3 * G + hh;
+    const unsigned char* const b_base = lds + L::X + ((ctl * 32 + r32) * X_CS + slot * 3 * G + hh) * 16;
+    const unsigned* const bh_base = xh + (ctl * 32 + r32) * XH_CS + slot * 3 * G + hh;
+    if (ctl >= blk.ctn || ktl >= blk.ktn) continue;  // (wave-uniform) a part one tile short: this wave has no tile, it only stages
     f32x16 acc[3];
     acc_zero(acc);
     // the x fragments of plane p for the three tap columns: the aligned run and the two runs shifted by one pixel
@@ -265,15 +239,14 @@ __global__ __launch_bounds__(192 * KT, VEC && KT == 2 ? 3 : 2) void splitconv_wg
     for (int s = 0; s < 3; ++s) tot[s] = tot[s] + acc[s];
   }
   // accumulator register i of lane (r32, hh) is output channel acc_channel(i, hh) of the tile, input channel r32
-  const int c = ct * 32 + r32;
-  if (c < C) {
+  const int c = (ct0 + ctl) * 32 + r32;
+  if (c < cend) {
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
-      float* const wt = ws + ((long)chunk * 9 + (tr * 3 + s)) * K * C;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int k = 32 * (kt0 + ktl) + acc_channel(i, hh);
-        if (k < K) wt[(long)k * C + c] = tot[s][i];
+        if (k < kend) ws[ws_index(chunk, tr * 3 + s, k, c, K, C)] = tot[s][i];
       }
     }
   }
@@ -290,16 +263,19 @@ __global__ __launch_bounds__(256) void splitconv_wgrad_finish_kernel(const float
   dw[(long)kc * 9 + tap] = (float)s;
 }
 
-template <int KT, bool VEC>
-int launch(const float* x, long x_bs, const float* dy, long dy_bs, float* ws, int C, int K, int H, int W, int kt_first, int kcnt,
+template <int KT, int CT, bool VEC>
+int launch(const float* x, long x_bs, const float* dy, long dy_bs, float* ws, int C, int K, int H, int W, const Launch& l,
            const Plan& p, hipStream_t st) {
-  using L = Lds<KT>;
-  if (const int rc = allow_dynamic_lds<&splitconv_wgrad_kernel<KT, VEC>>(L::BYTES)) return rc;
-  const long grid = p.chunks * kcnt * p.nct;
-  if (grid > INT_MAX) return ARFLOW_ESHAPE;
-  hipLaunchKernelGGL((splitconv_wgrad_kernel<KT, VEC>), dim3((unsigned)grid), dim3(192 * KT), L::BYTES, st, x, x_bs, dy, dy_bs, ws, C, K,
-                     H, W, kt_first, kcnt, p.nct, p.nstrips, p.SG, p.nrb, p.RPC);
-  return af_launch_status();
+  if constexpr (CT > plan_ct(KT, VEC)) {
+    return ARFLOW_ESHAPE;  // make_launch never asks for it: not built
+  } else {
+    using L = Lds<KT, CT>;
+    if (const int rc = allow_dynamic_lds<&splitconv_wgrad_kernel<KT, CT, VEC>>(L::BYTES)) return rc;
+    if (l.blocks > INT_MAX) return ARFLOW_ESHAPE;
+    hipLaunchKernelGGL((splitconv_wgrad_kernel<KT, CT, VEC>), dim3((unsigned)l.blocks), dim3(192 * KT * CT), L::BYTES, st, x, x_bs, dy,
+                       dy_bs, ws, C, K, H, W, l, p.SG, p.RPC);
+    return af_launch_status();
+  }
 }
 }  // namespace
 
@@ -307,7 +283,7 @@ extern "C" long arflow_splitconv_wgrad_ws_bytes(int N, int C, int K, int H, int 
   if (!shape_ok(N, C, K, H, W)) return ARFLOW_ESHAPE;
   const Plan p = make_plan(N, C, K, H, W);
   if (p.chunks > INT_MAX) return ARFLOW_ESHAPE;
-  return p.chunks * 9 * K * C * 4;
+  return ws_bytes(p, K, C);
 }
 
 extern "C" int arflow_splitconv_wgrad(const float* x, long x_bstride, const float* dy, long dy_bstride, float* dw, void* ws, int N,
@@ -326,16 +302,18 @@ extern "C" int arflow_splitconv_wgrad(const float* x, long x_bstride, const floa
   hipStream_t st = (hipStream_t)stream;
   // float4 loads where every row starts on a 16-byte boundary
   const bool vec = W % 4 == 0 && af_vec4_ok(x, x_bstride, N) && af_vec4_ok(dy, dy_bstride, N);
-  for (const TilePart& t : split_tiles(p.nkt, MAX_KT)) {  // one launch per part
-    if (t.count == 0) continue;
-    const auto go = [&](auto kt_c, auto vec_c) {
-      return launch<decltype(kt_c)::value, decltype(vec_c)::value>(x, x_bstride, dy, dy_bstride, (float*)ws, C, K, H, W, t.first, t.count, p, st);
-    };
-    using std::integral_constant;
-    const int rc = t.kt == 1 ? (vec ? go(integral_constant<int, 1>{}, std::true_type{}) : go(integral_constant<int, 1>{}, std::false_type{}))
-                           : (vec ? go(integral_constant<int, 2>{}, std::true_type{}) : go(integral_constant<int, 2>{}, std::false_type{}));
-    if (rc != ARFLOW_OK) return rc;
-  }
+  const Launch l = make_launch(p, vec);  // one launch: the parts of both channel axes are decoded from the block id
+  const auto go = [&](auto kt_c, auto ct_c, auto vec_c) {
+    return launch<decltype(kt_c)::value, decltype(ct_c)::value, decltype(vec_c)::value>(x, x_bstride, dy, dy_bstride, (float*)ws, C, K, H,
+                                                                                        W, l, p, st);
+  };
+  const auto go_ct = [&](auto kt_c, auto vec_c) {
+    return l.ct == 1 ? go(kt_c, std::integral_constant<int, 1>{}, vec_c) : go(kt_c, std::integral_constant<int, 2>{}, vec_c);
+  };
+  const auto go_kt = [&](auto vec_c) {
+    return l.kt == 1 ? go_ct(std::integral_constant<int, 1>{}, vec_c) : go_ct(std::integral_constant<int, 2>{}, vec_c);
+  };
+  if (const int rc = vec ? go_kt(std::true_type{}) : go_kt(std::false_type{})) return rc;
   hipLaunchKernelGGL(splitconv_wgrad_finish_kernel, dim3((unsigned)af_cdiv((long)9 * K * C, 256)), dim3(256), 0, st,
                      (const float*)ws, dw, K, C, (int)p.chunks);
   return af_launch_status();

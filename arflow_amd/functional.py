@@ -806,12 +806,17 @@ def splitconv_wgrad_takes(N, C, K, H, W):
 
 def _splitconv_wgrad_rule(N, C, K, H, W):
     # never below N H W = 16 x 48 x 80 (the shapes of the existing tests keep MIOpen's dw); measured at N = 16 over the seven
-    # (C, K) of section 17 and four map sizes: ahead of MIOpen's solver plus its layout copies by more than the spread of both
-    # only at 96x160 with many input channels -- 499->64 1.09x, 563->32 1.40x, 597->128 1.06x (403->96 1.02x, 147 / 275->128
-    # 0.93x / 0.97x are not) -- and on no call at 48x80 (0.75x .. 1.04x), 24x40 or 12x20
+    # (C, K) of section 17 and four map sizes with the 2 x 2 tiles of section 35 (profiles/wgrad_tile_kbench.log): the kernel's
+    # max is below the min of MIOpen's solver plus its layout copies at 96x160 on the six wide layers -- 147->128 1.23x,
+    # 275->128 1.36x, 403->96 1.55x, 499->64 1.55x, 563->32 1.46x, 597->128 1.39x (64->32 0.67x is not) -- and at 48x80 on
+    # 275->128 1.10x, 403->96 1.23x, 499->64 1.51x, 597->128 1.27x (147->128 0.90x is not; 563->32 1.06x, a single tile of
+    # output channels, is left where it was); on two calls at 24x40 (1.1x), which the floor keeps out
     if N * H * W < 16 * 48 * 80:
         return False
-    return _size_floor(N, H, W, 96, 160) and 448 <= C <= 640 and 32 <= K <= 128
+    if _size_floor(N, H, W, 96, 160):
+        return 128 <= C <= 640 and 32 <= K <= 128
+    # (fewer maps of 96x160 or more were not measured: they keep MIOpen)
+    return H * W < 96 * 160 and _size_floor(N, H, W, 48, 80) and 256 <= C <= 640 and 64 <= K <= 128
 
 
 def _batch_strided(t):
@@ -995,7 +1000,8 @@ def _inplace_wgrad_rule(N, C, K, H, W):
     # the three layers _splitconv_wgrad_rule leaves to MIOpen at 96x160, measured at N = 16 against MIOpen's call on the slice
     # (solver + layout copies + ATen's contiguous copy of x_k): 275->128 -103 us and 403->96 -230 us, ranges apart; 147->128 -24 us,
     # ranges apart in one job and touching in three others -- a tie in time, taken for the 144 MB copy it does not allocate.
-    # Never below that size.
+    # Never below that size.  (With the 2 x 2 tiles of section 35 _splitconv_wgrad_rule takes all three on its own -- in place the
+    # kernel is 260 .. 850 us ahead of MIOpen + copy -- so this rule adds no layer today; it stays as the in-place path's own.)
     return _size_floor(N, H, W, 96, 160) and 128 <= C < 448 and 96 <= K <= 128
 
 
