@@ -129,6 +129,9 @@ PROTOTYPES = {
     'arflow_mse_fwd': [c_fp, c_l, c_i, c_fp, c_l, c_i, c_i, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp],
     'arflow_mse_bwd': [c_fp, c_l, c_i, c_fp, c_l, c_i, c_i, c_fp, c_l, c_fp, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_resize_flow': [c_fp, c_l, c_i, c_i, c_fp, c_l, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_augment_partials': [c_i, c_i],
+    'arflow_augment_stats': [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_augment_apply': [c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_uncert_rows': [c_i, c_i],
     'arflow_uncert_prep': [c_fp, c_fp, c_fp, c_l, c_fp, c_fp, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_sparsify_sums': [c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp],

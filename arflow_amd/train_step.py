@@ -120,20 +120,26 @@ class TrainStep:
         self.last = None
         self._target = None
 
-    def __call__(self, img_pair, target=None):
+    def __call__(self, img_pair, target=None, img_pair_ph=None):
+        """img_pair_ph: the photometrically augmented version of img_pair (arflow_amd.augment).  The model sees it, the loss
+        always sees img_pair (trainer/uflow_trainer.py:47-54); None: the model sees img_pair too."""
+        model_in = img_pair if img_pair_ph is None else img_pair_ph
+        if model_in.shape != img_pair.shape:
+            raise ValueError('img_pair_ph must have the shape of img_pair %s (got %s)'
+                             % (tuple(img_pair.shape), tuple(model_in.shape)))
         if self.loss_cfg.type == 'mse':  # supervised: the forward direction alone against the ground-truth flow
             if target is None:  # a seeded synthetic flow of the batch's shape, made once
                 shape = (img_pair.shape[0],) + tuple(img_pair.shape[2:])
                 if self._target is None or self._target[0] != shape:
                     self._target = (shape, synthetic_flow(*shape, device=img_pair.device, seed=7))
                 target = self._target[1]
-            res = self.model(img_pair[:, :3], img_pair[:, 3:], with_bk=False)
+            res = self.model(model_in[:, :3], model_in[:, 3:], with_bk=False)
             return self._step(self.loss(res['flows_fw'], target))
         if self.loss_cfg.type == 'uflow_elbo':  # trainer/uflow_elbo_trainer.py: the model and the loss take the two frames
-            res = self.model(img_pair[:, :3], img_pair[:, 3:], with_bk=True)
+            res = self.model(model_in[:, :3], model_in[:, 3:], with_bk=True)
             out = self.loss(res, img_pair[:, :3], img_pair[:, 3:])
             return self._step(out)
-        res = self.model(img_pair, with_bk=True)
+        res = self.model(model_in, with_bk=True)
         if self.loss_cfg.type == 'mv':
             out = self.loss(res['flows_fw'], res['flows_bw'], img_pair)
         else:

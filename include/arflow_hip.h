@@ -862,6 +862,57 @@ int arflow_warp_bwd_bf16(const float* gout, const unsigned short* src, const flo
                          int B, int C, int Hs, int Ws, int H, int W, long flow_bstride, int pad_mode, int align_corners,
                          int norm_mode, arflow_stream_t stream);
 
+/* ---- on-device batch augmentation (csrc/augment.hip) -------------------------------
+ * transforms/geometric_transforms.py:7-15 (crop -> hflip -> scale) and transforms/photometric_transforms.py:7-25 (ColorJitter
+ * -> gamma -> channel permutation) on a whole batch:  src [B][F][3][Hs][Ws] contiguous, F = 1 .. ARFLOW_AUG_MAX_FRAMES, dtype
+ * ARFLOW_AUG_U8 (0 .. 255, divided by 255) or ARFLOW_AUG_F32 (already in [0,1])  ->  img [B][3F][h][w] (geometric only) and
+ * img_ph [B][3F][h][w] (geometric + photometric; NULL: not produced), both float32 and stored from ONE read of src.
+ *
+ * table: B rows of ARFLOW_AUG_ROW 32-bit words ON THE DEVICE, written once per batch by the host; every frame of a sample
+ * uses the sample's row.
+ *   word ARFLOW_AUG_Y1, ARFLOW_AUG_X1   int    crop origin in the source (the window is th x tw for every sample; the kernels
+ *                                              clamp the origin into [0, Hs - th] x [0, Ws - tw], the HOST checks it)
+ *   word ARFLOW_AUG_FLAGS               int    ARFLOW_AUG_FLIP | ARFLOW_AUG_ACTIVE(op) for each active ColorJitter operation |
+ *                                              ARFLOW_AUG_GAMMA_ON
+ *   word ARFLOW_AUG_ORDER               int    the sample's operation order: the k-th operation applied is bits 2k, 2k + 1
+ *                                              (0 brightness, 1 contrast, 2 saturation, 3 hue); inactive ones are skipped
+ *   word ARFLOW_AUG_PERM                int    output channel c of every frame is channel (perm >> 2c) & 3 (identity: 0x24)
+ *   words ARFLOW_AUG_FACTOR + op        float  the factor of operation op
+ *   word ARFLOW_AUG_GAMMA               float  the exponent
+ *   the remaining words are reserved (0).
+ * scale = 0: (h, w) must equal (th, tw) and img is src / 255 at the mapped pixel bit for bit; scale = 1: the cropped, flipped
+ * th x tw image is resized bilinearly to (h, w), align_corners = False.
+ *
+ * arflow_augment_stats: needed only when some sample has contrast active (and img_ph is wanted).  Stores, for every frame of
+ *   such a sample, arflow_augment_partials(h, w) float64 partial sums of grey of the frame as it stands in front of contrast
+ *   into work [B F][partials] (one per workgroup; the rows of other samples are not touched and not read).
+ * arflow_augment_apply: stores every element of img and, when not NULL, of img_ph; adds a frame's partials in index order.
+ *   work may be NULL when no sample has contrast active.  No atomics: two calls give the same bits in either mode.
+ * arflow_augment_partials: the partial count per frame, or ARFLOW_ESHAPE; needs no GPU.
+ *
+ * ARFLOW_ENULL: a required pointer is NULL;  ARFLOW_ESHAPE: B, F, h, w, Hs, Ws, th or tw < 1, F > ARFLOW_AUG_MAX_FRAMES,
+ * B F > 65535, a plane of 2^30 elements or more, th > Hs or tw > Ws (a crop window outside the source), (h, w) != (th, tw)
+ * with scale = 0;  ARFLOW_EPARAM: dtype or scale not 0 / 1. */
+#define ARFLOW_AUG_U8 0
+#define ARFLOW_AUG_F32 1
+#define ARFLOW_AUG_MAX_FRAMES 5
+#define ARFLOW_AUG_ROW 16
+#define ARFLOW_AUG_Y1 0
+#define ARFLOW_AUG_X1 1
+#define ARFLOW_AUG_FLAGS 2
+#define ARFLOW_AUG_ORDER 3
+#define ARFLOW_AUG_PERM 4
+#define ARFLOW_AUG_FACTOR 5
+#define ARFLOW_AUG_GAMMA 9
+#define ARFLOW_AUG_FLIP 1
+#define ARFLOW_AUG_ACTIVE(op) (2 << (op))
+#define ARFLOW_AUG_GAMMA_ON 32
+int arflow_augment_partials(int h, int w);
+int arflow_augment_stats(const void* src, int dtype, const int* table, double* work, int B, int F, int Hs, int Ws, int th,
+                         int tw, int h, int w, int scale, arflow_stream_t stream);
+int arflow_augment_apply(const void* src, int dtype, const int* table, const double* work, float* img, float* img_ph, int B,
+                         int F, int Hs, int Ws, int th, int tw, int h, int w, int scale, arflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

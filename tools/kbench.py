@@ -5,6 +5,7 @@ fraction of the 8 TB/s HBM roofline.  Calls the C ABI directly (no autograd over
     python tools/kbench.py [--iters 50] [--filter corr] [--levels uflow|pwclite]
     python tools/kbench.py --filter gauss_pyr      # the pyramid sampler node and an ElboLoss step
     python tools/kbench.py --filter mse            # one MseLoss step, fused against composed ATen ops
+    python tools/kbench.py --filter augment        # the batch augmentation, fused against composed ATen ops
 """
 import argparse
 import json
@@ -603,6 +604,50 @@ def mse_bench(dev, g, B=16, h=96, w=128, H=384, W=512, launches=30, repeats=5):
                   % (tag, statistics.median(t['composed ATen step']) / statistics.median(t['fused step']), a, b), flush=True)
 
 
+def augment_bench(dev, jsonl, B=64, src_hw=(384, 512), crop_hw=(256, 448), launches=20, repeats=5):
+    """arflow_amd.augment.augment_batch (one launch; two where contrast is active) on B = 64 uint8 pairs of
+    384 x 512 cropped to 256 x 448 -- configs/chairs_uflow_elbo.json: hflip, crop, hue 0.5, swap_channels -- and the same
+    geometry under the full jitter (brightness, contrast, saturation 0.4, hue 0.5, gamma, swap), next to the same transform
+    composed of ATen operations on the same device (tests/augment_ref.py in float32: index gather for crop and flip, the
+    formulas of the four operations per group of samples that share an operation at a step, pow, index permutation).  HIP
+    events around `launches` calls after 5 warm-ups, the versions in alternation, `repeats` rounds: median (min .. max).
+    Algorithmic bytes: the crop windows of the source once + both outputs once."""
+    import statistics
+    from arflow_amd import augment as A
+    from tests import augment_ref as R
+    cpu = torch.Generator().manual_seed(0)
+    src = torch.randint(0, 256, (B, 2, 3) + tuple(src_hw), dtype=torch.uint8, generator=cpu).to(dev)
+    geo = dict(crop=True, crop_size=list(crop_hw), hflip=True)
+    cases = {'hue+swap (chairs_uflow_elbo.json)': dict(hue=0.5, swap_channels=True),
+             'full jitter, contrast active': dict(brightness=0.4, contrast=0.4, saturation=0.4, hue=0.5, gamma=1, swap_channels=True)}
+    th, tw = crop_hw
+    nbytes = B * 2 * 3 * th * tw * (1 + 2 * 4)
+    with open(jsonl, 'a') as out:
+        for tag, pho in cases.items():
+            params = A.draw_params(geo, pho, B, src_hw, cpu)
+            fns = {'fused': lambda: A.augment_batch(src, params), 'composed ATen': lambda: R.augment(src, params, dtype=torch.float32)}
+            a, b = fns['fused'](), fns['composed ATen']()
+            diff = [float((a[0] - b[0]).abs().max()), float((a[1] - b[1]).abs().max())]
+            del a, b
+            t = {name: [] for name in fns}
+            for _ in range(repeats):
+                for name, fn in fns.items():
+                    t[name].append(timeit(fn, launches))
+                    MANIFEST[-1].update(name='augment/' + name, shape=[])
+            line = {'bench': 'augment', 'case': tag, 'shape': [B, 2, 3] + list(src_hw), 'crop': list(crop_hw), 'dtype': 'uint8',
+                    'algorithmic_bytes': nbytes, 'max_abs_diff_img': diff[0], 'max_abs_diff_img_ph': diff[1]}
+            for name, v in t.items():
+                key = name.split()[0]
+                line.update({key + '_us': statistics.median(v), key + '_us_min': min(v), key + '_us_max': max(v)})
+                print('augment %-36s %-14s %9.1f us (%.1f .. %.1f)' % (tag, name, statistics.median(v), min(v), max(v)), flush=True)
+            gbs = nbytes / line['fused_us'] / 1e3
+            line.update(fused_gbs=gbs, fused_fraction_of_hbm_peak=gbs / HBM_PEAK_GBS, hbm_peak_gbs=HBM_PEAK_GBS,
+                        composed_over_fused=line['composed_us'] / line['fused_us'])
+            print('augment %-36s composed / fused = %.2f   fused %.0f GB/s = %.1f%% of HBM peak   (max |diff| img %.1e, img_ph %.1e)'
+                  % (tag, line['composed_over_fused'], gbs, 100 * gbs / HBM_PEAK_GBS, diff[0], diff[1]), flush=True)
+            out.write(json.dumps(line) + '\n')
+
+
 def main():
     if os.environ.get('ARFLOW_LIB_PATH'):  # an alternative build of the library (A/B timing; tools only)
         _lib.LIB_PATH = os.environ['ARFLOW_LIB_PATH']
@@ -612,6 +657,8 @@ def main():
     ap.add_argument('--levels', default='uflow')
     ap.add_argument('--batch', type=int, default=16, help='model-side batch (2B: both directions stacked)')
     ap.add_argument('--size', type=int, nargs=2, default=[384, 640])
+    ap.add_argument('--jsonl', default=os.path.join(ROOT, 'profiles', 'augment_kbench.jsonl'),
+                    help='--filter augment appends its result lines here')
     ap.add_argument('--manifest', default='', help='write the ordered (name, shape, calls) list of the timed ops here')
     args = ap.parse_args()
     lib = _lib.load()
@@ -1038,6 +1085,8 @@ def main():
         gauss_pyr_bench(dev, g)
     if want('mse'):  # one MseLoss step on the fused residual kernels (csrc/mse.hip) against the composed ATen formulation
         mse_bench(dev, g)
+    if want('augment'):  # the batch augmentation (csrc/augment.hip) against the same transform composed of ATen operations
+        augment_bench(dev, args.jsonl)
     if args.manifest:
         json.dump(MANIFEST, open(args.manifest, 'w'), indent=1)
     if not rows:  # only ops that keep their own byte model (the head convolutions) were selected
