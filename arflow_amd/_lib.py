@@ -14,6 +14,7 @@ c_fp = ctypes.c_void_p  # device pointers travel as integers
 c_i = ctypes.c_int
 c_l = ctypes.c_long
 c_f = ctypes.c_float
+c_d = ctypes.c_double
 
 # name -> argtypes, exactly the prototypes of include/arflow_hip.h
 PROTOTYPES = {
@@ -132,6 +133,9 @@ PROTOTYPES = {
     'arflow_augment_partials': [c_i, c_i],
     'arflow_augment_stats': [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_augment_apply': [c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_optim_partials': [c_l],
+    'arflow_optim_gradnorm': [c_fp, c_fp, c_l, c_fp],
+    'arflow_optim_step': [c_fp, c_i, c_fp, c_fp, c_fp, c_l, c_fp, c_i, c_fp, c_i, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_d, c_fp],
     'arflow_uncert_rows': [c_i, c_i],
     'arflow_uncert_prep': [c_fp, c_fp, c_fp, c_l, c_fp, c_fp, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_sparsify_sums': [c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp],

@@ -92,7 +92,9 @@ def synthetic_flow(batch, height, width, device='cuda', seed=0):
 
 
 class TrainStep:
-    def __init__(self, workload, device, lr=1e-4, seed=0, n_buckets=4, feature_storage='fp32'):
+    def __init__(self, workload, device, lr=1e-4, seed=0, n_buckets=4, feature_storage='fp32', train_cfg=None):
+        """train_cfg: the `train` section of a config (optim, lr, decay groups, clip, lr schedule): the step is then taken by
+        arflow_amd.optim.FlatOptimizer on the flat gradient buffer and `lr` is ignored.  None: torch.optim.Adam as below."""
         mcfg, lcfg = WORKLOADS[workload]
         if feature_storage != 'fp32':
             if mcfg['type'] != 'pwclite_uflow':
@@ -113,10 +115,14 @@ class TrainStep:
         ddp.enable_global_loss_norm(os.environ.get('ARFLOW_GLOBAL_LOSS_NORM') == '1')
         # Adam, lr 1e-4, betas (0.9, 0.999), eps 1e-8, no decay: configs/chairs_uflow.json:29-48
         kw = dict(lr=lr, betas=(0.9, 0.999), eps=1e-8)
-        try:
-            self.opt = torch.optim.Adam(self.model.parameters(), fused=(device.type == 'cuda'), **kw)
-        except (TypeError, RuntimeError):
-            self.opt = torch.optim.Adam(self.model.parameters(), **kw)
+        if train_cfg is not None:
+            from .optim import FlatOptimizer
+            self.opt = FlatOptimizer(self.reducer, train_cfg)
+        else:
+            try:
+                self.opt = torch.optim.Adam(self.model.parameters(), fused=(device.type == 'cuda'), **kw)
+            except (TypeError, RuntimeError):
+                self.opt = torch.optim.Adam(self.model.parameters(), **kw)
         self.last = None
         self._target = None
 
@@ -154,3 +160,15 @@ class TrainStep:
         self.opt.step()
         self.last = out[0].detach()
         return self.last
+
+    def save(self, path, epoch):
+        """{'epoch', 'state_dict'} as trainer/base_trainer.py:155-156 writes them (utils/torch_utils.load_checkpoint reads the
+        file), plus 'optimizer': the state of whichever optimiser the step holds."""
+        torch.save({'epoch': int(epoch), 'state_dict': self.model.state_dict(), 'optimizer': self.opt.state_dict()}, path)
+
+    def restore(self, path):
+        """Load what save() wrote into the model and the optimiser, in place (parameter storage does not move) -> epoch."""
+        ckpt = torch.load(path, map_location=next(self.model.parameters()).device)
+        self.model.load_state_dict(ckpt['state_dict'])
+        self.opt.load_state_dict(ckpt['optimizer'])
+        return ckpt['epoch']

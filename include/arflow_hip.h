@@ -913,6 +913,47 @@ int arflow_augment_stats(const void* src, int dtype, const int* table, double* w
 int arflow_augment_apply(const void* src, int dtype, const int* table, const double* work, float* img, float* img_ph, int B,
                          int F, int Hs, int Ws, int th, int tw, int h, int w, int scale, arflow_stream_t stream);
 
+/* ---- fused optimiser step on the flat gradient buffer (csrc/optim.hip) --------------
+ * trainer/base_trainer.py:78-129 (Adam / the reference's AdamW / SGD over a decay and a no-decay group) and the
+ * clip_grad_norm_ of trainer/uflow_elbo_trainer.py:94-99, for the WHOLE model in one launch (two with the norm).
+ *
+ * grad, s1, s2: flat float32 buffers of n elements in ONE layout (s1 = exp_avg or momentum_buffer, s2 = exp_avg_sq, NULL for
+ *   ARFLOW_OPTIM_SGD).  The parameters stay where they are: the chunk table names them.
+ * table: nrows rows of ARFLOW_OPTIM_ROW 64-bit words ON THE DEVICE, one workgroup each:
+ *   word ARFLOW_OPTIM_ADDR    the address of the row's first parameter element (float32, 4-byte aligned)
+ *   word ARFLOW_OPTIM_OFFSET  the flat offset of that element in grad / s1 / s2
+ *   word ARFLOW_OPTIM_COUNT   1 .. ARFLOW_OPTIM_CHUNK elements, all of ONE parameter tensor
+ *   word ARFLOW_OPTIM_DECAY   the weight decay of the tensor's group, the bits of a double
+ *   A row with offset < 0, a count outside 1 .. ARFLOW_OPTIM_CHUNK or offset + count > n is not run.  The kernel cannot check
+ *   the address: the caller guarantees it (arflow_amd.optim compares every data_ptr() with the table before every step).
+ * arflow_optim_gradnorm: stores arflow_optim_partials(n) float64 partial sums of grad^2 (one per workgroup; no atomics, no
+ *   zero-fill: two calls give the same bits in either mode).  arflow_optim_partials needs no GPU; ARFLOW_ESHAPE for n < 1.
+ * arflow_optim_step: nparts = 0: no norm, the gradient is used as it stands (clip must be <= 0 and skipped NULL).  nparts =
+ *   arflow_optim_partials(n): the partials are added in index order, total_norm = sqrt(sum), and the gradient is multiplied by
+ *   min(1, clip / (total_norm + 1e-6)) as it is read when clip > 0 (the stored gradient is NOT rewritten).  skipped != NULL
+ *   turns the non-finite guard on: when total_norm is not finite nothing is written but *skipped, which is incremented.
+ *   The scalars are doubles and are rounded to float32 once, in the kernel: lr, bc1 = 1 - beta1^t, sqbc2 = sqrt(1 - beta2^t),
+ *   eps, beta1 (the momentum for SGD), beta2, clip.  first = 1: SGD's buffer becomes the gradient (its first step).  The
+ *   float32 operation order of each rule is written at the head of csrc/optim.hip.
+ *
+ * ARFLOW_ENULL: a required pointer is NULL;  ARFLOW_ESHAPE: nrows or n < 1, nparts neither 0 nor arflow_optim_partials(n);
+ * ARFLOW_EPARAM: an unknown rule, first not 0 / 1, clip > 0 or skipped without partials, lr or clip not finite, a beta outside
+ * [0, 1), eps < 0, bc1 or sqbc2 outside (0, 1], a misaligned pointer. */
+#define ARFLOW_OPTIM_ADAM 0
+#define ARFLOW_OPTIM_ADAMW 1
+#define ARFLOW_OPTIM_SGD 2
+#define ARFLOW_OPTIM_CHUNK 2048
+#define ARFLOW_OPTIM_ROW 4
+#define ARFLOW_OPTIM_ADDR 0
+#define ARFLOW_OPTIM_OFFSET 1
+#define ARFLOW_OPTIM_COUNT 2
+#define ARFLOW_OPTIM_DECAY 3
+int arflow_optim_partials(long n);
+int arflow_optim_gradnorm(const float* grad, double* partials, long n, arflow_stream_t stream);
+int arflow_optim_step(const long long* table, int nrows, const float* grad, float* s1, float* s2, long n, const double* partials,
+                      int nparts, int* skipped, int rule, int first, double lr, double bc1, double sqbc2, double eps, double beta1,
+                      double beta2, double clip, arflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

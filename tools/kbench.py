@@ -6,6 +6,7 @@ fraction of the 8 TB/s HBM roofline.  Calls the C ABI directly (no autograd over
     python tools/kbench.py --filter gauss_pyr      # the pyramid sampler node and an ElboLoss step
     python tools/kbench.py --filter mse            # one MseLoss step, fused against composed ATen ops
     python tools/kbench.py --filter augment        # the batch augmentation, fused against composed ATen ops
+    python tools/kbench.py --filter optim          # the fused optimiser step against torch.optim.Adam(fused=True)
 """
 import argparse
 import json
@@ -648,6 +649,64 @@ def augment_bench(dev, jsonl, B=64, src_hw=(384, 512), crop_hw=(256, 448), launc
             out.write(json.dumps(line) + '\n')
 
 
+def optim_bench(dev, jsonl, launches=20, repeats=5):
+    """arflow_amd.optim.FlatOptimizer.step() (one launch; two with the clip) on the parameters of
+    PWCProbFlow [2,2,0] (5,909,172 elements) under the train section of configs/chairs_uflow_elbo.json, next to what TrainStep
+    does today on the same flat gradient buffer: torch.optim.Adam(fused=True), plus torch.nn.utils.clip_grad_norm_ for the clip
+    case.  HIP events around `launches` calls after 5 warm-ups, the legs in alternation, `repeats` rounds: median (min .. max).
+    Algorithmic bytes: 7 x 4 N for the step (p, m, v read and written, g read), 4 N more for the norm."""
+    import statistics
+    from arflow_amd.config import AttrDict
+    from arflow_amd.ddp import FlatGradAllReduce
+    from arflow_amd.models import get_model
+    from arflow_amd.optim import FlatOptimizer
+    STREAM_GBS = 6300.0  # what a plain device-to-device stream reaches of the 8 TB/s peak (tools/copy_bw.py measures it)
+    mcfg = AttrDict(type='uflow_prob', feature_norm=True, level_dropout=0.1, out_channels=[2, 2, 0], inv_cov=False, n_pyramids=1,
+                    mixture_weights=False)
+    train = dict(optim='adam', lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-6, bias_decay=0.0)
+    cpu = torch.Generator().manual_seed(0)
+    with open(jsonl, 'a') as out:
+        for tag, clip in (('adam, clip off', -1.0), ('adam, clip 1.0', 1.0)):
+            legs = {}
+            for name in ('fused', 'torch'):
+                torch.manual_seed(0)
+                model = get_model(mcfg)
+                model.init_weights()
+                model.to(dev)
+                reducer = FlatGradAllReduce(model)
+                reducer.flat.copy_(1e-3 * torch.randn(reducer.flat.numel(), generator=torch.Generator().manual_seed(1)))
+                if name == 'fused':
+                    opt = FlatOptimizer(reducer, AttrDict(dict(train, clip=clip)))
+                    legs[name] = (opt.step, model, reducer, opt)
+                else:
+                    params = list(model.parameters())
+                    opt = torch.optim.Adam(params, fused=True, lr=train['lr'], betas=(0.9, 0.999), eps=1e-8)
+
+                    def torch_step(params=params, opt=opt, clip=clip):
+                        if clip > 0:
+                            torch.nn.utils.clip_grad_norm_(params, clip)
+                        opt.step()
+                    legs[name] = (torch_step, model, reducer, opt)
+            n = legs['fused'][2].flat.numel()
+            nbytes = 4 * n * (8 if clip > 0 else 7)
+            t = {name: [] for name in legs}
+            for _ in range(repeats):
+                for name, leg in legs.items():
+                    t[name].append(timeit(leg[0], launches))
+                    MANIFEST[-1].update(name='optim/' + name, shape=[n])
+            line = {'bench': 'optim', 'case': tag, 'model': 'PWCProbFlow [2,2,0]', 'elements': n, 'tensors': len(legs['fused'][2]._spans),
+                    'table_rows': int(legs['fused'][3]._table.shape[0]), 'algorithmic_bytes': nbytes, 'launches': launches, 'rounds': repeats}
+            for name, v in t.items():
+                line.update({name + '_us': statistics.median(v), name + '_us_min': min(v), name + '_us_max': max(v)})
+                print('optim %-18s %-8s %9.1f us (%.1f .. %.1f)' % (tag, name, statistics.median(v), min(v), max(v)), flush=True)
+            gbs = nbytes / line['fused_us'] / 1e3
+            line.update(fused_gbs=gbs, stream_gbs=STREAM_GBS, fused_fraction_of_stream=gbs / STREAM_GBS,
+                        torch_over_fused=line['torch_us'] / line['fused_us'])
+            print('optim %-18s torch / fused = %.2f   fused %.0f GB/s = %.1f%% of the %.0f GB/s a stream reaches   (%d elements, %d rows)'
+                  % (tag, line['torch_over_fused'], gbs, 100 * gbs / STREAM_GBS, STREAM_GBS, n, line['table_rows']), flush=True)
+            out.write(json.dumps(line) + '\n')
+
+
 def main():
     if os.environ.get('ARFLOW_LIB_PATH'):  # an alternative build of the library (A/B timing; tools only)
         _lib.LIB_PATH = os.environ['ARFLOW_LIB_PATH']
@@ -657,8 +716,8 @@ def main():
     ap.add_argument('--levels', default='uflow')
     ap.add_argument('--batch', type=int, default=16, help='model-side batch (2B: both directions stacked)')
     ap.add_argument('--size', type=int, nargs=2, default=[384, 640])
-    ap.add_argument('--jsonl', default=os.path.join(ROOT, 'profiles', 'augment_kbench.jsonl'),
-                    help='--filter augment appends its result lines here')
+    ap.add_argument('--jsonl', default='', help='--filter augment and --filter optim append their result lines here '
+                    '(default: profiles/augment_kbench.jsonl and profiles/optim_kbench.jsonl)')
     ap.add_argument('--manifest', default='', help='write the ordered (name, shape, calls) list of the timed ops here')
     args = ap.parse_args()
     lib = _lib.load()
@@ -1086,7 +1145,9 @@ def main():
     if want('mse'):  # one MseLoss step on the fused residual kernels (csrc/mse.hip) against the composed ATen formulation
         mse_bench(dev, g)
     if want('augment'):  # the batch augmentation (csrc/augment.hip) against the same transform composed of ATen operations
-        augment_bench(dev, args.jsonl)
+        augment_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'augment_kbench.jsonl'))
+    if want('optim'):  # the fused optimiser step (csrc/optim.hip) against torch.optim.Adam(fused=True) on the same flat buffer
+        optim_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'optim_kbench.jsonl'))
     if args.manifest:
         json.dump(MANIFEST, open(args.manifest, 'w'), indent=1)
     if not rows:  # only ops that keep their own byte model (the head convolutions) were selected
