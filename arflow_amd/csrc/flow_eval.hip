@@ -7,7 +7,7 @@
 // Per ground-truth pixel, fp32, in the reference's order (flow_utils.py:137-146):
 //   taps   u = (pred_u / w) * W,  v = (pred_v / h) * H                       scaled BEFORE the resize
 //   resize bilinear, half-pixel rule (cv2.INTER_LINEAR = ATen upsample_bilinear2d(align_corners=False) with a size given):
-//          up_source / up_blend of taps.hpp, the device code of flow_up.hip and of the level's x2 upsample
+//          up_source / up_blend of upsample_dev.hpp, the device code of upsample.hip and of the level's x2 upsample
 //   epe  = sqrt(du^2 + dv^2) against gt[:, 0:2];  valid = gt[:, 2], noc = gt[:, 3] (both 1 when C = 2)
 //   bad  = (e > 3) && (e / max(|gt|, 1e-10) > 0.05),  e = epe * valid          (flow_utils.py:123-128)
 // The resize grid is separable: a lane's four columns fix x0, x1 and their weights once, a tile row fixes y0, y1 once.

@@ -1,5 +1,5 @@
 // Launchers shared between translation units: the level entry points (level.hip) chain kernels that live in
-// warp.hip, corr.hip and featnorm.hip inside ONE C-ABI call.
+// warp.hip, corr.hip, featnorm.hip and upsample.hip inside ONE C-ABI call.
 #pragma once
 #include "common.hpp"
 

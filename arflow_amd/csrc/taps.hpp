@@ -3,6 +3,7 @@
 // utils/warp_utils.py:83-90 and utils/uflow_utils.py:53-77), computed once per pixel.
 #pragma once
 #include "common.hpp"
+#include "upsample_dev.hpp"  // up_source / up2_source / up_blend: the bilinear resize, for the kernels that warp and resize
 
 namespace {
 
@@ -82,52 +83,6 @@ __device__ __forceinline__ void tap_select(const TapPlan& p, const float* __rest
 __device__ __forceinline__ void tap_corner_grad(const Taps& t, const float (&v)[4], float& sx, float& sy) {
   sx = (v[1] - v[0]) * t.wy0 + (v[3] - v[2]) * t.wy1;
   sy = (v[2] - v[0]) * t.wx0 + (v[3] - v[1]) * t.wx1;
-}
-
-// Source rows / weights of output index d of the bilinear resize n_in -> n_out: ATen/native/UpSample.h
-// area_pixel_compute_source_index + the index / lambda arithmetic of upsample_bilinear2d.  rs is the half-pixel scale of
-// the align_corners=False map: 1 / scale_factor where the caller of F.interpolate gave one (flow_up.hip, the level's x2),
-// (float)n_in / n_out where it gave a size (flow_eval.hip; cv2.INTER_LINEAR is the same map).  Both taps are clamped.
-__device__ __forceinline__ void up_source(int d, int n_in, int n_out, float rs, bool align, int& i0, int& i1, float& l0,
-                                          float& l1) {
-  float src;
-  if (align) {
-    const float scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
-    src = scale * (float)d;
-  } else {
-    src = rs * ((float)d + 0.5f) - 0.5f;
-    src = src < 0.f ? 0.f : src;
-  }
-  i0 = min((int)src, n_in - 1);
-  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.f - l1;
-}
-// ... the x2 case n_out = 2 n_in of the fused level (scale_factor = 2 given: scale = 1 / 2)
-__device__ __forceinline__ void up2_source(int d, int n_in, int n_out, bool align, int& i0, int& i1, float& l0,
-                                           float& l1) {
-  up_source(d, n_in, n_out, 0.5f, align, i0, i1, l0, l1);
-}
-// ... and the blend of the four taps in ATen's order (rows of the x blend, then y); no contraction (-ffp-contract=off)
-__device__ __forceinline__ float up_blend(float wx0, float wx1, float wy0, float wy1, float a00, float a01, float a10,
-                                          float a11) {
-  return wy0 * (wx0 * a00 + wx1 * a01) + wy1 * (wx0 * a10 + wx1 * a11);
-}
-
-// Gather adjoints of the resize (flow_up.hip, out_up.hip): one thread per coarse cell (i, j).  The fine rows that read
-// coarse row i are those whose source index i0 is i or i - 1, i.e. src in [i - 1, i + 1): a run of consecutive rows found from the inverse of the source map and widened by two on
-// either side -- the weights themselves come from up_source, so a row outside the true run simply weighs 0 and the margin
-// only has to be generous, not exact.  Rows ascending, columns ascending inside a row: a fixed order.
-__device__ __forceinline__ void fine_run(int i, int n_in, int n_out, int factor, bool align, int& lo, int& hi) {
-  if (align) {
-    const float inv = n_in > 1 ? (float)(n_out - 1) / (float)(n_in - 1) : (float)n_out;  // fine rows per coarse row
-    lo = (int)floorf((float)(i - 1) * inv) - 2;
-    hi = (int)ceilf((float)(i + 1) * inv) + 2;
-  } else {
-    lo = factor * (i - 1) - 2;
-    hi = factor * (i + 2) + 2;
-  }
-  lo = max(lo, 0), hi = min(hi, n_out - 1);
 }
 
 // The four target cells and weights of a forward splat at position (cx, cy) (splat_kernel, warp.hip, and its fixed-order

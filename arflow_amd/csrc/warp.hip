@@ -712,50 +712,6 @@ __global__ __launch_bounds__(256) void level_warp_bwd_flow_kernel(const float* _
   level_warp_bwd_flow_body<FIX>(g2n, src, flow, gflow, nimg, C, H, W, fbs, pad, align, norm, add1, add1_bs, add2, la, blockIdx.x);
 }
 
-// Adjoint of the x2 bilinear flow upsample of the level forward (up2_source), times the factor 2 of
-// interpolate(flow * 2): one thread per coarse cell gathers the fine pixels that read it -- rows 2i-2 .. 2i+3 cover
-// either align flag -- in a fixed order (ATen's backward scatters with atomics; this one is reproducible).
-__global__ __launch_bounds__(256) void up2_bwd_kernel(const float* __restrict__ gfine, float* __restrict__ gcoarse,
-                                                      int planes, int H, int W, int up_align) {
-  const int Hc = H / 2, Wc = W / 2;
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)planes * Hc * Wc) return;
-  const int j = (int)(idx % Wc), i = (int)((idx / Wc) % Hc);
-  const long pl = idx / ((long)Wc * Hc);
-  const float* g = gfine + pl * H * W;
-  float wy[6], wx[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    int a0, a1;
-    float l0, l1;
-    const int y = 2 * i - 2 + k;
-    wy[k] = 0.f;
-    if (y >= 0 && y < H) {
-      up2_source(y, Hc, H, up_align != 0, a0, a1, l0, l1);
-      wy[k] = (a0 == i ? l0 : 0.f) + (a1 == i ? l1 : 0.f);
-    }
-    const int x = 2 * j - 2 + k;
-    wx[k] = 0.f;
-    if (x >= 0 && x < W) {
-      up2_source(x, Wc, W, up_align != 0, a0, a1, l0, l1);
-      wx[k] = (a0 == j ? l0 : 0.f) + (a1 == j ? l1 : 0.f);
-    }
-  }
-  float acc = 0.f;
-#pragma unroll
-  for (int ky = 0; ky < 6; ++ky) {
-    const int y = min(max(2 * i - 2 + ky, 0), H - 1);
-    float row = 0.f;
-#pragma unroll
-    for (int kx = 0; kx < 6; ++kx) {
-      const int x = min(max(2 * j - 2 + kx, 0), W - 1);
-      row = fmaf(wx[kx], g[(long)y * W + x], row);
-    }
-    acc = fmaf(wy[ky], row, acc);
-  }
-  gcoarse[idx] = 2.f * acc;
-}
-
 // ------------------------------------------------------------------------------------------------
 // d loss / d src of the warp: the 4-tap scatter turned into a gather through an index list in LDS.
 //
@@ -1588,24 +1544,6 @@ int af_level_warp_bwd_launch(const float* g2n, const float* x2, const float* x2w
                        (const int4*)slab_meta, slab_ovf, gx2, B, C, H, W, (int)per, slab_cap);
   }
   return af_launch_status();
-}
-
-int af_up2_bwd_launch(const float* gfine, float* gcoarse, int planes, int H, int W, int up_align, hipStream_t st) {
-  const long n = (long)planes * (H / 2) * (W / 2);
-  hipLaunchKernelGGL(up2_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gfine, gcoarse, planes, H, W,
-                     up_align);
-  return af_launch_status();
-}
-
-// Adjoint of `flow_up = interpolate(flow * 2, x2, bilinear)` as arflow_level_warp_fwd evaluates it (gather form, no
-// atomics, gcoarse fully written): gfine [B,2,H,W] -> gcoarse [B,2,H/2,W/2].  models/pwclite.py:178-179 backward.
-extern "C" int arflow_up2_bwd(const float* gfine, float* gcoarse, int B, int H, int W, int up_align_corners,
-                              arflow_stream_t stream) {
-  af_clear_stale_error();
-  AF_REQUIRE_PTR(gfine);
-  AF_REQUIRE_PTR(gcoarse);
-  AF_REQUIRE(B > 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && B <= 65535, ARFLOW_ESHAPE);
-  return af_up2_bwd_launch(gfine, gcoarse, B * 2, H, W, up_align_corners, (hipStream_t)stream);
 }
 
 extern "C" int arflow_warp_bwd(const float* gout, const float* src, const float* flow, float* gsrc,

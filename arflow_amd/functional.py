@@ -1431,56 +1431,70 @@ def _plane_view(x):
     return x.contiguous(), C * H * W
 
 
-def _out_up_bwd(g, B, C, h, w, n_flow):
-    """Adjoint of one x2 step: g [B,C,2h,2w] (any channel slice with contiguous planes) -> [B,C,h,w]."""
+# op name -> (entry-point stem, takes a factor argument).  out_upsample is the x2 align_corners=False resize, prob_upsample
+# its align_corners=True sibling for factors 2 and 4 (DESIGN.md sections 22, 27, 38).
+_CHAN_UP = {'out_upsample': ('arflow_out_up2', False), 'prob_upsample': ('arflow_prob_up', True)}
+
+
+def _chan_up_bwd(op, g, B, C, h, w, factor, n_flow):
+    """Adjoint of one step of `op`: g [B,C,factor h,factor w] (any channel slice with contiguous planes) -> [B,C,h,w]."""
+    stem, has_factor = _CHAN_UP[op]
+    f = (factor,) if has_factor else ()
     g, gbs = _plane_view(g)
     gin = torch.empty(B, C, h, w, device=g.device, dtype=torch.float32)
     with torch.cuda.device_of(g):
-        _call('arflow_out_up2_bwd', _p(g), gbs, _p(gin), C * h * w, B, C, h, w, n_flow, _stream(), key=(B, C, h, w, 'bwd'))
+        _call(stem + '_bwd', _p(g), gbs, _p(gin), C * h * w, B, C, h, w, *f, n_flow, _stream(), key=(B, C, h, w, *f, 'bwd'))
     return gin
 
 
-class OutUpsampleFunction(torch.autograd.Function):
-    """models/uflow_prob_model.py:223-250 upsample_out as one launch: out[:, c] = s_c * interpolate(x[:, c] + b_c, x2,
-    bilinear, align_corners=False), s_c = 2 for the first n_flow channels, b_c = diag_bias for the next n_diag.  The adjoint
-    is a gather (arflow_out_up2_bwd): reproducible in either mode, so the node does not sample the mode."""
+class ChannelUpsampleFunction(torch.autograd.Function):
+    """out[:, c] = s_c * interpolate(x[:, c] + b_c, x factor, bilinear), s_c = factor for the first n_flow channels, b_c =
+    diag_bias for the next n_diag, as one launch: op 'out_upsample' is models/uflow_prob_model.py:223-250 upsample_out
+    (x2, align_corners=False), op 'prob_upsample' is models/pwclite_prob.py:183-186,216-217 (x2 or x4, align_corners=True).
+    The adjoint is a gather (arflow_out_up2_bwd / arflow_prob_up_bwd): reproducible in either mode, so the node does not
+    sample the mode."""
 
     @staticmethod
-    def forward(ctx, out, x, n_flow, n_diag, diag_bias):
+    def forward(ctx, out, x, op, factor, n_flow, n_diag, diag_bias):
         # (`out` first: autograd treats input 0 of a node that writes into a view as the tensor modified in place)
         _need_gpu(x, out)
         if x.dim() != 4:
-            raise ValueError('out_upsample expects a [B,C,h,w] tensor')
+            raise ValueError('%s expects a [B,C,h,w] tensor' % op)
         B, C, h, w = x.shape
-        n_flow, n_diag = int(n_flow), int(n_diag)
+        stem, has_factor = _CHAN_UP[op]
+        factor, n_flow, n_diag = int(factor), int(n_flow), int(n_diag)
+        if has_factor and factor not in (2, 4):
+            raise ValueError('%s: factor must be 2 or 4 (got %r)' % (op, factor))
         if n_flow < 0 or n_diag < 0 or n_flow + n_diag > C:
-            raise ValueError('out_upsample: n_flow %d + n_diag %d exceed the %d channels' % (n_flow, n_diag, C))
+            raise ValueError('%s: n_flow %d + n_diag %d exceed the %d channels' % (op, n_flow, n_diag, C))
+        f = (factor,) if has_factor else ()
         x, xbs = _plane_view(x)
         if out is None:
-            out = torch.empty(B, C, 2 * h, 2 * w, device=x.device, dtype=torch.float32)
+            out = torch.empty(B, C, factor * h, factor * w, device=x.device, dtype=torch.float32)
         else:
-            if tuple(out.shape) != (B, C, 2 * h, 2 * w):
-                raise ValueError('out_upsample: out must be [B,C,2h,2w]')
+            if tuple(out.shape) != (B, C, factor * h, factor * w):
+                raise ValueError('%s: out must be [B,C,%dh,%dw]' % (op, factor, factor))
             view, _ = _plane_view(out)
             if view is not out:
-                raise ValueError('out_upsample: out must have contiguous planes (a channel slice of a contiguous buffer)')
+                raise ValueError('%s: out must have contiguous planes (a channel slice of a contiguous buffer)' % op)
             ctx.mark_dirty(out)
         _, obs = _plane_view(out)
         with torch.cuda.device_of(x):
-            _call('arflow_out_up2_fwd', _p(x), xbs, _p(out), obs, B, C, h, w, n_flow, n_diag, float(diag_bias), _stream(),
-                  key=(B, C, h, w, 'fwd'))
-        ctx.cfg = (B, C, h, w, n_flow)
+            _call(stem + '_fwd', _p(x), xbs, _p(out), obs, B, C, h, w, *f, n_flow, n_diag, float(diag_bias), _stream(),
+                  key=(B, C, h, w, *f, 'fwd'))
+        ctx.cfg = (op, B, C, h, w, factor, n_flow)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        return None, _out_up_bwd(gout, *ctx.cfg), None, None, None
+        op, *dims = ctx.cfg
+        return None, _chan_up_bwd(op, gout, *dims), None, None, None, None, None
 
 
 def out_upsample(x, n_flow, n_diag, diag_bias, out=None):
     """x [B,C,h,w] (may be a channel slice) -> [B,C,2h,2w]; `out` may be a channel slice of a preallocated buffer (it is
     written in place and returned).  diag_bias is a constant: no gradient."""
-    return OutUpsampleFunction.apply(out, x, n_flow, n_diag, diag_bias)
+    return ChannelUpsampleFunction.apply(out, x, 'out_upsample', 2, n_flow, n_diag, diag_bias)
 
 
 class OutTailFunction(torch.autograd.Function):
@@ -1510,11 +1524,11 @@ class OutTailFunction(torch.autograd.Function):
     def backward(ctx, g1, g0):
         B, C, h, w, n_flow = ctx.cfg
         if g0 is not None:
-            g10 = _out_up_bwd(g0, B, C, 2 * h, 2 * w, n_flow)
+            g10 = _chan_up_bwd('out_upsample', g0, B, C, 2 * h, 2 * w, 2, n_flow)
             g1 = g10 if g1 is None else g1 + g10
         if g1 is None:
             return None, None, None, None
-        return _out_up_bwd(g1, B, C, h, w, n_flow), None, None, None
+        return _chan_up_bwd('out_upsample', g1, B, C, h, w, 2, n_flow), None, None, None
 
 
 def out_tail(x, n_flow, n_diag, diag_bias):
@@ -1522,55 +1536,10 @@ def out_tail(x, n_flow, n_diag, diag_bias):
     return OutTailFunction.apply(x, n_flow, n_diag, diag_bias)
 
 
-class ProbUpsampleFunction(torch.autograd.Function):
-    """models/pwclite_prob.py:183-186,216-217 as one launch: out[:, c] = s_c * interpolate(x[:, c] + b_c, x factor, bilinear,
-    align_corners=True), s_c = factor for the first n_flow channels, b_c = diag_bias for the next n_diag (DESIGN.md section
-    27).  The adjoint is a gather (arflow_prob_up_bwd): reproducible in either mode, so the node does not sample the mode."""
-
-    @staticmethod
-    def forward(ctx, out, x, factor, n_flow, n_diag, diag_bias):
-        # (`out` first, as in OutUpsampleFunction)
-        _need_gpu(x, out)
-        if x.dim() != 4:
-            raise ValueError('prob_upsample expects a [B,C,h,w] tensor')
-        B, C, h, w = x.shape
-        factor, n_flow, n_diag = int(factor), int(n_flow), int(n_diag)
-        if factor not in (2, 4):
-            raise ValueError('prob_upsample: factor must be 2 or 4 (got %r)' % (factor,))
-        if n_flow < 0 or n_diag < 0 or n_flow + n_diag > C:
-            raise ValueError('prob_upsample: n_flow %d + n_diag %d exceed the %d channels' % (n_flow, n_diag, C))
-        x, xbs = _plane_view(x)
-        if out is None:
-            out = torch.empty(B, C, factor * h, factor * w, device=x.device, dtype=torch.float32)
-        else:
-            if tuple(out.shape) != (B, C, factor * h, factor * w):
-                raise ValueError('prob_upsample: out must be [B,C,%dh,%dw]' % (factor, factor))
-            view, _ = _plane_view(out)
-            if view is not out:
-                raise ValueError('prob_upsample: out must have contiguous planes (a channel slice of a contiguous buffer)')
-            ctx.mark_dirty(out)
-        _, obs = _plane_view(out)
-        with torch.cuda.device_of(x):
-            _call('arflow_prob_up_fwd', _p(x), xbs, _p(out), obs, B, C, h, w, factor, n_flow, n_diag, float(diag_bias),
-                  _stream(), key=(B, C, h, w, factor, 'fwd'))
-        ctx.cfg = (B, C, h, w, factor, n_flow)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        B, C, h, w, factor, n_flow = ctx.cfg
-        g, gbs = _plane_view(gout)
-        gin = torch.empty(B, C, h, w, device=g.device, dtype=torch.float32)
-        with torch.cuda.device_of(g):
-            _call('arflow_prob_up_bwd', _p(g), gbs, _p(gin), C * h * w, B, C, h, w, factor, n_flow, _stream(),
-                  key=(B, C, h, w, factor, 'bwd'))
-        return None, gin, None, None, None, None
-
-
 def prob_upsample(x, factor, n_flow, n_diag, diag_bias, out=None):
     """x [B,C,h,w] (may be a channel slice) -> [B,C,factor h,factor w], factor 2 or 4, align_corners=True; `out` may be a
     channel slice of a preallocated buffer (it is written in place and returned).  diag_bias is a constant: no gradient."""
-    return ProbUpsampleFunction.apply(out, x, factor, n_flow, n_diag, diag_bias)
+    return ChannelUpsampleFunction.apply(out, x, 'prob_upsample', factor, n_flow, n_diag, diag_bias)
 
 
 def interpolate_flow(flow, factor, align_corners):

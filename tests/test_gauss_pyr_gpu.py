@@ -1,5 +1,5 @@
 """GPU: the pyramid sampler (csrc/gauss_pyr.hip; arflow_amd.gauss_pyr.reparam_pyramid) and the align_corners=True upsample
-(csrc/out_up.hip; AF.prob_upsample) per element against the float64 restatements of tests/gauss_pyr_ref.py.
+(csrc/upsample.hip; AF.prob_upsample) per element against the float64 restatements of tests/gauss_pyr_ref.py.
 
 Bounds are derived, not tuned (u = 2^-24, the unit roundoff of fp32):
   z     |z - ref| <= u |z| + 8 u |std eps|.  z = mean + RN(expf(logvar / 2) eps): one rounding of the sum (u |z|); the product

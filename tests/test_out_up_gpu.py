@@ -1,4 +1,4 @@
-"""GPU: the output-upsample kernels (csrc/out_up.hip; AF.out_upsample, AF.out_tail) per pixel against the float64
+"""GPU: the output-upsample kernels (csrc/upsample.hip; AF.out_upsample, AF.out_tail) per pixel against the float64
 restatement of upsample_out (tests/prob_ref.py, pinned to the composed ATen path in tests/test_prob_model_cpu.py).
 
 Bounds are derived, not tuned (EPS = 2^-24, the unit roundoff of fp32):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""Bit fingerprints of the variational-family entry points and of the metric launchers that share their plumbing (DESIGN.md
-section 29): for every entry point, plane, layout and family parameter the inputs come from a CPU generator with a fixed
-seed, the raw C-ABI call runs once, and every output tensor, the float64 work and rows buffers included, is fingerprinted
+"""Bit fingerprints of the variational-family entry points, of the metric launchers that share their plumbing (DESIGN.md
+section 29) and of the bilinear upsamples (family out_up: every entry point of csrc/upsample.hip):
+for every entry point, plane, layout and family parameter the inputs come from a CPU generator with a fixed seed, the raw C-ABI call runs once, and every output tensor, the float64 work and rows buffers included, is fingerprinted
 by the first 12 hex digits of the sha256 of its bytes.  One line per entry point, parameters and plane:
 
     name parameters plane  tensor[shape] contig=<hash> slice=<hash> offset1=<hash>  tensor[shape] ...
@@ -267,21 +267,52 @@ def uncert(plane, layout):
         show('calib_hist', par, plane, layout, rows=crows)
 
 
+def signed_zeros(t):
+    """t with some entries +0.0 and some -0.0: the bias add of the output upsamples turns a -0.0 tap into +0.0 (also where the
+    bias is 0), the flow upsample has no such add and keeps it, so a moved `+ 0.f` shows in the hashes.  All values finite."""
+    v = t.view(-1)
+    v[::7] = 0.0
+    v[3::11] = -0.0
+    return t
+
+
 def out_up(plane, layout):
     h, w = plane
     C, n_flow, n_diag, bias = 4, 2, 1, 0.5
-    x = lay(randn(B, C, h, w), layout)
+    x = lay(signed_zeros(randn(B, C, h, w)), layout)
     o2 = out(layout, B, C, 2 * h, 2 * w)
     _call('arflow_out_up2_fwd', _p(x), x.stride(0), _p(o2), o2.stride(0), B, C, h, w, n_flow, n_diag, bias, _stream())
     show('out_up2_fwd', 'C=4', plane, layout, out=o2)
+    gx = out(layout, B, C, h, w)
+    g2 = lay(signed_zeros(randn(B, C, 2 * h, 2 * w)), layout)
+    _call('arflow_out_up2_bwd', _p(g2), g2.stride(0), _p(gx), gx.stride(0), B, C, h, w, n_flow, _stream())
+    show('out_up2_bwd', 'C=4', plane, layout, gcoarse=gx)
     for factor in (2, 4):
         o = out(layout, B, C, factor * h, factor * w)
         _call('arflow_prob_up_fwd', _p(x), x.stride(0), _p(o), o.stride(0), B, C, h, w, factor, n_flow, n_diag, bias, _stream())
         show('prob_up_fwd', 'factor=%d' % factor, plane, layout, out=o)
-    if layout != 'slice':  # the two outputs are dense
-        o1, o0 = out(layout, B, C, 2 * h, 2 * w), out(layout, B, C, 4 * h, 4 * w)
-        _call('arflow_out_tail_fwd', _p(x), x.stride(0), _p(o1), _p(o0), B, C, h, w, n_flow, n_diag, bias, _stream())
-        show('out_tail_fwd', 'C=4', plane, layout, out1=o1, out0=o0)
+        gx, gf = out(layout, B, C, h, w), lay(signed_zeros(randn(B, C, factor * h, factor * w)), layout)
+        _call('arflow_prob_up_bwd', _p(gf), gf.stride(0), _p(gx), gx.stride(0), B, C, h, w, factor, n_flow, _stream())
+        show('prob_up_bwd', 'factor=%d' % factor, plane, layout, gcoarse=gx)
+    if layout == 'slice':
+        return  # the remaining entry points take dense tensors: no batch stride to vary
+    o1, o0 = out(layout, B, C, 2 * h, 2 * w), out(layout, B, C, 4 * h, 4 * w)
+    _call('arflow_out_tail_fwd', _p(x), x.stride(0), _p(o1), _p(o0), B, C, h, w, n_flow, n_diag, bias, _stream())
+    show('out_tail_fwd', 'C=4', plane, layout, out1=o1, out0=o0)
+    flow = lay(signed_zeros(randn(B, 2, h, w)), layout)
+    for factor in (2, 4):
+        for align in (0, 1):
+            par = 'factor=%d,align=%d' % (factor, align)
+            o = out(layout, B, 2, factor * h, factor * w)
+            _call('arflow_flow_up_fwd', _p(flow), _p(o), B, h, w, factor, align, _stream())
+            show('flow_up_fwd', par, plane, layout, out=o)
+            gx, gf = out(layout, B, 2, h, w), lay(signed_zeros(randn(B, 2, factor * h, factor * w)), layout)
+            _call('arflow_flow_up_bwd', _p(gf), _p(gx), B, h, w, factor, align, _stream())
+            show('flow_up_bwd', par, plane, layout, gcoarse=gx)
+    for align in (0, 1):  # the level's x2 adjoint: its fine plane is twice the tool's plane
+        gx, gf = out(layout, B, 2, h, w), lay(signed_zeros(randn(B, 2, 2 * h, 2 * w)), layout)
+        _call('arflow_up2_bwd', _p(gf), _p(gx), B, 2 * h, 2 * w, align, _stream())
+        show('up2_bwd', 'align=%d' % align, plane, layout, gcoarse=gx)
 
 
 FAMILIES = dict(lowrank=lowrank, mixture=mixture, band=band, pyramid=pyramid, mse=mse, flow_eval=flow_eval, uncert=uncert,

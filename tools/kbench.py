@@ -360,7 +360,8 @@ def out_up_bench(dev, g, B2=8, launches=30, repeats=5):
     ATen's autograd of that), at the workload's own shapes with 2B = 8: C = 4 at the 12x20, 24x40 and 48x80 inputs, and the
     tail (two steps) at 34 x 96 x 160.  The two versions alternate, `repeats` windows of `launches` calls each: median and
     (min .. max).  Bytes are algorithmic: every input element read once, every output element written once (backward: the
-    fine gradients read once, the coarse one written once); the share is of the HBM3E spec peak, 8 TB/s."""
+    fine gradients read once, the coarse one written once); the share is of the HBM3E spec peak, 8 TB/s.  Then, the kernels
+    alone, the other entry points of csrc/upsample.hip: prob_upsample, flow_upsample and the raw arflow_up2_bwd."""
     import math
     import statistics
     import torch.nn.functional as F
@@ -435,6 +436,56 @@ def out_up_bench(dev, g, B2=8, launches=30, repeats=5):
     # forward: x read, out1 and out0 written; backward: g0 and g1 read, gx written (the level-1 gradient in between is
     # the composed algorithm's own traffic, not counted)
     report('tail %s' % [B2, C, h, w], res, {'fwd': 21 * n, 'bwd': 21 * n})
+
+    # the rest of the upsample family, the kernels alone: prob_upsample at PWCLiteProb's finest level,
+    # flow_upsample at [16, 2, 48, 80] and the raw x2 adjoint of the level backward at its own fine sizes
+    def solo(tag, make, x, go):
+        y = make(x)
+
+        def fwd():
+            with torch.no_grad():
+                make(x)
+        res = spread({'fwd': fwd, 'bwd': lambda: torch.autograd.grad(y, x, go, retain_graph=True)})
+        for what, (med, lo, hi) in res.items():
+            print('out_up %-34s %s  fused %8.1f us (%.1f .. %.1f)' % (tag, what, med, lo, hi), flush=True)
+
+    for f, C, nf, nd, h, w in ((4, 4, 2, 2, 96, 160), (2, 2, 0, 2, 48, 80)):
+        x = torch.randn(16, C, h, w, device=dev, generator=g).requires_grad_(True)
+        go = torch.randn(16, C, f * h, f * w, device=dev, generator=g)
+        solo('prob_upsample x%d %s' % (f, [16, C, h, w]), lambda t: AF.prob_upsample(t, f, nf, nd, 2 * math.log(f)), x, go)
+    for f in (2, 4):
+        x = torch.randn(16, 2, 48, 80, device=dev, generator=g).requires_grad_(True)
+        go = torch.randn(16, 2, f * 48, f * 80, device=dev, generator=g)
+        solo('flow_upsample x%d %s' % (f, [16, 2, 48, 80]), lambda t: AF.flow_upsample(t, f, True), x, go)
+    from arflow_amd import _lib
+    lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+    for H, W in ((96, 160), (12, 20)):
+        gf = torch.randn(16, 2, H, W, device=dev, generator=g)
+        gc = torch.empty(16, 2, H // 2, W // 2, device=dev)
+        res = spread({'bwd': lambda: lib.arflow_up2_bwd(p(gf), p(gc), 16, H, W, 1, st)})
+        print('out_up %-34s bwd  fused %8.1f us (%.1f .. %.1f)' % ('arflow_up2_bwd %s' % [16, 2, H, W], *res['bwd']), flush=True)
+    # the nodes above are host-bound (tens of us of autograd around a launch of a few): the same entry points as bare C-ABI
+    # launches back to back, which is what resolves a change to a kernel
+    def raw(tag, C, h, w, f, fwd, bwd):
+        a, b = torch.randn(16, C, h, w, device=dev, generator=g), torch.randn(16, C, f * h, f * w, device=dev, generator=g)
+        assert fwd(p(a), p(b), C, h, w) == 0 and bwd(p(b), p(a), C, h, w) == 0
+        res = spread({'fwd': lambda: fwd(p(a), p(b), C, h, w), 'bwd': lambda: bwd(p(b), p(a), C, h, w)})
+        for what, (med, lo, hi) in res.items():
+            print('out_up %-34s %s  launch %7.1f us (%.1f .. %.1f)' % ('%s %s' % (tag, [16, C, h, w]), what, med, lo, hi), flush=True)
+
+    for C, h, w in ((4, 48, 80), (34, 96, 160)):  # (the second: long enough to show the kernel, not the launch rate)
+        raw('arflow_out_up2', C, h, w, 2,
+            lambda a, b, C, h, w: lib.arflow_out_up2_fwd(a, C * h * w, b, 4 * C * h * w, 16, C, h, w, 2, 2, bias, st),
+            lambda b, a, C, h, w: lib.arflow_out_up2_bwd(b, 4 * C * h * w, a, C * h * w, 16, C, h, w, 2, st))
+    for f, C, h, w in ((4, 4, 96, 160), (2, 2, 48, 80)):
+        raw('arflow_prob_up x%d' % f, C, h, w, f,
+            lambda a, b, C, h, w: lib.arflow_prob_up_fwd(a, C * h * w, b, f * f * C * h * w, 16, C, h, w, f, 2, C - 2, bias, st),
+            lambda b, a, C, h, w: lib.arflow_prob_up_bwd(b, f * f * C * h * w, a, C * h * w, 16, C, h, w, f, 2, st))
+    for f in (2, 4):
+        for ac in (0, 1):
+            raw('arflow_flow_up x%d align %d' % (f, ac), 2, 48, 80, f,
+                lambda a, b, C, h, w: lib.arflow_flow_up_fwd(a, b, 16, h, w, f, ac, st),
+                lambda b, a, C, h, w: lib.arflow_flow_up_bwd(b, a, 16, h, w, f, ac, st))
 
 
 def gauss_pyr_bench(dev, g, B=8, H=384, W=640, launches=30, repeats=5):
@@ -1138,7 +1189,7 @@ def main():
         mixture_bench(dev, g)
     if want('band'):  # the fused sparse-covariance sampler (csrc/band.hip) against the reference's formulation in torch ops
         band_bench(dev, g)
-    if want('out_up'):  # the probabilistic model's output upsample (csrc/out_up.hip) against the composed ATen path
+    if want('out_up'):  # the probabilistic model's output upsample (csrc/upsample.hip) against the composed ATen path, and the rest of the upsample family alone
         out_up_bench(dev, g)
     if want('gauss_pyr'):  # the pyramid sampler node and one ElboLoss step (csrc/gauss_pyr.hip) against the torch formulation
         gauss_pyr_bench(dev, g)
