@@ -77,6 +77,10 @@ PROTOTYPES = {
     'arflow_splitconv_fwd_ex': [c_fp, c_l, c_fp, c_fp, c_l, c_fp, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_splitconv_wgrad_ws_bytes': [c_i, c_i, c_i, c_i, c_i],
     'arflow_splitconv_wgrad': [c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_phase_layout': [c_i, c_i, c_i, c_i, c_fp],
+    'arflow_phase_rows': [c_i, c_i, c_i, c_i, c_i],
+    'arflow_phase_move': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_phase_act_bwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_fp],
     'arflow_dense_cat_fwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_l, c_f, c_fp],
     'arflow_dense_gbias_rows': [c_i, c_l],
     'arflow_dense_grad_gather': [c_fp, c_i, c_fp, c_l, c_fp, c_fp, c_i, c_i, c_l, c_f, c_fp],

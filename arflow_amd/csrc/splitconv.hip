@@ -383,14 +383,7 @@ extern "C" int arflow_splitconv_fwd_ex(const float* x, long x_bstride, const voi
   AF_REQUIRE(act == 1 || bias == nullptr, ARFLOW_EPARAM);
   AF_REQUIRE(((uintptr_t)packed & 15) == 0, ARFLOW_EPARAM);
   const Ends ends{x, x_bstride, y, y_bstride, bias, act, negative_slope};
-  // pixel tile: 32 x 1 where the rows are long enough, else 16 x 2 or 8 x 4 (fewer columns of padding at W = 80, 40, 20)
-  const auto waste = [&](int pw) {
-    const int th = 8 * (32 / pw);
-    return (long)((W + pw - 1) / pw * pw) * ((H + th - 1) / th * th);
-  };
-  int PW = 32;
-  if (waste(16) < waste(PW)) PW = 16;
-  if (waste(8) < waste(PW)) PW = 8;
+  const int PW = pixel_tile_width(H, W);  // split_tiles.hpp
   const bf16x8* pk = (const bf16x8*)packed;
   hipStream_t st = (hipStream_t)stream;
   for (const TilePart& p : split_tiles(tiles32(K), MAX_KT)) {  // one launch per part: chunks over gridDim.y

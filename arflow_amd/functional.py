@@ -1116,6 +1116,172 @@ def dense_estimator(x, slope, params):
     return DenseEstimatorFunction.apply(x, slope, *params)
 
 
+# ------------------------------------------------------------------------------------------------
+# The dilated context layers as phase mosaics on the split-bf16 kernels (csrc/phase.hip)
+_DILATED_CHAIN = __import__('os').environ.get('ARFLOW_DILATED_CHAIN', '1') != '0'  # A/B switch for tools/ and tests: 0 = composed path
+DILATED_CHAIN_LAYERS = ((128, 128, 2), (128, 128, 4), (128, 96, 8), (96, 64, 16))  # (C, K, dilation) of ContextNetwork's layers 2..5
+# Which of the four weight gradients run arflow_splitconv_wgrad on the virtual tensors; the others are MIOpen's on NCHW copies
+# that the permutation passes write as a second destination.  Read off profiles/dilated_kbench.log by section 30's rule -- the
+# kernel's max below the min of MIOpen's solver plus its layout copies, at 16 x 96 x 160: d 2 (64 x 48 x 80) 496 (493 .. 498) us
+# against 642 (642 .. 656), 1.30x; d 4, 8 and 16 0.70x, 0.76x and 0.66x (many small images: short chunks, and the mosaics'
+# 1.2x .. 1.3x pixels), still behind with the two second destinations (20 .. 40 us each) on MIOpen's side.  ARFLOW_DILATED_WGRAD=0101 (one digit per layer) overrides it
+# for tools/ and tests.
+_DILATED_WGRAD_NATIVE = (True, False, False, False)
+
+
+def dilated_chain_enabled():
+    return _DILATED_CHAIN
+
+
+def _dilated_wgrad_native():
+    env = __import__('os').environ.get('ARFLOW_DILATED_WGRAD')
+    if env and len(env) == 4 and set(env) <= {'0', '1'}:
+        return tuple(c == '1' for c in env)
+    return _DILATED_WGRAD_NATIVE
+
+
+def phase_layout(N, H, W, d):
+    """(Nv, Hv, Wv, Pg, Qg) of layout d of an [N, *, H, W] tensor (csrc/phase_plan.hpp); raises where d > H or d > W."""
+    import ctypes
+    out = (ctypes.c_int * 5)()
+    _lib.check(_lib.load().arflow_phase_layout(int(N), int(H), int(W), int(d), ctypes.cast(out, ctypes.c_void_p)), 'arflow_phase_layout')
+    return tuple(out)
+
+
+def _phase_empty(N, C, H, W, d, device):
+    if d == 1:
+        return torch.empty(N, C, H, W, device=device, dtype=torch.float32)
+    Nv, Hv, Wv, _, _ = phase_layout(N, H, W, d)
+    return torch.empty(Nv, C, Hv, Wv, device=device, dtype=torch.float32)
+
+
+def _phase_check(t, N, H, W, d, what):
+    _need_gpu(t)
+    Nv, Hv, Wv, _, _ = phase_layout(N, H, W, d)
+    if t.dim() != 4 or (t.shape[0], t.shape[2], t.shape[3]) != (Nv, Hv, Wv) or not t.is_contiguous():
+        raise ValueError('%s must be a contiguous [%d,C,%d,%d] tensor: layout %d of [%d,C,%d,%d]' % (what, Nv, Hv, Wv, d, N, H, W))
+
+
+def phase_move(src, real, d_src, d_dst, d_dst2=0, out=None, out2=None):
+    """src, layout d_src of an [N,C,H,W] tensor with real = (N, H, W), rewritten in layout d_dst and, for d_dst2 != 0, in that
+    layout as well from the one read: (dst, dst2 or None).  Layout 1 is NCHW.  out / out2: tensors of the destinations' shapes
+    to write into (every element is stored); they must not share memory with src.  No autograd."""
+    N, H, W = (int(v) for v in real)
+    _phase_check(src, N, H, W, d_src, 'phase_move: src')
+    C = int(src.shape[1])
+    dst = _phase_empty(N, C, H, W, d_dst, src.device) if out is None else out
+    dst2 = (_phase_empty(N, C, H, W, d_dst2, src.device) if out2 is None else out2) if d_dst2 else None
+    for t, d in ((out, d_dst), (out2 if d_dst2 else None, d_dst2)):
+        if t is not None:
+            _phase_check(t, N, H, W, d, 'phase_move: out')
+            if t.shape[1] != C:
+                raise ValueError('phase_move: out has %d channels, src %d' % (t.shape[1], C))
+    with torch.cuda.device_of(src):
+        _call('arflow_phase_move', _p(src), _p(dst), _p(dst2), N, C, H, W, int(d_src), int(d_dst), int(d_dst2), _stream())
+    return dst, dst2
+
+
+def phase_act_bwd(gout, y, real, d_a, d_b, d_b2=0, slope=0.1, want_bias=True):
+    """gin = gout * (y > 0 ? 1 : slope) for gout and y in layout d_a, written in layout d_b (and d_b2), and the bias gradient
+    over real pixels: (gin, gin2 or None, gbias [C] or None).  No autograd."""
+    N, H, W = (int(v) for v in real)
+    _phase_check(gout, N, H, W, d_a, 'phase_act_bwd: gout')
+    _phase_check(y, N, H, W, d_a, 'phase_act_bwd: y')
+    if y.shape != gout.shape:
+        raise ValueError('phase_act_bwd: gout and y differ in shape')
+    C = int(gout.shape[1])
+    gin = _phase_empty(N, C, H, W, d_b, gout.device)
+    gin2 = _phase_empty(N, C, H, W, d_b2, gout.device) if d_b2 else None
+    rows = None
+    if want_bias:
+        n = _lib.load().arflow_phase_rows(N, H, W, int(d_b), int(d_b2))
+        if n <= 0:
+            _lib.check(n, 'arflow_phase_rows')
+        rows = torch.empty(n, C, device=gout.device, dtype=torch.float64)
+    with torch.cuda.device_of(gout):
+        _call('arflow_phase_act_bwd', _p(gout), _p(y), _p(gin), _p(gin2), _p(rows), N, C, H, W, int(d_a), int(d_b), int(d_b2),
+              float(slope), _stream())
+    return gin, gin2, (None if rows is None else rows.sum(0).float())
+
+
+def _dilated_wgrad_miopen(x, gy, w, d):
+    args = [1, 1], [d, d], [d, d], False, [0, 0], 1
+    return torch.ops.aten.convolution_backward(gy, x, w, None, *args, [False, True, False])[1]
+
+
+class DilatedChainFunction(torch.autograd.Function):
+    """ContextNetwork's layers 2..5 (models/pwclite.py:91-106) behind ONE autograd node:
+
+        for k in 2..5:  x = leaky_relu(conv2d(x, w_k, padding=d_k, dilation=d_k) + b_k),   d = 2, 4, 8, 16
+
+    Every convolution is the dilation-1 split-bf16 kernel on the layer's phase mosaic (layout d_k, csrc/phase_plan.hpp) with its
+    bias + LeakyReLU epilogue; arflow_phase_move carries the activation from the layout of one layer to the layout of the next
+    (five moves where the composed path has four bias / LeakyReLU passes), and backward arflow_phase_act_bwd does the same for
+    the gradient while it applies the LeakyReLU derivative and sums the bias gradient.  Saves each layer's input in its own
+    layout -- the previous layer's activation, element-aligned with the gradient that meets it -- and the NCHW output.  A weight
+    gradient that _DILATED_WGRAD_NATIVE leaves to MIOpen gets its NCHW operands from the second destination of those passes."""
+
+    @staticmethod
+    def forward(ctx, x, slope, *params):
+        if len(params) != 8:
+            raise ValueError('dilated_chain expects (w, b) of four layers')
+        _need_gpu(x, *params)
+        ws, bs = params[0::2], params[1::2]
+        shapes = tuple((int(w.shape[1]), int(w.shape[0]), d) for w, (_, _, d) in zip(ws, DILATED_CHAIN_LAYERS))
+        if shapes != DILATED_CHAIN_LAYERS or x.dim() != 4 or x.shape[1] != shapes[0][0]:
+            raise ValueError('dilated_chain: the layers are %s' % (DILATED_CHAIN_LAYERS,))
+        slope = float(slope)
+        ds = [d for _, _, d in DILATED_CHAIN_LAYERS]
+        native = _dilated_wgrad_native()
+        x = x.contiguous()
+        N, _, H, W = x.shape
+        real = (N, H, W)
+        a, _ = phase_move(x, real, 1, ds[0])
+        ins, plain = [], [x]
+        for k in range(4):
+            ins.append(a)
+            y = splitconv(a, ws[k], bias=bs[k], slope=slope)
+            if k == 3:
+                a, _ = phase_move(y, real, ds[k], 1)
+            else:
+                a, a_plain = phase_move(y, real, ds[k], ds[k + 1], 0 if native[k + 1] else 1)
+                plain.append(a_plain)
+        ctx.save_for_backward(a, *ins, *plain, *ws)
+        ctx.slope, ctx.real, ctx.native = slope, real, native
+        return a
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        saved = ctx.saved_tensors
+        out, ins, plain, ws = saved[0], saved[1:5], saved[5:9], saved[9:13]
+        need = ctx.needs_input_grad
+        ds = [d for _, _, d in DILATED_CHAIN_LAYERS]
+        grads = [None] * 10
+        g, lay, yk = gout.contiguous(), 1, out
+        for k in range(3, -1, -1):
+            want_dw, want_db = need[2 + 2 * k], need[3 + 2 * k]
+            native = ctx.native[k] or not want_dw
+            gin, gin_plain, grads[3 + 2 * k] = phase_act_bwd(g, yk, ctx.real, lay, ds[k], 0 if native else 1, ctx.slope, want_db)
+            if want_dw:
+                grads[2 + 2 * k] = splitconv_wgrad(ins[k], gin) if native else _dilated_wgrad_miopen(plain[k], gin_plain, ws[k], ds[k])
+            if k > 0 or need[0]:
+                g, lay, yk = splitconv(gin, ws[k], transpose_flip=True), ds[k], ins[k]
+        if need[0]:
+            grads[0] = phase_move(g, ctx.real, ds[0], 1)[0]
+        return tuple(grads)
+
+
+def dilated_chain(x, slope, params):
+    """ContextNetwork's layers 2..5 on x [N,128,H,W]; params = (w2, b2, ..., w5, b5)."""
+    return DilatedChainFunction.apply(x, slope, *params)
+
+
+def dilated_chain_takes(N, H, W):
+    """Whether ContextNetwork routes its dilated layers to the node: measured at 16 x 96 x 160 and not below."""
+    return _SPLITCONV and _DILATED_CHAIN and _size_floor(int(N), int(H), int(W), 96, 160)
+
+
 @_samples_mode
 class BiasLeakyReLUMomentsFunction(torch.autograd.Function):
     """bias_leaky_relu that also returns the partial moments (sum y, sum y^2) of its output as rows of 2 doubles

@@ -182,8 +182,27 @@ class ContextNetwork(nn.Module):
             conv(ch_in, 128, 3, 1, 1), conv(128, 128, 3, 1, 2), conv(128, 128, 3, 1, 4), conv(128, 96, 3, 1, 8),
             conv(96, 64, 3, 1, 16), conv(64, 32, 3, 1, 1), conv(32, ch_out, isReLU=False))
 
+    def native(self, x):
+        """Layers 2..5 -- the dilated ones -- as one autograd node on the split-bf16 kernels (AF.dilated_chain) under the rule
+        ConvAct._split_kind applies: a CUDA fp32 4-D input, the package's own bias_act, the reference's four layer shapes, at a
+        size AF.dilated_chain_takes routes (a twin that has swapped bias_act out, and every smaller map, keep the Sequential)."""
+        if not (bias_act is AF.bias_leaky_relu and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+            return False
+        convs = [layer[0] for layer in self.convs[1:5]]
+        kind = all(c.weight.dtype == torch.float32 and c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == c.dilation and
+                   c.dilation[0] == c.dilation[1] and c.groups == 1 and c.padding_mode == 'zeros' and c.bias is not None for c in convs)
+        shapes = tuple((c.in_channels, c.out_channels, c.dilation[0]) for c in convs)
+        slopes = {layer[1].negative_slope for layer in self.convs[1:5]}
+        return (kind and shapes == AF.DILATED_CHAIN_LAYERS and len(slopes) == 1 and
+                AF.dilated_chain_takes(x.shape[0], x.shape[2], x.shape[3]))
+
     def forward(self, x):
-        return self.convs(x)
+        if not self.native(x):
+            return self.convs(x)
+        x = self.convs[0](x)
+        params = [p for layer in self.convs[1:5] for p in (layer[0].weight, layer[0].bias)]
+        x = AF.dilated_chain(x, self.convs[1][1].negative_slope, params)
+        return self.convs[6](self.convs[5](x))
 
 
 def init_conv_weights(module, scheme):

@@ -336,6 +336,34 @@ long arflow_splitconv_wgrad_ws_bytes(int N, int C, int K, int H, int W);
 int arflow_splitconv_wgrad(const float* x, long x_bstride, const float* dy, long dy_bstride, float* dw, void* ws, int N, int C,
                            int K, int H, int W, arflow_stream_t stream);
 
+/* ---- phase-mosaic layouts: dilated 3x3 convolutions on the dilation-1 kernels above -------------
+ * A 3x3 convolution with dilation d and padding d is d*d independent dilation-1 / padding-1 convolutions on the phases
+ * x[:, :, p::d, q::d].  LAYOUT d of a tensor [N,C,H,W] (csrc/phase_plan.hpp) is the dense tensor [Nv,C,Hv,Wv] in which Pg x Qg
+ * phase images of Hs = ceil(H/d) x Ws = ceil(W/d) lie side by side with one row / column of zeros between neighbours:
+ * Hv = Pg (Hs + 1) - 1, Wv = Qg (Ws + 1) - 1, Nv = N d d / (Pg Qg); real (n, h, w) sits at sample
+ * (n (d/Pg) + (h%d)/Pg) (d/Qg) + (w%d)/Qg, row ((h%d)%Pg) (Hs+1) + h/d, column ((w%d)%Qg) (Ws+1) + w/d.  (Pg, Qg) is the pair of
+ * divisors of d that costs arflow_splitconv_fwd_ex's pixel tiles the least.  Layout 1 is NCHW.  conv2d(x, w, padding = d,
+ * dilation = d) in layout d IS arflow_splitconv_fwd_ex on (Nv, C, Hv, Wv) at the real positions, provided the separators and
+ * ragged tails (cells of phases that have a row or column less when d does not divide H or W) of the input hold zero; the
+ * outputs there are finite garbage.  The same holds for the data gradient and, with zeros there in dy, the weight gradient.
+ *
+ * arflow_phase_layout: the host-side plan, out = {Nv, Hv, Wv, Pg, Qg}; needs no GPU.
+ * arflow_phase_move: dst (layout d_dst) = src (layout d_src); dst2 != NULL: the same values in layout d_dst2 as well, from the
+ *   one read (dst2 == NULL needs d_dst2 == 0 and the reverse, else ARFLOW_EPARAM).  Every separator and tail element of a
+ *   destination is stored as zero; those of the source are never loaded.  Every element of every destination is stored.
+ * arflow_phase_act_bwd: gin (layout d_b; gin2 in d_b2 likewise) = gout * (y > 0 ? 1 : negative_slope), gout and y in layout d_a:
+ *   arflow_bias_act_bwd's arithmetic, zeros at separators and tails.  rows != NULL: [arflow_phase_rows(N, H, W, d_b, d_b2)][C]
+ *   float64 partial sums of gin over REAL pixels (by position), one row per workgroup, every row stored; the bias gradient is
+ *   their sum, which the caller takes in any fixed order.  No atomics: the same bits in either mode.
+ * ARFLOW_ESHAPE: a dimension < 1, d > H or d > W, rows too long for the workgroup's LDS (W beyond about 900), N or C > 65535, or a layout of more than INT_MAX elements --
+ * returned before anything is launched.  Sources and destinations must not overlap. */
+int arflow_phase_layout(int N, int H, int W, int d, int* nv_hv_wv_pg_qg);
+int arflow_phase_rows(int N, int H, int W, int d_dst, int d_dst2);
+int arflow_phase_move(const float* src, float* dst, float* dst2, int N, int C, int H, int W, int d_src, int d_dst, int d_dst2,
+                      arflow_stream_t stream);
+int arflow_phase_act_bwd(const float* gout, const float* y, float* gin, float* gin2, double* rows, int N, int C, int H, int W,
+                         int d_a, int d_b, int d_b2, float negative_slope, arflow_stream_t stream);
+
 /* ---- dense flow estimator: concatenating epilogue and gradient gather ---------------------------
  * FlowEstimatorDense (models/pwclite.py:48-66) runs five times x = cat([lrelu(conv(x) + bias), x], 1).
  *

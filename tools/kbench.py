@@ -1036,6 +1036,66 @@ def main():
                     print('splitconv_wgrad error %4d->%-4d at %dx%dx%d (%d terms): dw %6.2f / %6.2f u   (kernel / MIOpen, u = 2^-24)' % (
                         Cl, Kl, B2, h, w, B2 * h * w, e(dw), lib_e), flush=True)
                 del x, gy, ws
+    if want('dilated'):  # the context network's dilated layers as phase mosaics (csrc/phase.hip)
+        import statistics
+        from arflow_amd import functional as AF
+        _, h, w = levels[-1]
+        real = (B2, h, w)
+
+        def alternate(fns, rounds=5):  # {name: fn} -> {name: (median, min, max)} us; one window each per round, in alternation
+            t = {name: [] for name in fns}
+            for _ in range(rounds):
+                for name, fn in fns.items():
+                    t[name].append(timeit(fn, args.iters))
+                    MANIFEST[-1].update(name='dilated ' + name, shape=[], us=t[name][-1])
+            return {name: (statistics.median(v), min(v), max(v)) for name, v in t.items()}
+
+        fmt = lambda v: '%8.1f (%8.1f .. %8.1f)' % v
+        print('dilated: time in us as median (min .. max) of 5 x %d calls in alternation at %dx%dx%d; kernel = this tree on the virtual '
+              'tensors (forward and data gradient: pack + convolution with its epilogue), MIOpen = the ATen call with the layout copies '
+              'it launches; TF = fp32-equivalent TFLOP/s of the REAL convolution' % (args.iters, B2, h, w))
+        for Cl, Kl, d in AF.DILATED_CHAIN_LAYERS:
+            cargs = ([1, 1], [d, d], [d, d], False, [0, 0], 1)
+            x = 3.0 + torch.randn(B2, Cl, h, w, device=dev, generator=g)
+            gy = 3.0 + torch.randn(B2, Kl, h, w, device=dev, generator=g)
+            wt = torch.randn(Kl, Cl, 3, 3, device=dev, generator=g)
+            bias = torch.randn(Kl, device=dev, generator=g)
+            xv, gv = AF.phase_move(x, real, 1, d)[0], AF.phase_move(gy, real, 1, d)[0]
+            flop = 2.0 * B2 * h * w * Cl * Kl * 9
+            tag = '%3d->%-3d d %-2d %s' % (Cl, Kl, d, 'x'.join(map(str, xv.shape[0:1] + xv.shape[2:])))
+            for name, ours, theirs in (
+                    ('fwd  ', lambda: AF.splitconv(xv, wt, bias=bias, slope=0.1), lambda: torch.ops.aten.convolution(x, wt, None, *cargs)),
+                    ('dgrad', lambda: AF.splitconv(gv, wt, transpose_flip=True),
+                     lambda: torch.ops.aten.convolution_backward(gy, x, wt, None, *cargs, [True, False, False])),
+                    ('wgrad', lambda: AF.splitconv_wgrad(xv, gv),
+                     lambda: torch.ops.aten.convolution_backward(gy, x, wt, None, *cargs, [False, True, False]))):
+                r = alternate({'kernel': ours, 'MIOpen': theirs})
+                print('dilated %s %s kernel %s  MIOpen %s  %5.2fx  %6.1f TF  %s' % (
+                    name, tag, fmt(r['kernel']), fmt(r['MIOpen']), r['MIOpen'][0] / r['kernel'][0], flop / r['kernel'][0] / 1e6,
+                    'kernel max < MIOpen min' if r['kernel'][2] < r['MIOpen'][1] else 'ranges touch'), flush=True)
+            del x, gy, xv, gv
+        # the permutation passes, next to the passes they replace; GB/s = one read (two for act_bwd) + the writes of the REAL map
+        chain = [(128, 1, 2), (128, 2, 4), (128, 4, 8), (96, 8, 16), (64, 16, 1)]
+        for Cl, da, db in chain:
+            t = torch.randn(B2, Cl, h, w, device=dev, generator=g)
+            t2 = torch.randn(B2, Cl, h, w, device=dev, generator=g)
+            sv, yv = AF.phase_move(t, real, 1, da)[0], AF.phase_move(t2, real, 1, da)[0]
+            o1, o2 = AF._phase_empty(B2, Cl, h, w, db, dev), AF._phase_empty(B2, Cl, h, w, 1, dev)
+            bvec = torch.randn(Cl, device=dev, generator=g)
+            gb = torch.empty(Cl, device=dev)
+            nbytes = 4.0 * B2 * Cl * h * w
+            r = alternate({
+                'move': lambda: AF.phase_move(sv, real, da, db, out=o1),
+                'move+2nd': lambda: AF.phase_move(sv, real, da, db, 1, out=o1, out2=o2),
+                'bias_act_fwd': lambda: lib.arflow_bias_act_fwd(p(t), p(bvec), p(t), B2, Cl, h * w, 0.1, s),
+                'act_bwd': lambda: AF.phase_act_bwd(sv, yv, real, da, db, 0, 0.1),
+                'act_bwd+2nd': lambda: AF.phase_act_bwd(sv, yv, real, da, db, 1, 0.1),
+                'bias_act_bwd': lambda: lib.arflow_bias_act_bwd(p(t), p(t2), p(o2), p(gb), B2, Cl, h * w, 0.1, s)})
+            passes = {'move': 2, 'move+2nd': 3, 'bias_act_fwd': 2, 'act_bwd': 3, 'act_bwd+2nd': 4, 'bias_act_bwd': 3}
+            for name, v in r.items():
+                print('dilated pass %3d ch  %2d -> %-2d  %-13s %s us  %7.1f GB/s  %4.1f%% of HBM peak' % (
+                    Cl, da, db, name, fmt(v), passes[name] * nbytes / v[0] / 1e3, 100 * passes[name] * nbytes / v[0] / 1e3 / HBM_PEAK_GBS), flush=True)
+            del t, t2, sv, yv, o1, o2
     if want('dense'):  # the dense estimator's concatenating epilogue and gradient gather (csrc/dense.hip), five layers x four levels
         import ctypes
         from arflow_amd.functional import _DenseSrc
