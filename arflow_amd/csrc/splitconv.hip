@@ -15,15 +15,19 @@
 // 16-byte slots: odd, so the 16 lanes ds_read_b128 serves together fall on 16 different slots of the 256-byte bank row.
 //
 // A workgroup of 4 waves owns 8 pixel tiles (32 pixels each: PW columns x 32 / PW rows, stacked vertically) and KT <= 2
-// tiles of 32 output channels; a wave holds 2 pixel tiles x KT channel tiles, twice: the accumulators of the current block
-// and the running totals, up to 128 registers.  Two workgroups share a CU (2 x 70 KB of LDS, 256 registers per lane): one
-// stages its next block while the other multiplies.  More than 64 output channels go over gridDim.y in chunks of equal
-// size (+-1 tile: no tile of zeros is multiplied).
+// tiles of 32 output channels.  A wave holds ONE channel tile x 2 KT pixel tiles -- at KT = 1 two of the eight pixel tiles,
+// at KT = 2 four of them for one of the two channel tiles (a weight fragment is then fetched by two
+// waves of the workgroup instead of four, a pixel fragment by two instead of one, and LDS has the bandwidth to spare) --
+// twice: the accumulators of the current block and the running totals, up to 128 registers.  Two workgroups share a CU
+// (2 x 70 KB of LDS, 256 registers per lane): one stages its next block while the other multiplies.  More than 64 output
+// channels go over gridDim.y in chunks of equal size (+-1 tile: no tile of zeros is multiplied).
 //
-// Operand fetch is software-pipelined: the weight and pixel fragments of a unit -- one (tap, step) in
+// Operand fetch is software-pipelined (DESIGN.md sections 32, 40): the weight fragments of a unit -- one (tap, step) in
 // pass 0, three of them in pass 1 -- are requested while the unit before it multiplies, into the second of two register
-// buffers (2 x 24 registers each at KT = 2: 251..253 in all), through both passes and across the block boundary; the
-// staging loads of three items go out together.  Which products are formed, and in which order, is untouched.
+// buffers of three fragments; the pixel fragments come a unit ahead as well, in halves of two pixel tiles x three planes,
+// into a ring of KT + 1 buffers of six fragments (24 + 72 registers at KT = 2: 242..251 in all), through both passes and
+// across the block boundary; the staging loads of three items go out together.  Which products are formed, and in which
+// order, is untouched.
 //
 // Summation order is fixed.  Within a block of 32 input channels one MFMA accumulator chain starts from zero and takes, over
 // taps row-major and 16-channel steps ascending, FIRST the five small products of every step -- (w2,x0) (w1,x1) (w0,x2)
@@ -96,52 +100,62 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
   const int t = blockIdx.x;
   const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, n = t / (tiles_x * tiles_y);
   const int h0 = ty * G::TH, w0 = tx * PW;
-  const int kt0 = kt_first + blockIdx.y * KT;
+  // The wave's tile: ONE channel tile x PT pixel tiles.  KT = 1: the four waves take two pixel tiles each.  KT = 2: waves
+  // 0, 1 take the workgroup's first channel tile and waves 2, 3 its second, pixel tiles 0..3 (waves 0, 2) or 4..7 (waves
+  // 1, 3) -- a weight fragment is fetched by two waves of the workgroup, not by all four.
+  constexpr int PT = 2 * KT;
+  constexpr int NH = KT;      // half-units (two pixel tiles each) of a pass-0 unit
+  constexpr int NB = KT + 1;  // pixel-fragment buffers: a ring, one unit ahead
+  const int ktw = kt_first + blockIdx.y * KT + (KT == 2 ? wv >> 1 : 0);
+  const int pt0 = KT == 2 ? 4 * (wv & 1) : 2 * wv;
   const long plane_frags = (long)9 * nkt * ncs * 64;  // fragments (of 8 bf16) per plane
 
-  f32x16 tot[2][KT];  // running totals; every block of 32 input channels is summed in fresh accumulators first
+  f32x16 tot[PT];  // running totals; every block of 32 input channels is summed in fresh accumulators first
   acc_zero(tot);
 
-  // the lane's pixel in each of the wave's two pixel tiles: halo-tile byte offset of tap (0, 0), plus its k half
-  int pbase[2], prow[2], pcol;
-  pcol = r % PW;
-#pragma unroll
-  for (int pt = 0; pt < 2; ++pt) {
-    prow[pt] = (2 * wv + pt) * G::PR + r / PW;
-    pbase[pt] = (prow[pt] * G::HW + pcol) * PIX_BYTES + hh * 16;
-  }
+  // the lane's pixel in the first of the wave's pixel tiles: halo-tile byte offset of tap (0, 0), plus its k half
+  // (tile pt: pbase + pt * PT_BYTES, a constant apart, so that every LDS address is this one register plus a uniform offset)
+  constexpr int PT_BYTES = G::PR * G::HW * PIX_BYTES;
+  const int pcol = r % PW, prow0 = pt0 * G::PR + r / PW;
+  const int pbase = (prow0 * G::HW + pcol) * PIX_BYTES + hh * 16;
   const float* xn = x + (long)n * x_bs;  // the sample's planes are dense; the batch stride is the caller's
   const long HWl = (long)H * W;
   const unsigned HWu = (unsigned)(H * W);
 
   // Weight fragments travel one unit ahead of the MFMAs that take them: two register buffers of three
-  // fragments per channel tile; while a unit multiplies out of one, the next unit's loads fill the other, and the wait before
+  // fragments; while a unit multiplies out of one, the next unit's loads fill the other, and the wait before
   // the MFMAs retires the older loads only.  The chain runs through both passes and from block to block: the first unit of a
   // block does not depend on LDS and is in flight across the barriers and the staging.  The loads stand between two
   // scheduling barriers that only plain ALU work may cross, so the compiler neither sinks them to their use
-  // nor hoists later ones until registers spill.
+  // nor hoists later ones until registers spill.  An address is a wave-uniform pointer (the fragment: scalar arithmetic)
+  // plus the lane's 32-bit byte offset wl: no vector add per load.
   constexpr int SCHED_FREE = 0x2 | 0x4;  // VALU, SALU
   const long tap_frags = (long)nkt * ncs * 64;  // fragments from a tap to the next
-  bf16x8 wq[2][KT][3];
-  const auto wload = [&](bf16x8 (&d)[KT][3], const bf16x8* base, long o0, long o1, long o2) __attribute__((always_inline)) {
+  // (wl is re-defined by an empty asm at the head of every trip: were its zero-extension hoisted out of the loads' basic
+  // block, instruction selection would not see it and the add would be 64-bit VALU again)
+  unsigned wl = lane * (unsigned)sizeof(bf16x8);
+  const auto pin_wl = [&]() __attribute__((always_inline)) { asm volatile("" : "+v"(wl)); };
+  bf16x8 wq[2][3];
+  const auto wload = [&](bf16x8 (&d)[3], const bf16x8* base, long o0, long o1, long o2) __attribute__((always_inline)) {
+    const auto frag = [&](long o) { return *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(base + o) + wl); };
+    d[0] = frag(o0), d[1] = frag(o1), d[2] = frag(o2);
+  };
+  const bf16x8* wblk = packed + (long)ktw * ncs * 64;  // the block's (tap 0, tile ktw, step 0) fragment of plane 0: lane 0's
+  wload(wq[0], wblk, 0, plane_frags, 2 * plane_frags);
+  // The pixel fragments likewise, out of LDS: byte offsets from the lane's pixel of tap (0, 0).  A buffer holds two pixel
+  // tiles x three fragments (slot 3 ptl + i): half s of a unit is the wave's pixel tiles 2 s and 2 s + 1.  At KT = 2 pass 1
+  // uses four slots of a buffer, one fragment of each of the four tiles.
+  bf16x8 bq[NB][6];
+  const auto bload = [&](bf16x8 (&d)[6], int s, int o0, int o1, int o2) __attribute__((always_inline)) {
 #pragma unroll
-    for (int kt = 0; kt < KT; ++kt) {
-      d[kt][0] = base[o0 + (long)kt * ncs * 64];
-      d[kt][1] = base[o1 + (long)kt * ncs * 64];
-      d[kt][2] = base[o2 + (long)kt * ncs * 64];
+    for (int ptl = 0; ptl < 2; ++ptl) {
+      d[3 * ptl + 0] = *reinterpret_cast<const bf16x8*>(lds + pbase + ((2 * s + ptl) * PT_BYTES + o0));
+      d[3 * ptl + 1] = *reinterpret_cast<const bf16x8*>(lds + pbase + ((2 * s + ptl) * PT_BYTES + o1));
+      d[3 * ptl + 2] = *reinterpret_cast<const bf16x8*>(lds + pbase + ((2 * s + ptl) * PT_BYTES + o2));
     }
   };
-  const bf16x8* wblk = packed + (long)kt0 * ncs * 64 + lane;  // the block's (tap 0, tile kt0, step 0) fragment of plane 0
-  wload(wq[0], wblk, 0, plane_frags, 2 * plane_frags);
-  // The pixel fragments likewise, out of LDS: byte offsets from the lane's pixel of tap (0, 0).
-  bf16x8 bq[2][2][3];
-  const auto bload = [&](bf16x8 (&d)[2][3], int o0, int o1, int o2) __attribute__((always_inline)) {
-#pragma unroll
-    for (int pt = 0; pt < 2; ++pt) {
-      d[pt][0] = *reinterpret_cast<const bf16x8*>(lds + pbase[pt] + o0);
-      d[pt][1] = *reinterpret_cast<const bf16x8*>(lds + pbase[pt] + o1);
-      d[pt][2] = *reinterpret_cast<const bf16x8*>(lds + pbase[pt] + o2);
-    }
+  const auto mfma = [](const bf16x8& a, const bf16x8& b, const f32x16& c) __attribute__((always_inline)) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
   };
 
   for (int cb = 0; cb < C; cb += CB) {
@@ -186,132 +200,173 @@ __global__ __launch_bounds__(NT, 2) void splitconv_kernel(const float* __restric
       }
     }
     __syncthreads();
-    // ---- multiply: two passes of 9 taps x 2 k-steps; weight fragments from L2, pixel fragments from LDS, 12 KT MFMAs per step
-    f32x16 acc[2][KT];
+    // ---- multiply: two passes of 9 taps x 2 k-steps; weight fragments from L2, pixel fragments from LDS, 6 PT MFMAs per step
+    f32x16 acc[PT];
     acc_zero(acc);
     // The block after this one, whose first unit the last trip requests.  After the last block there is none: the pointer is
     // CLAMPED to this block, whose first unit is loaded once more and dropped -- no address outside `packed` is formed.
     const bf16x8* const wnext = cb + CB < C ? wblk + 2 * 64 : wblk;
-    bload(bq[0], 0, PLANE_BYTES, 2 * PLANE_BYTES);  // the first unit's pixel fragments: the one LDS fetch that nothing covers
+    // the first unit's pixel fragments: the one LDS fetch that nothing covers
+#pragma unroll
+    for (int s = 0; s < NH; ++s) bload(bq[s], s, 0, PLANE_BYTES, 2 * PLANE_BYTES);
     // pass 0: the five small products of every tap and step, while the accumulator is small (their roundings are 2^-8 of the
-    // block's sum).  A unit is one (tap, step): three planes of weights per channel tile and of pixels per pixel tile, 10 KT
-    // MFMAs.  The next unit's weights are requested before the unit's first MFMAs, its pixels behind them.
+    // block's sum).  A unit is one (tap, step): three planes of weights, and of pixels per pixel tile, 5 PT MFMAs, taken in
+    // NH halves of two pixel tiles.  The next unit's weights are requested before the unit's first MFMAs, and behind the
+    // first MFMAs of every half the same half of the next unit: NH halves ahead, into the ring's free buffer.
 #pragma unroll 1  // a row of taps per trip: unrolled further, the scheduler hoists pass 1's loads until registers spill
     for (int trow = 0; trow < 3; ++trow) {
       const long wrow = 3 * trow * tap_frags;
+      pin_wl();
       const int brow = trow * G::HW * PIX_BYTES;
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
         constexpr int PA[5] = {2, 1, 0, 1, 0}, PB[5] = {0, 1, 2, 0, 1};  // (weight plane, input plane), smallest product first
-        const bool more = trow < 2;  // j == 5: the next row's first unit, else pass 1's first three (plane 0 of units 0..2)
-        __builtin_amdgcn_sched_barrier(SCHED_FREE);
-        if (j < 5) {
-          const long o = wrow + ((j + 1) >> 1) * tap_frags + ((j + 1) & 1) * 64;
-          wload(wq[(j + 1) & 1], wblk, o, o + plane_frags, o + 2 * plane_frags);
-        } else {
-          const long o = wrow + 3 * tap_frags;
-          wload(wq[0], wblk, more ? o : 0, more ? o + plane_frags : 64, more ? o + 2 * plane_frags : tap_frags);
-        }
-        __builtin_amdgcn_sched_barrier(SCHED_FREE);
+        const bool more = trow < 2;  // j == 5: the next row's first unit, else pass 1's first fragments
 #pragma unroll
-        for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-          for (int kt = 0; kt < KT; ++kt)
-            acc[pt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[j & 1][kt][PA[0]], bq[j & 1][pt][PB[0]], acc[pt][kt], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(SCHED_FREE);
-        if (j < 5) {
-          const int o = brow + ((j + 1) >> 1) * PIX_BYTES + ((j + 1) & 1) * 32;
-          bload(bq[(j + 1) & 1], o, o + PLANE_BYTES, o + 2 * PLANE_BYTES);
-        } else {
-          const int o = brow + G::HW * PIX_BYTES;
-          bload(bq[0], more ? o : 0, more ? o + PLANE_BYTES : 32, more ? o + 2 * PLANE_BYTES : PIX_BYTES);
-        }
-        __builtin_amdgcn_sched_barrier(SCHED_FREE);
-#pragma unroll
-        for (int q = 1; q < 5; ++q)
-#pragma unroll
-          for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt)
-              acc[pt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[j & 1][kt][PA[q]], bq[j & 1][pt][PB[q]], acc[pt][kt], 0, 0, 0);
-      }
-    }
-    // pass 1: the (w0, x0) products on top -- 18 roundings at the block's magnitude instead of 108.  A unit is 2 KT MFMAs,
-    // shorter than a load takes: the units are requested three at a time (a buffer holds plane 0 of three consecutive units),
-    // so that three to six are in flight.
-#pragma unroll 1
-    for (int trow = 0; trow < 3; ++trow) {
-      const long wrow = 3 * trow * tap_frags;
-      const int brow = trow * G::HW * PIX_BYTES;
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        const bool more = trow < 2;  // g == 1: units 0..2 of the next row, else the next block's first unit of pass 0 (wnext)
-        __builtin_amdgcn_sched_barrier(SCHED_FREE);
-        if (g == 0) {  // units 3..5 of this row: (tap 1, step 1), (2, 0), (2, 1)
-          wload(wq[1], wblk, wrow + tap_frags + 64, wrow + 2 * tap_frags, wrow + 2 * tap_frags + 64);
-        } else {
-          const long o = wrow + 3 * tap_frags;
-          wload(wq[0], more ? wblk : wnext, more ? o : 0, more ? o + 64 : plane_frags, more ? o + tap_frags : 2 * plane_frags);
-        }
-        __builtin_amdgcn_sched_barrier(SCHED_FREE);
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-#pragma unroll
-          for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt)
-              acc[pt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[g][kt][p], bq[g][pt][p], acc[pt][kt], 0, 0, 0);
-          if (p == 0) {
-            __builtin_amdgcn_sched_barrier(SCHED_FREE);
-            if (g == 0) {
-              bload(bq[1], brow + PIX_BYTES + 32, brow + 2 * PIX_BYTES, brow + 2 * PIX_BYTES + 32);
-            } else {  // after the last row the next block is not staged yet: this row's fragments are read again and dropped
-              const int o = more ? brow + G::HW * PIX_BYTES : brow;
-              bload(bq[0], o, o + 32, o + PIX_BYTES);
+        for (int s = 0; s < NH; ++s) {
+          bf16x8(&cur)[6] = bq[(NH * j + s) % NB];
+          bf16x8(&nxt)[6] = bq[(NH * j + s + NH) % NB];  // 6 NH halves per trip, a multiple of NB: the indices are static
+          __builtin_amdgcn_sched_barrier(SCHED_FREE);
+          if (s == 0) {
+            if (j < 5) {
+              const long o = wrow + ((j + 1) >> 1) * tap_frags + ((j + 1) & 1) * 64;
+              wload(wq[(j + 1) & 1], wblk, o, o + plane_frags, o + 2 * plane_frags);
+            } else {  // pass 1 starts with plane 0 of units 0..2
+              const long o = wrow + 3 * tap_frags;
+              wload(wq[0], wblk, more ? o : 0, more ? o + plane_frags : 64, more ? o + 2 * plane_frags : tap_frags);
             }
             __builtin_amdgcn_sched_barrier(SCHED_FREE);
           }
+#pragma unroll
+          for (int ptl = 0; ptl < 2; ++ptl)
+            acc[2 * s + ptl] = mfma(wq[j & 1][PA[0]], cur[3 * ptl + PB[0]], acc[2 * s + ptl]);
+          __builtin_amdgcn_sched_barrier(SCHED_FREE);
+          if (j < 5) {
+            const int o = brow + ((j + 1) >> 1) * PIX_BYTES + ((j + 1) & 1) * 32;
+            bload(nxt, s, o, o + PLANE_BYTES, o + 2 * PLANE_BYTES);
+          } else if constexpr (KT == 1) {  // pass 1's first group: plane 0 of units 0..2
+            const int o = brow + G::HW * PIX_BYTES;
+            bload(nxt, 0, more ? o : 0, more ? o + PLANE_BYTES : 32, more ? o + 2 * PLANE_BYTES : PIX_BYTES);
+          } else {  // pass 1's unit s: plane 0 of (tap 0, step s) for the four pixel tiles; slots 4 and 5 are not used there
+            const int o = brow + G::HW * PIX_BYTES;
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+              nxt[i] = *reinterpret_cast<const bf16x8*>(
+                  lds + pbase + (more ? (2 * s + i / 3) * PT_BYTES + o + (i % 3) * PLANE_BYTES : (i & 3) * PT_BYTES + 32 * s));
+          }
+          __builtin_amdgcn_sched_barrier(SCHED_FREE);
+#pragma unroll
+          for (int q = 1; q < 5; ++q)
+#pragma unroll
+            for (int ptl = 0; ptl < 2; ++ptl)
+              acc[2 * s + ptl] = mfma(wq[j & 1][PA[q]], cur[3 * ptl + PB[q]], acc[2 * s + ptl]);
+        }
+      }
+    }
+    // pass 1: the (w0, x0) products on top -- 18 roundings at the block's magnitude instead of 108.  A unit is PT MFMAs,
+    // shorter than a load takes.  The weights are requested three units at a time (a buffer holds plane 0 of three
+    // consecutive units), so that three to six are in flight.
+    if constexpr (KT == 1) {  // the pixel fragments likewise: a buffer holds three units of both tiles
+#pragma unroll 1
+      for (int trow = 0; trow < 3; ++trow) {
+        const long wrow = 3 * trow * tap_frags;
+        pin_wl();
+        const int brow = trow * G::HW * PIX_BYTES;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          const bool more = trow < 2;  // g == 1: units 0..2 of the next row, else the next block's first unit of pass 0 (wnext)
+          __builtin_amdgcn_sched_barrier(SCHED_FREE);
+          if (g == 0) {  // units 3..5 of this row: (tap 1, step 1), (2, 0), (2, 1)
+            wload(wq[1], wblk, wrow + tap_frags + 64, wrow + 2 * tap_frags, wrow + 2 * tap_frags + 64);
+          } else {
+            const long o = wrow + 3 * tap_frags;
+            wload(wq[0], more ? wblk : wnext, more ? o : 0, more ? o + 64 : plane_frags, more ? o + tap_frags : 2 * plane_frags);
+          }
+          __builtin_amdgcn_sched_barrier(SCHED_FREE);
+#pragma unroll
+          for (int p = 0; p < 3; ++p) {
+#pragma unroll
+            for (int pt = 0; pt < 2; ++pt) acc[pt] = mfma(wq[g][p], bq[g][3 * pt + p], acc[pt]);
+            if (p == 0) {
+              __builtin_amdgcn_sched_barrier(SCHED_FREE);
+              if (g == 0) {
+                bload(bq[1], 0, brow + PIX_BYTES + 32, brow + 2 * PIX_BYTES, brow + 2 * PIX_BYTES + 32);
+              } else {  // after the last row the next block is not staged yet: this row's fragments are read again and dropped
+                const int o = more ? brow + G::HW * PIX_BYTES : brow;
+                bload(bq[0], 0, o, o + 32, o + PIX_BYTES);
+              }
+              __builtin_amdgcn_sched_barrier(SCHED_FREE);
+            }
+          }
+        }
+      }
+    } else {  // one unit's four pixel fragments per buffer (slots 0..3), two units ahead in the ring of three
+      const auto bload4 = [&](bf16x8 (&d)[6], int o) __attribute__((always_inline)) {
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt) d[pt] = *reinterpret_cast<const bf16x8*>(lds + pbase + (pt * PT_BYTES + o));
+      };
+#pragma unroll 1
+      for (int trow = 0; trow < 3; ++trow) {
+        const long wrow = 3 * trow * tap_frags;
+        pin_wl();
+        const int brow = trow * G::HW * PIX_BYTES;
+#pragma unroll
+        for (int u = 0; u < 6; ++u) {  // unit u = (tap u >> 1, step u & 1): weights wq[u / 3][u % 3], pixels bq[u % 3]
+          const bool more = trow < 2;  // u >= 3: units 0..2 of the next row, else the next block's first unit of pass 0 (wnext)
+          __builtin_amdgcn_sched_barrier(SCHED_FREE);
+          if (u == 0) {  // units 3..5 of this row: (tap 1, step 1), (2, 0), (2, 1)
+            wload(wq[1], wblk, wrow + tap_frags + 64, wrow + 2 * tap_frags, wrow + 2 * tap_frags + 64);
+            __builtin_amdgcn_sched_barrier(SCHED_FREE);
+          } else if (u == 3) {
+            const long o = wrow + 3 * tap_frags;
+            wload(wq[0], more ? wblk : wnext, more ? o : 0, more ? o + 64 : plane_frags, more ? o + tap_frags : 2 * plane_frags);
+            __builtin_amdgcn_sched_barrier(SCHED_FREE);
+          }
+          acc[0] = mfma(wq[u / 3][u % 3], bq[u % 3][0], acc[0]);
+          __builtin_amdgcn_sched_barrier(SCHED_FREE);
+          if (u < 4) {
+            bload4(bq[(u + 2) % 3], brow + ((u + 2) >> 1) * PIX_BYTES + ((u + 2) & 1) * 32);
+          } else {  // after the last row the next block is not staged yet: this row's fragments are read again and dropped
+            bload4(bq[(u + 2) % 3], (more ? brow + G::HW * PIX_BYTES : brow) + (u & 1) * 32);
+          }
+          __builtin_amdgcn_sched_barrier(SCHED_FREE);
+#pragma unroll
+          for (int pt = 1; pt < 4; ++pt) acc[pt] = mfma(wq[u / 3][u % 3], bq[u % 3][pt], acc[pt]);
         }
       }
     }
     wblk = wnext;
 #pragma unroll
-    for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) tot[pt][kt] = tot[pt][kt] + acc[pt][kt];
+    for (int pt = 0; pt < PT; ++pt) tot[pt] = tot[pt] + acc[pt];
   }
   // ---- store: accumulator register i of lane (r, hh) is output channel acc_channel(i, hh) of its tile, pixel r
   // act: the dense estimator's epilogue, bias_act_fwd_kernel's arithmetic (v += b; v > 0 ? v : v * slope), applied to the
-  // totals in registers under ONE uniform branch, the bias index clamped so that the lane's 16 KT loads need no guard and go
+  // totals in registers under ONE uniform branch, the bias index clamped so that the lane's 16 loads need no guard and go
   // out together.  (One branch and one guarded load per store cost every call 1.7 %, with or without the epilogue.)
   if (act) {
 #pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
+    for (int i = 0; i < 16; ++i) {
+      const int k = 32 * ktw + acc_channel(i, hh);
+      const float b = bias ? bias[k < K ? k : K - 1] : 0.f;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int k = 32 * (kt0 + kt) + acc_channel(i, hh);
-        const float b = bias ? bias[k < K ? k : K - 1] : 0.f;
-#pragma unroll
-        for (int pt = 0; pt < 2; ++pt) {
-          float v = tot[pt][kt][i];
-          v += b;
-          tot[pt][kt][i] = v > 0.f ? v : v * slope;
-        }
+      for (int pt = 0; pt < PT; ++pt) {
+        float v = tot[pt][i];
+        v += b;
+        tot[pt][i] = v > 0.f ? v : v * slope;
       }
+    }
   }
   float* yn = y + (long)n * y_bs;
   const int gw = w0 + pcol;
 #pragma unroll
-  for (int pt = 0; pt < 2; ++pt) {
-    const int gh = h0 + prow[pt];
+  for (int pt = 0; pt < PT; ++pt) {
+    const int gh = h0 + prow0 + pt * G::PR;
     if (gh >= H || gw >= W) continue;
 #pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int k = 32 * (kt0 + kt) + acc_channel(i, hh);
-        if (k < K) yn[(long)k * HWl + gh * W + gw] = tot[pt][kt][i];
-      }
+    for (int i = 0; i < 16; ++i) {
+      const int k = 32 * ktw + acc_channel(i, hh);
+      if (k < K) yn[(long)k * HWl + gh * W + gw] = tot[pt][i];
+    }
   }
 }
 

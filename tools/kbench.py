@@ -934,6 +934,8 @@ def main():
                          lambda: torch.ops.aten.convolution_backward(gy, x, wt, None, *conv_args, [True, False, False]))):
                     a, b = spread(mine), spread(theirs)
                     cin, cout = (Cl, Kl) if what == 'fwd  ' else (Kl, Cl)
+                    for k, m in enumerate(MANIFEST[-6:]):  # the six segments above: tools/pmc_kernels.py finds the layer by them
+                        m.update(name='splitconv/%s %s' % ('kernel' if k < 3 else 'miopen', what.strip()), shape=[B2, cin, cout, h, w])
                     print('splitconv %s %-22s kernel %8.1f (%8.1f .. %8.1f)  MIOpen %8.1f (%8.1f .. %8.1f)  %5.2fx  %6.1f TF' % (
                         what, [B2, cin, cout, h, w], a[0], a[1], a[2], b[0], b[1], b[2], b[0] / a[0], flop / a[0] / 1e6), flush=True)
                 del x, gy, y, dx

@@ -23,6 +23,11 @@ tile; two; two; a chunk of two and a chunk of one), N = 2, and five maps.  5x7, 
 tile by the host's rule (pixel_tile below restates it), so 9x13 (16 x 2) and 17x7 (8 x 4) are there as well.  Weight
 gradient: 2x3x2x5x7, 1x17x33x13x21, 3x40x96x9x35, 1x33x64x5x160 (three strips, the last with two steps) and 1x8x40x6x24
 (three groups: a half-empty step).
+
+--cases retile: a second list for the 4 x 1 wave tile of the KT = 2 launches, recorded in
+tests/golden/splitconv_retile_bits.txt: K in {40, 65, 160} (a partly filled second tile of a wave pair; chunks of 2 + 1 and
+2 + 2 + 1 tiles with their first-tile offsets), C in {64, 70}, N = 2, and the maps 8x32 (all eight 32 x 1 tiles live), 4x33
+(pixel tiles 4..7, the four of waves 1 and 3, wholly outside the map; two tiles across) and 9x13 (16 x 2).
 """
 import argparse
 import hashlib
@@ -36,6 +41,9 @@ KS = (1, 33, 64, 96)
 N_FWD = 2
 MAPS = ((5, 7), (6, 20), (3, 40), (9, 13), (17, 7))
 WGRAD_CASES = ((2, 3, 2, 5, 7), (1, 17, 33, 13, 21), (3, 40, 96, 9, 35), (1, 33, 64, 5, 160), (1, 8, 40, 6, 24))
+RETILE_CS = (64, 70)
+RETILE_KS = (40, 65, 160)
+RETILE_MAPS = ((8, 32), (4, 33), (9, 13))
 SLOPE = 0.1
 NAN_BITS = 0x7FC07FC0  # a NaN as float32 and as two bf16
 
@@ -192,11 +200,19 @@ def all_lines(run):
         yield fmt(wgrad_head(*case), wgrad_case(run, *case))
 
 
+def retile_lines(run):
+    for H, W in RETILE_MAPS:
+        for C in RETILE_CS:
+            for K in RETILE_KS:
+                yield fmt(fwd_head(C, K, H, W), fwd_case(run, C, K, H, W))
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument('--flagship', action='store_true', help='the flagship step\'s layers at 16x96x160 and 16x48x80 instead of the cases')
+    ap.add_argument('--cases', choices=('default', 'retile'), default='default', help='which case list (see the module docstring)')
     args = ap.parse_args()
     run = Runner(args.root)
-    for line in (flagship_lines(run) if args.flagship else all_lines(run)):
+    for line in (flagship_lines(run) if args.flagship else retile_lines(run) if args.cases == 'retile' else all_lines(run)):
         print(line, flush=True)
