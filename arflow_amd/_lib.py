@@ -140,6 +140,10 @@ PROTOTYPES = {
     'arflow_optim_partials': [c_l],
     'arflow_optim_gradnorm': [c_fp, c_fp, c_l, c_fp],
     'arflow_optim_step': [c_fp, c_i, c_fp, c_fp, c_fp, c_l, c_fp, c_i, c_fp, c_i, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_d, c_fp],
+    'arflow_ar_transform': [c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_ar_loss_partials': [c_i, c_i, c_i],
+    'arflow_ar_loss_fwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_f, c_f, c_fp],
+    'arflow_ar_loss_bwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_f, c_f, c_fp],
     'arflow_uncert_rows': [c_i, c_i],
     'arflow_uncert_prep': [c_fp, c_fp, c_fp, c_l, c_fp, c_fp, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_sparsify_sums': [c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp],

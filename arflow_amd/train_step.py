@@ -92,10 +92,17 @@ def synthetic_flow(batch, height, width, device='cuda', seed=0):
 
 
 class TrainStep:
-    def __init__(self, workload, device, lr=1e-4, seed=0, n_buckets=4, feature_storage='fp32', train_cfg=None):
+    def __init__(self, workload, device, lr=1e-4, seed=0, n_buckets=4, feature_storage='fp32', train_cfg=None, ar_cfg=None):
         """train_cfg: the `train` section of a config (optim, lr, decay groups, clip, lr schedule): the step is then taken by
-        arflow_amd.optim.FlatOptimizer on the flat gradient buffer and `lr` is ignored.  None: torch.optim.Adam as below."""
+        arflow_amd.optim.FlatOptimizer on the flat gradient buffer and `lr` is ignored.  None: torch.optim.Adam as below.
+        ar_cfg: the augmentation-regularisation pass (arflow_amd.ar; build-defined wiring): w_ar, ar_eps
+        (0.0), ar_q (1.0), mask_st (True) and st_cfg (ar.draw_ar_params; missing keys read as off).  None: no second pass."""
         mcfg, lcfg = WORKLOADS[workload]
+        if ar_cfg is not None and lcfg['type'] in ('mse', 'elbo', 'uflow_elbo'):
+            raise ValueError('ar_cfg is wired into the unsupervised flow losses only, not into loss type %r' % lcfg['type'])
+        self.ar_cfg = ar_cfg
+        self.ar_generator = None if ar_cfg is None else torch.Generator(device='cpu').manual_seed(int(seed))
+        self.last_ar = None
         if feature_storage != 'fp32':
             if mcfg['type'] != 'pwclite_uflow':
                 raise ValueError('feature_storage=%r is wired into the pwclite_uflow model only' % feature_storage)
@@ -151,7 +158,33 @@ class TrainStep:
         else:
             flows = [torch.cat([fw, bw], 1) for fw, bw in zip(res['flows_fw'], res['flows_bw'])]
             out = self.loss(flows, img_pair)
+        if self.ar_cfg is not None:
+            out = self._ar_pass(out, res, model_in)
         return self._step(out)
+
+    def _ar_pass(self, out, res, model_in):
+        """The second pass (arflow_amd.ar): the first pass's finest forward flow and, with mask_st and a loss that exposes one
+        (unFlowLoss.pyramid_occu_mask1), its non-occlusion mask are moved through a drawn theta together with the model's
+        input; the model runs again on the transformed frames without the backward direction and w_ar * ar_loss joins the
+        first loss, so one backward serves both.  The targets carry no gradient."""
+        from . import ar
+        from .augment import _get
+        cfg = self.ar_cfg
+        flow = res['flows_fw'][0][:, :2].detach()
+        B, _, H, W = (int(v) for v in model_in.shape)
+        if tuple(flow.shape[-2:]) != (H, W):
+            raise ValueError('the AR pass needs the finest flow at the input size %r (got %r)' % ((H, W), tuple(flow.shape[-2:])))
+        noc = None
+        masks = getattr(self.loss, 'pyramid_occu_mask1', None)
+        if _get(cfg, 'mask_st', True) and masks:
+            noc = masks[0].detach()
+        theta = ar.draw_ar_params(_get(cfg, 'st_cfg', None), B, (H, W), self.ar_generator)
+        img_t, flow_t, mask_t = ar.ar_transform(theta, img=model_in, flow=flow, noc=noc)
+        pred = self.model(img_t, with_bk=False)['flows_fw'][0][:, :2]
+        self.last_ar = ar.ar_loss(pred, flow_t, mask_t, eps=float(_get(cfg, 'ar_eps', 0.0)), q=float(_get(cfg, 'ar_q', 1.0)))
+        total = out[0] + float(_get(cfg, 'w_ar', 0.0)) * self.last_ar.to(out[0].dtype)
+        self.last_ar = self.last_ar.detach()
+        return (total,) + tuple(out[1:])
 
     def _step(self, out):
         self.reducer.zero_grad()

@@ -982,6 +982,39 @@ int arflow_optim_step(const long long* table, int nrows, const float* grad, floa
                       int nparts, int* skipped, int rule, int first, double lr, double bc1, double sqbc2, double eps, double beta1,
                       double beta2, double clip, arflow_stream_t stream);
 
+/* ---- the augmentation-regularisation pass (csrc/ar.hip) ----------------------------
+ * arflow_ar_transform: ONE launch moves an image stack, a flow field and a non-occlusion mask through a per-sample affine map.
+ *   theta [B][6] float32 ON THE DEVICE, (a b tx; c d ty): output pixel (x', y') samples the source position
+ *   s = (a x' + b y' + tx, c x' + d y' + ty) in pixel units, bilinear with zero padding (utils/warp_utils.py:83-90 with
+ *   pad='zeros', align_corners=True, without grid_sample's normalise / un-normalise round trip).
+ *     img [B][C][Hs][Ws]  -> img_t  [B][C][H][W]   every channel of a sample shares its row of theta
+ *     flow [B][2][Hs][Ws] -> flow_t [B][2][H][W]   the sampled vector g times the inverse of L = [[a, b], [c, d]]:
+ *                                                  u_t = (d g_u - b g_v) / det, v_t = (a g_v - c g_u) / det, det = a d - b c
+ *     noc [B][1][Hs][Ws]  -> mask_t [B][1][H][W]   the sampled mask times border_mask (utils/warp_utils.py:119-134, strict:
+ *                                                  0 < s_x < Ws - 1 and 0 < s_y < Hs - 1); noc NULL reads as ones
+ *   (Hs, Ws) = (H, W) is the reference's flow_warp; another source size carries a ground truth through a crop or a resize.
+ *   All tensors dense.  A NULL destination skips its group; a source whose destination is NULL is not read.  The HOST refuses a
+ *   row with det = 0 (the kernel divides by it); tap indices are clamped into the plane, so any theta reads inside the planes.
+ *   The fp32 operation order is written at the head of csrc/ar.hip.  float4 stores where W % 4 == 0 and the destinations are
+ *   16-byte aligned.
+ * arflow_ar_loss_fwd: sums[0] = sum over b, c, y, x of (|pred - flow_t| + eps)^q mask, sums[1] = sum over b, y, x of mask, both
+ *   float64; pred, flow_t [B][2][H][W], mask [B][1][H][W] or NULL (ones), dense.  One partial pair per workgroup into work
+ *   (arflow_ar_loss_partials(B, H, W) pairs of float64; the query needs no GPU), added in index order by a second launch of the
+ *   same call.  No atomics, no zero-fill: two calls give the same bits in either mode.
+ * arflow_ar_loss_bwd: gpred = (float)gsums[0] q (|e| + eps)^(q - 1) sign(e) mask with e = pred - flow_t and sign(0) = 0, every
+ *   element stored; gsums float64 ON THE DEVICE (only gsums[0] is read: there is no gradient to flow_t or mask).
+ *
+ * ARFLOW_ENULL: theta, pred, flow_t, work, sums, gsums or gpred NULL, or a destination without its source (img_t without img,
+ * flow_t without flow);  ARFLOW_ESHAPE: B outside 1 .. 65535, a side (H, W, Hs, Ws) < 1 or > 2^24, a plane of 2^30 elements or more, C < 1
+ * with img_t given;  ARFLOW_EPARAM: no destination at all; eps < 0, q <= 0, either not finite, or q < 1 with eps = 0. */
+int arflow_ar_transform(const float* theta, const float* img, float* img_t, int C, const float* flow, float* flow_t,
+                        const float* noc, float* mask_t, int B, int Hs, int Ws, int H, int W, arflow_stream_t stream);
+int arflow_ar_loss_partials(int B, int H, int W);
+int arflow_ar_loss_fwd(const float* pred, const float* flow_t, const float* mask, double* work, double* sums, int B, int H,
+                       int W, float eps, float q, arflow_stream_t stream);
+int arflow_ar_loss_bwd(const float* pred, const float* flow_t, const float* mask, const double* gsums, float* gpred, int B,
+                       int H, int W, float eps, float q, arflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ fraction of the 8 TB/s HBM roofline.  Calls the C ABI directly (no autograd over
     python tools/kbench.py --filter mse            # one MseLoss step, fused against composed ATen ops
     python tools/kbench.py --filter augment        # the batch augmentation, fused against composed ATen ops
     python tools/kbench.py --filter optim          # the fused optimiser step against torch.optim.Adam(fused=True)
+    python tools/kbench.py --filter ar             # the AR transform and loss, fused against composed ATen ops
 """
 import argparse
 import json
@@ -25,6 +26,7 @@ def p(t):
     return None if t is None else t.data_ptr()
 
 
+EXACT_FILTERS = ('ar',)
 MANIFEST = []  # (calls in the segment) per timed op, in launch order: tools/pmc_calls.py cuts the counter trace with it
 _marker = None
 
@@ -700,6 +702,88 @@ def augment_bench(dev, jsonl, B=64, src_hw=(384, 512), crop_hw=(256, 448), launc
             out.write(json.dumps(line) + '\n')
 
 
+def ar_bench(dev, jsonl, B=8, hw=(384, 640), launches=20, repeats=5, steps=10):
+    """the fused transform (arflow_ar_transform, one launch: 6 image channels, the flow and the mask of B = 8
+    pairs of 384 x 640 under the drawn theta of ar.DEFAULT_ST_CFG) next to the same transform composed of ATen operations on the
+    same device (tests/ar_ref.composed: three grid_sample calls, the border mask, the 2 x 2 product), and the loss node forward +
+    backward next to its ATen formulation.  HIP events around `launches` calls after 5 warm-ups, the versions in alternation,
+    `repeats` rounds: median (min .. max).  Algorithmic bytes: every plane read once and written once (transform: 9 + 9 planes;
+    loss: pred, flow_t, mask forward and backward, the gradient stored: 12 planes).  Then the step time of pwclite+unflow_loss
+    with and without ar_cfg, `steps` steps per round after 3 warm-ups, in alternation."""
+    import statistics
+    from arflow_amd import ar as AR
+    from arflow_amd.functional import _call, _stream
+    from arflow_amd.train_step import TrainStep, synthetic_pairs
+    from tests import ar_ref as R
+    H, W = hw
+    cpu = torch.Generator().manual_seed(0)
+    theta = AR.draw_ar_params(AR.DEFAULT_ST_CFG, B, hw, cpu).to(dev)
+    img = torch.rand(B, 6, H, W, generator=cpu).to(dev)
+    flow = (3.0 * torch.randn(B, 2, H, W, generator=cpu)).to(dev)
+    noc = (torch.rand(B, 1, H, W, generator=cpu) > 0.2).float().to(dev)
+
+    def fused():
+        out = [torch.empty_like(img), torch.empty_like(flow), torch.empty_like(noc)]
+        _call('arflow_ar_transform', p(theta), p(img), p(out[0]), 6, p(flow), p(out[1]), p(noc), p(out[2]), B, H, W, H, W, _stream())
+        return out
+
+    pred = (flow + torch.randn(B, 2, H, W, generator=cpu).to(dev))
+    eps, q = 0.01, 0.4
+
+    def node(loss):
+        x = pred.clone().requires_grad_(True)
+        loss(x, flow, noc, eps, q).backward()
+        return x.grad
+    cases = {'transform': ({'fused': fused, 'composed ATen': lambda: R.composed(theta, img, flow, noc)}, 18 * B * H * W * 4),
+             'loss fwd+bwd': ({'fused': lambda: node(AR.ar_loss), 'composed ATen': lambda: node(R.composed_loss)}, 12 * B * H * W * 4)}
+    with open(jsonl, 'a') as out:
+        for tag, (fns, nbytes) in cases.items():
+            a, b = fns['fused'](), fns['composed ATen']()
+            diff = max(float((x - y).abs().max()) for x, y in (zip(a, b) if tag == 'transform' else [(a, b)]))
+            del a, b
+            t = {name: [] for name in fns}
+            for _ in range(repeats):
+                for name, fn in fns.items():
+                    t[name].append(timeit(fn, launches))
+                    MANIFEST[-1].update(name='ar/%s/%s' % (tag, name), shape=[])
+            line = {'bench': 'ar', 'case': tag, 'shape': [B, 6 + 2 + 1, H, W], 'st_cfg': {k: list(v) if isinstance(v, tuple) else v
+                                                                                        for k, v in AR.DEFAULT_ST_CFG.items()},
+                    'algorithmic_bytes': nbytes, 'max_abs_diff': diff}
+            for name, v in t.items():
+                key = name.split()[0]
+                line.update({key + '_us': statistics.median(v), key + '_us_min': min(v), key + '_us_max': max(v)})
+                print('ar %-14s %-14s %9.1f us (%.1f .. %.1f)' % (tag, name, statistics.median(v), min(v), max(v)), flush=True)
+            gbs = nbytes / line['fused_us'] / 1e3
+            line.update(fused_gbs=gbs, fused_fraction_of_hbm_peak=gbs / HBM_PEAK_GBS, hbm_peak_gbs=HBM_PEAK_GBS,
+                        composed_over_fused=line['composed_us'] / line['fused_us'])
+            print('ar %-14s composed / fused = %.2f   fused %.0f GB/s = %.1f%% of HBM peak   (max |diff| %.1e)'
+                  % (tag, line['composed_over_fused'], gbs, 100 * gbs / HBM_PEAK_GBS, diff), flush=True)
+            out.write(json.dumps(line) + '\n')
+        # the whole step, with and without the second pass
+        x = synthetic_pairs(B, H, W, device=dev, seed=5)
+        ar_cfg = dict(w_ar=0.01, ar_eps=eps, ar_q=q, mask_st=True, st_cfg=AR.DEFAULT_ST_CFG)
+        runs = {'plain': TrainStep('pwclite+unflow_loss', dev, seed=0), 'ar_cfg': TrainStep('pwclite+unflow_loss', dev, seed=0, ar_cfg=ar_cfg)}
+        t = {name: [] for name in runs}
+        for r in range(repeats):
+            for name, step in runs.items():
+                for _ in range(3 if r == 0 else 1):
+                    step(x)
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(steps):
+                    step(x)
+                e1.record()
+                torch.cuda.synchronize()
+                t[name].append(e0.elapsed_time(e1) / steps)
+        line = {'bench': 'ar', 'case': 'step pwclite+unflow_loss', 'shape': [B, 6, H, W], 'steps': steps}
+        for name, v in t.items():
+            line.update({name + '_ms': statistics.median(v), name + '_ms_min': min(v), name + '_ms_max': max(v)})
+            print('ar step %-8s %8.2f ms (%.2f .. %.2f)' % (name, statistics.median(v), min(v), max(v)), flush=True)
+        line['ar_over_plain'] = line['ar_cfg_ms'] / line['plain_ms']
+        out.write(json.dumps(line) + '\n')
+
+
 def optim_bench(dev, jsonl, launches=20, repeats=5):
     """arflow_amd.optim.FlatOptimizer.step() (one launch; two with the clip) on the parameters of
     PWCProbFlow [2,2,0] (5,909,172 elements) under the train section of configs/chairs_uflow_elbo.json, next to what TrainStep
@@ -767,8 +851,8 @@ def main():
     ap.add_argument('--levels', default='uflow')
     ap.add_argument('--batch', type=int, default=16, help='model-side batch (2B: both directions stacked)')
     ap.add_argument('--size', type=int, nargs=2, default=[384, 640])
-    ap.add_argument('--jsonl', default='', help='--filter augment and --filter optim append their result lines here '
-                    '(default: profiles/augment_kbench.jsonl and profiles/optim_kbench.jsonl)')
+    ap.add_argument('--jsonl', default='', help='--filter augment, optim and ar append their result lines here '
+                    '(default: profiles/augment_kbench.jsonl, profiles/optim_kbench.jsonl, profiles/ar_kbench.jsonl)')
     ap.add_argument('--manifest', default='', help='write the ordered (name, shape, calls) list of the timed ops here')
     args = ap.parse_args()
     lib = _lib.load()
@@ -794,7 +878,8 @@ def main():
         print('%-22s %-26s %9.1f us %9.1f GB/s  %5.1f%% of HBM peak' % (name, list(shape), us, gbs, 100 * gbs / HBM_PEAK_GBS), flush=True)
 
     def want(n):
-        return any(f in n for f in args.filter.split('|'))
+        # a token in EXACT_FILTERS is a substring of other ops' names ('ar' of 'warp'): it selects the bench of that name only
+        return any(f == n if f in EXACT_FILTERS else f in n for f in args.filter.split('|'))
 
     for C, h, w in levels:
         x1 = torch.randn(B2, C, h, w, device=dev, generator=g)
@@ -1261,6 +1346,8 @@ def main():
         augment_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'augment_kbench.jsonl'))
     if want('optim'):  # the fused optimiser step (csrc/optim.hip) against torch.optim.Adam(fused=True) on the same flat buffer
         optim_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'optim_kbench.jsonl'))
+    if want('ar'):  # the AR transform and loss (csrc/ar.hip) against the same arithmetic composed of ATen operations
+        ar_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'ar_kbench.jsonl'))
     if args.manifest:
         json.dump(MANIFEST, open(args.manifest, 'w'), indent=1)
     if not rows:  # only ops that keep their own byte model (the head convolutions) were selected
