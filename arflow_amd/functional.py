@@ -811,12 +811,11 @@ def _splitconv_wgrad_rule(N, C, K, H, W):
     # 275->128 1.36x, 403->96 1.55x, 499->64 1.55x, 563->32 1.46x, 597->128 1.39x (64->32 0.67x is not) -- and at 48x80 on
     # 275->128 1.10x, 403->96 1.23x, 499->64 1.51x, 597->128 1.27x (147->128 0.90x is not; 563->32 1.06x, a single tile of
     # output channels, is left where it was); on two calls at 24x40 (1.1x), which the floor keeps out
-    if N * H * W < 16 * 48 * 80:
-        return False
+    # (every size condition goes through _size_floor, like the other rules': a test that patches the floor moves all of them)
     if _size_floor(N, H, W, 96, 160):
         return 128 <= C <= 640 and 32 <= K <= 128
-    # (fewer maps of 96x160 or more were not measured: they keep MIOpen)
-    return H * W < 96 * 160 and _size_floor(N, H, W, 48, 80) and 256 <= C <= 640 and 64 <= K <= 128
+    # (fewer maps of 96x160 or more were not measured: they keep MIOpen -- 16 maps of that size would pass the floor)
+    return not _size_floor(16, H, W, 96, 160) and _size_floor(N, H, W, 48, 80) and 256 <= C <= 640 and 64 <= K <= 128
 
 
 def _batch_strided(t):

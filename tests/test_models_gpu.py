@@ -174,14 +174,21 @@ def _worst_rel(ga, gb, names):
     return worst
 
 
-@pytest.mark.parametrize('tag,linear', [('pwclite2', True), ('pwclite2', False), ('pwclite_uflow_0', False),
-                                        ('pwclite_uflow_1', False), ('pwcflow', False), ('pwcflow', True),
-                                        ('pwclite_uflow_border', False)])
+GRAD_CASES = [('pwclite2', True, False), ('pwclite2', False, False), ('pwclite_uflow_0', False, False),
+              ('pwclite_uflow_1', False, False), ('pwcflow', False, False), ('pwcflow', True, False),
+              ('pwclite_uflow_border', False, False),
+              # native: the benchmark's configuration with the routing floor moved so that this input's four levels take the
+              # split-bf16 / in-place / dilated-chain paths the benchmark's take (tests/test_conv_stack_cpu.py holds the table,
+              # tests/test_conv_stack_gpu.py asserts the launches); same objective, same twin, same bound
+              ('pwclite_uflow_1', False, True)]
+
+
+@pytest.mark.parametrize('tag,linear,native', GRAD_CASES, ids=['%s-%s%s' % (t, l, '-native' if n else '') for t, l, n in GRAD_CASES])
 # (ADVICE r2 asked for a fixed-tolerance `linear` variant per architecture.  PWCFlow has one (1e-3, like pwclite2).  For
 #  PWCLiteUflow it cannot be held: with the conv activations removed some bias gradients nearly cancel (max|g| 2e-5 against
 #  3e-2 elsewhere) and the ORACLE twin on the GPU differs from the oracle twin on the CPU by 0.74 of that maximum -- more
 #  than the HIP path does (0.38): measured with tools-style probing in round 3, nothing a tolerance can pin.)
-def test_model_parameter_gradients_elementwise(tag, linear):
+def test_model_parameter_gradients_elementwise(tag, linear, native, monkeypatch):
     """Whole-model backward, ELEMENT-WISE per parameter tensor: the product model on the HIP kernels against
     the same host model with the oracle ops patched in, same deterministic weights and inputs.
 
@@ -202,7 +209,17 @@ def test_model_parameter_gradients_elementwise(tag, linear):
     cls, cfg = _case(tag)
     x = synth_pair(2, 192, 256, torch.Generator().manual_seed(5))[0]
     torch.set_num_threads(16)
+    if native:
+        import arflow_amd.functional as AF
+        from tests.test_conv_stack_cpu import patch_floor_to_benchmark
+        patch_floor_to_benchmark(monkeypatch)
+        launched, real_call = [], AF._call
+        monkeypatch.setattr(AF, '_call', lambda name, *a, **kw: (launched.append(name), real_call(name, *a, **kw))[1])
     l_hip, g_hip, names = _param_grads(cls, cfg, x, 'cuda', True, linear)
+    if native:
+        monkeypatch.setattr(AF, '_call', real_call)
+        assert launched.count('arflow_splitconv_wgrad') == 10 and launched.count('arflow_phase_move') == 6, \
+            'the native paths did not run: %s' % {n: launched.count(n) for n in set(launched)}
     l_cpu, g_cpu, _ = _param_grads(cls, cfg, x, 'cpu', False, linear)
     assert abs(l_hip - l_cpu) <= 2e-6 * abs(l_cpu), (l_hip, l_cpu)
     if linear:
