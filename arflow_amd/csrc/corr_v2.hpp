@@ -198,13 +198,10 @@ __global__ __launch_bounds__(NT * G, (NBUF == 4 && G == 1) ? 2 : 3) void fwd_ker
     m.m1 = m.m2 = m.mu = 0.f, m.var = 1.f;
     if (na.nrows > 0 || na.r1)
       m = featnorm::moments_of(featnorm::MomentSrc{na.acc, na.nrows, na.r1, na.n1, na.r2, na.n2}, b, (long)C * cs, na.mode);
-    const float sd = sqrtf(m.var + 1e-16f);
+    const float sd = featnorm::sd_of(m);
     mu = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, m.mu)));
     rs = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, 1.0f / sd)));
-    if (na.stats && btx == 0 && bty == 0 && threadIdx.x == 0) {
-      float* st = na.stats + 4 * b;
-      st[0] = m.m1, st[1] = m.m2, st[2] = m.mu, st[3] = sd;
-    }
+    if (na.stats && btx == 0 && bty == 0 && threadIdx.x == 0) featnorm::store_stats(na.stats + 4 * b, m, sd);
     if (na.x1n) x1n_p = na.x1n + (long)b * na.x1n_bs + (long)gy * W + gx;
   }
 

@@ -24,19 +24,20 @@
 
 namespace {
 
-constexpr int NT = 256, VPT = 16;  // floats per thread per tensor and trip (4 float4)
+constexpr int NT = 256;
+using featnorm::VPT;  // floats per thread per tensor and trip (4 float4)
 // Partial sums: every workgroup of the reduction pass STORES its 4 doubles into its own row of `acc`
 // ([B][rows][4], rows = its grid.x <= 2048/B + 1), the apply pass adds a sample's rows (one per lane, wave-reduced).
 // No zero-fill and no atomics (round 1 added into 8 slotted rows per sample after a hipMemsetAsync -- a separate
 // ~4 us GPU operation per call; ~120 workgroups adding into ONE address per sample had serialised at the L2).
+// The arithmetic of every kernel below is featnorm_stats.hpp's; what is left here is which block does what.
 
 using featnorm::Moments;
-using featnorm::moments_from_totals;
-using featnorm::moments_of;
-using featnorm::sum_rows;
-template <int NV, int NTH = NT>
-__device__ __forceinline__ void block_sum_f64(double (&v)[NV], double* scratch) {
-  af_block_sum_f64<NV, NTH>(v, scratch);
+
+// y1's gradient comes in two parts: g1 and g1b (nullable), a second gradient that is added on load -- the slot of the
+// decoder's concatenated input that holds y1 (sample b at g1b + b * g1b_bs, n contiguous floats); saves the separate add pass.
+__device__ __forceinline__ const float* g1b_of(const float* g1b, long g1b_bs, int b) {
+  return g1b ? g1b + (long)b * g1b_bs : nullptr;
 }
 
 // grid (blocks per sample, B).  acc[b] += (sum x1, sum x1^2, sum x2, sum x2^2) of this block's slice.
@@ -46,8 +47,10 @@ __global__ __launch_bounds__(NT) void moment_kernel(const float* __restrict__ x1
   const int b = blockIdx.y;
   const float* p1 = x1 + (long)b * n;
   const float* p2 = x2 + (long)b * n;
+  // featnorm::moment_partials<NT>(p1, p2, n, blockIdx.x, gridDim.x, s), written out: the call compiles to another schedule,
+  // measured 2 % slower with apply_kernel at n = 122880 and 491520; the steps are the header's
   double s[4] = {0.0, 0.0, 0.0, 0.0};
-  const long n4 = (n % 4 == 0) ? n / 4 : 0;  // float4 part (rows are 16-byte aligned only when n % 4 == 0)
+  const long n4 = (n % 4 == 0) ? n / 4 : 0;
   for (long i0 = (long)blockIdx.x * NT * (VPT / 4); i0 < n4; i0 += (long)gridDim.x * NT * (VPT / 4)) {
     float a1 = 0.f, q1 = 0.f, a2 = 0.f, q2 = 0.f;
 #pragma unroll
@@ -56,19 +59,17 @@ __global__ __launch_bounds__(NT) void moment_kernel(const float* __restrict__ x1
       if (i < n4) {
         const float4 u = reinterpret_cast<const float4*>(p1)[i];
         const float4 v = reinterpret_cast<const float4*>(p2)[i];
-        a1 += (u.x + u.y) + (u.z + u.w);
-        q1 = fmaf(u.x, u.x, fmaf(u.y, u.y, fmaf(u.z, u.z, fmaf(u.w, u.w, q1))));
-        a2 += (v.x + v.y) + (v.z + v.w);
-        q2 = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, q2))));
+        featnorm::moment_step(u, a1, q1);
+        featnorm::moment_step(v, a2, q2);
       }
     }
     s[0] += (double)a1, s[1] += (double)q1, s[2] += (double)a2, s[3] += (double)q2;
   }
-  for (long i = 4 * n4 + (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {  // unaligned sizes
+  for (long i = 4 * n4 + (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
     const float u = p1[i], v = p2[i];
     s[0] += (double)u, s[1] += (double)u * (double)u, s[2] += (double)v, s[3] += (double)v * (double)v;
   }
-  block_sum_f64<4>(s, scratch);
+  af_block_sum_f64<4, NT>(s, scratch);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[4 * ((long)b * gridDim.x + blockIdx.x) + k] = s[k];
@@ -81,24 +82,20 @@ __global__ __launch_bounds__(NT) void apply_kernel(const float* __restrict__ x1,
                                                    const double* __restrict__ acc, int nrows, float* __restrict__ stats,
                                                    long n, int mode) {
   const int b = blockIdx.y;
-  const Moments m = moments_of(acc + 4L * nrows * b, nrows, n, mode);
-  const float sd = sqrtf(m.var + 1e-16f);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    float* st = stats + 4 * b;
-    st[0] = m.m1, st[1] = m.m2, st[2] = m.mu, st[3] = sd;
-  }
+  const Moments m = featnorm::moments_of(acc + 4L * nrows * b, nrows, n, mode);
+  const float sd = featnorm::sd_of(m);
+  if (blockIdx.x == 0 && threadIdx.x == 0) featnorm::store_stats(stats + 4 * b, m, sd);
   const float* p1 = x1 + (long)b * n;
   const float* p2 = x2 + (long)b * n;
   float* o1 = y1 + (long)b * n;
   float* o2 = y2 + (long)b * n;
+  // featnorm::apply_fwd(p1, p2, o1, o2, n, m.mu, sd, blockIdx.x * NT + threadIdx.x, gridDim.x * NT), written out (see moment_kernel)
   const long n4 = (n % 4 == 0) ? n / 4 : 0;
   for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT) {
     const float4 u = reinterpret_cast<const float4*>(p1)[i];
     const float4 v = reinterpret_cast<const float4*>(p2)[i];
-    reinterpret_cast<float4*>(o1)[i] =
-        make_float4((u.x - m.mu) / sd, (u.y - m.mu) / sd, (u.z - m.mu) / sd, (u.w - m.mu) / sd);
-    reinterpret_cast<float4*>(o2)[i] =
-        make_float4((v.x - m.mu) / sd, (v.y - m.mu) / sd, (v.z - m.mu) / sd, (v.w - m.mu) / sd);
+    reinterpret_cast<float4*>(o1)[i] = featnorm::normalized(u, m.mu, sd);
+    reinterpret_cast<float4*>(o2)[i] = featnorm::normalized(v, m.mu, sd);
   }
   for (long i = 4 * n4 + (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
     o1[i] = (p1[i] - m.mu) / sd;
@@ -107,91 +104,34 @@ __global__ __launch_bounds__(NT) void apply_kernel(const float* __restrict__ x1,
 }
 
 // acc[b] += (sum g, sum g (x - mu)) over both tensors (entries 0, 1)
-// g1b (nullable): a second gradient of y1 that is added on load -- the slot of the decoder's concatenated input that
-// holds y1 (sample b at g1b + b * g1b_bs, n contiguous floats); saves the separate add pass.
-__device__ __forceinline__ float4 ld4_sum(const float* a, const float* b, long i) {
-  float4 v = reinterpret_cast<const float4*>(a)[i];
-  if (b) {
-    const float4 w = reinterpret_cast<const float4*>(b)[i];
-    v.x += w.x, v.y += w.y, v.z += w.z, v.w += w.w;
-  }
-  return v;
-}
 __global__ __launch_bounds__(NT) void bwd_sum_kernel(const float* __restrict__ g1, const float* __restrict__ g2,
                                                      const float* __restrict__ x1, const float* __restrict__ x2,
                                                      const float* __restrict__ stats, double* __restrict__ acc,
                                                      long n, const float* __restrict__ g1b, long g1b_bs) {
   __shared__ double scratch[2 * (NT / 64)];
   const int b = blockIdx.y;
-  const float mu = stats[4 * b + 2];
   const long o = (long)b * n;
-  const float* gbp = g1b ? g1b + (long)b * g1b_bs : nullptr;
-  double s[2] = {0.0, 0.0};
-  const long n4 = (n % 4 == 0) ? n / 4 : 0;
-  for (long i0 = (long)blockIdx.x * NT * (VPT / 4); i0 < n4; i0 += (long)gridDim.x * NT * (VPT / 4)) {
-    float sg = 0.f, sq = 0.f;
-#pragma unroll
-    for (int k = 0; k < VPT / 4; ++k) {
-      const long i = i0 + (long)k * NT + threadIdx.x;
-      if (i < n4) {
-        const float4 ga = ld4_sum(g1 + o, gbp, i), xa = reinterpret_cast<const float4*>(x1 + o)[i];
-        const float4 gb = reinterpret_cast<const float4*>(g2 + o)[i], xb = reinterpret_cast<const float4*>(x2 + o)[i];
-        sg += ((ga.x + ga.y) + (ga.z + ga.w)) + ((gb.x + gb.y) + (gb.z + gb.w));
-        sq = fmaf(ga.x, xa.x - mu, fmaf(ga.y, xa.y - mu, fmaf(ga.z, xa.z - mu, fmaf(ga.w, xa.w - mu, sq))));
-        sq = fmaf(gb.x, xb.x - mu, fmaf(gb.y, xb.y - mu, fmaf(gb.z, xb.z - mu, fmaf(gb.w, xb.w - mu, sq))));
-      }
-    }
-    s[0] += (double)sg, s[1] += (double)sq;
-  }
-  for (long i = 4 * n4 + (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
-    const float ga = g1[o + i] + (gbp ? gbp[i] : 0.f), gb = g2[o + i];
-    s[0] += (double)ga + (double)gb;
-    s[1] += (double)ga * (double)(x1[o + i] - mu) + (double)gb * (double)(x2[o + i] - mu);
-  }
-  block_sum_f64<2>(s, scratch);
+  double s[2];
+  featnorm::bwd_partials<NT>(g1 + o, g1b_of(g1b, g1b_bs, b), g2 + o, x1 + o, x2 + o, stats[4 * b + 2], n, blockIdx.x,
+                             gridDim.x, s);
+  af_block_sum_f64<2, NT>(s, scratch);
   if (threadIdx.x == 0) {
     acc[4 * ((long)b * gridDim.x + blockIdx.x)] = s[0];
     acc[4 * ((long)b * gridDim.x + blockIdx.x) + 1] = s[1];
   }
 }
 
-// With r = 1/std, G = sum g, Q = sum g (x - mu) (both tensors):
-//   JOINT: dx = r g - r G / N - r^3 Q (x - mu) / (N - 1),           N = 2n
-//   AVG:   dx_i = r g - r G / (2n) - r^3 Q (x - m_i) / (2 (n - 1))
+// d1, d2 (either nullable) from the rows the sum pass left
 __global__ __launch_bounds__(NT) void bwd_apply_kernel(const float* __restrict__ g1, const float* __restrict__ g2,
                                                        const float* __restrict__ x1, const float* __restrict__ x2,
                                                        const float* __restrict__ stats, const double* __restrict__ acc,
                                                        int nrows, float* __restrict__ d1, float* __restrict__ d2, long n,
                                                        int mode, const float* __restrict__ g1b, long g1b_bs) {
   const int b = blockIdx.y;
-  const float* gbp = g1b ? g1b + (long)b * g1b_bs : nullptr;
-  const float* st = stats + 4 * b;
-  const double r = 1.0 / (double)st[3];
-  double gq[2];
-  sum_rows<2>(acc + 4L * nrows * b, nrows, gq);
-  const double G = gq[0], Q = gq[1];
-  const double dn = (double)n;
-  const float rf = (float)r;
-  const float cg = (float)(r * G / (2.0 * dn));
-  const float cq = (float)(mode == ARFLOW_FEATNORM_JOINT ? r * r * r * Q / (2.0 * dn - 1.0) : r * r * r * Q / (2.0 * (dn - 1.0)));
-  const float c1 = mode == ARFLOW_FEATNORM_JOINT ? st[2] : st[0], c2 = mode == ARFLOW_FEATNORM_JOINT ? st[2] : st[1];
+  const featnorm::NormBwd nb = featnorm::norm_bwd_coeffs(acc + 4L * nrows * b, nrows, stats + 4 * b, n, mode);
   const long o = (long)b * n;
-  auto f = [&](float g, float x, float c) { return fmaf(rf, g, -cg) - cq * (x - c); };
-  const long n4 = (n % 4 == 0) ? n / 4 : 0;
-  for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT) {
-    if (d1) {
-      const float4 g = ld4_sum(g1 + o, gbp, i), x = reinterpret_cast<const float4*>(x1 + o)[i];
-      reinterpret_cast<float4*>(d1 + o)[i] = make_float4(f(g.x, x.x, c1), f(g.y, x.y, c1), f(g.z, x.z, c1), f(g.w, x.w, c1));
-    }
-    if (d2) {
-      const float4 g = reinterpret_cast<const float4*>(g2 + o)[i], x = reinterpret_cast<const float4*>(x2 + o)[i];
-      reinterpret_cast<float4*>(d2 + o)[i] = make_float4(f(g.x, x.x, c2), f(g.y, x.y, c2), f(g.z, x.z, c2), f(g.w, x.w, c2));
-    }
-  }
-  for (long i = 4 * n4 + (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
-    if (d1) d1[o + i] = f(g1[o + i] + (gbp ? gbp[i] : 0.f), x1[o + i], c1);
-    if (d2) d2[o + i] = f(g2[o + i], x2[o + i], c2);
-  }
+  featnorm::apply_bwd(nb, g1 + o, g1b_of(g1b, g1b_bs, b), g2 + o, x1 + o, x2 + o, d1 ? d1 + o : nullptr, d2 ? d2 + o : nullptr,
+                      n, (long)blockIdx.x * NT + threadIdx.x, (long)gridDim.x * NT);
 }
 
 // Coarsest pyramid levels (n <= SMALL_N floats per tensor and sample; at n = 30720 the two-launch form is
@@ -207,54 +147,17 @@ __global__ __launch_bounds__(NTS) void fwd_small_kernel(const float* __restrict_
   __shared__ double scratch[4 * (NTS / 64)];
   __shared__ double tot[4];
   const int b = blockIdx.x;
-  const float* p1 = x1 + (long)b * n;
-  const float* p2 = x2 + (long)b * n;
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  const long n4 = (n % 4 == 0) ? n / 4 : 0;
-  for (long i0 = 0; i0 < n4; i0 += 4 * NTS) {  // fp32 partials over <= 16 values, double beyond
-    float a1 = 0.f, q1 = 0.f, a2 = 0.f, q2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const long i = i0 + (long)k * NTS + threadIdx.x;
-      if (i < n4) {
-        const float4 u = reinterpret_cast<const float4*>(p1)[i];
-        const float4 v = reinterpret_cast<const float4*>(p2)[i];
-        a1 += (u.x + u.y) + (u.z + u.w);
-        q1 = fmaf(u.x, u.x, fmaf(u.y, u.y, fmaf(u.z, u.z, fmaf(u.w, u.w, q1))));
-        a2 += (v.x + v.y) + (v.z + v.w);
-        q2 = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, q2))));
-      }
-    }
-    s[0] += (double)a1, s[1] += (double)q1, s[2] += (double)a2, s[3] += (double)q2;
-  }
-  for (long i = 4 * n4 + threadIdx.x; i < n; i += NTS) {
-    const float u = p1[i], v = p2[i];
-    s[0] += (double)u, s[1] += (double)u * (double)u, s[2] += (double)v, s[3] += (double)v * (double)v;
-  }
-  block_sum_f64<4, NTS>(s, scratch);
+  const long o = (long)b * n;
+  double s[4];
+  featnorm::moment_partials<NTS>(x1 + o, x2 + o, n, 0, 1, s);
+  af_block_sum_f64<4, NTS>(s, scratch);
   if (threadIdx.x == 0) tot[0] = s[0], tot[1] = s[1], tot[2] = s[2], tot[3] = s[3];
   __syncthreads();
   const double a[4] = {tot[0], tot[1], tot[2], tot[3]};
-  const Moments m = moments_from_totals(a, n, mode);
-  const float sd = sqrtf(m.var + 1e-16f);
-  if (threadIdx.x == 0) {
-    float* st = stats + 4 * b;
-    st[0] = m.m1, st[1] = m.m2, st[2] = m.mu, st[3] = sd;
-  }
-  float* o1 = y1 + (long)b * n;
-  float* o2 = y2 + (long)b * n;
-  for (long i = threadIdx.x; i < n4; i += NTS) {
-    const float4 u = reinterpret_cast<const float4*>(p1)[i];
-    const float4 v = reinterpret_cast<const float4*>(p2)[i];
-    reinterpret_cast<float4*>(o1)[i] =
-        make_float4((u.x - m.mu) / sd, (u.y - m.mu) / sd, (u.z - m.mu) / sd, (u.w - m.mu) / sd);
-    reinterpret_cast<float4*>(o2)[i] =
-        make_float4((v.x - m.mu) / sd, (v.y - m.mu) / sd, (v.z - m.mu) / sd, (v.w - m.mu) / sd);
-  }
-  for (long i = 4 * n4 + threadIdx.x; i < n; i += NTS) {
-    o1[i] = (p1[i] - m.mu) / sd;
-    o2[i] = (p2[i] - m.mu) / sd;
-  }
+  const Moments m = featnorm::moments_from_totals(a, n, mode);
+  const float sd = featnorm::sd_of(m);
+  if (threadIdx.x == 0) featnorm::store_stats(stats + 4 * b, m, sd);
+  featnorm::apply_fwd(x1 + o, x2 + o, y1 + o, y2 + o, n, m.mu, sd, threadIdx.x, NTS);
 }
 
 __global__ __launch_bounds__(NTS) void bwd_small_kernel(const float* __restrict__ g1, const float* __restrict__ g2,
@@ -265,58 +168,17 @@ __global__ __launch_bounds__(NTS) void bwd_small_kernel(const float* __restrict_
   __shared__ double scratch[2 * (NTS / 64)];
   __shared__ double tot[2];
   const int b = blockIdx.x;
-  const float* gbp = g1b ? g1b + (long)b * g1b_bs : nullptr;
+  const float* gbp = g1b_of(g1b, g1b_bs, b);
   const float* st = stats + 4 * b;
-  const float mu = st[2];
   const long o = (long)b * n;
-  double s[2] = {0.0, 0.0};
-  const long n4 = (n % 4 == 0) ? n / 4 : 0;
-  for (long i0 = 0; i0 < n4; i0 += 4 * NTS) {
-    float sg = 0.f, sq = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const long i = i0 + (long)k * NTS + threadIdx.x;
-      if (i < n4) {
-        const float4 ga = ld4_sum(g1 + o, gbp, i), xa = reinterpret_cast<const float4*>(x1 + o)[i];
-        const float4 gb = reinterpret_cast<const float4*>(g2 + o)[i], xb = reinterpret_cast<const float4*>(x2 + o)[i];
-        sg += ((ga.x + ga.y) + (ga.z + ga.w)) + ((gb.x + gb.y) + (gb.z + gb.w));
-        sq = fmaf(ga.x, xa.x - mu, fmaf(ga.y, xa.y - mu, fmaf(ga.z, xa.z - mu, fmaf(ga.w, xa.w - mu, sq))));
-        sq = fmaf(gb.x, xb.x - mu, fmaf(gb.y, xb.y - mu, fmaf(gb.z, xb.z - mu, fmaf(gb.w, xb.w - mu, sq))));
-      }
-    }
-    s[0] += (double)sg, s[1] += (double)sq;
-  }
-  for (long i = 4 * n4 + threadIdx.x; i < n; i += NTS) {
-    const float ga = g1[o + i] + (gbp ? gbp[i] : 0.f), gb = g2[o + i];
-    s[0] += (double)ga + (double)gb;
-    s[1] += (double)ga * (double)(x1[o + i] - mu) + (double)gb * (double)(x2[o + i] - mu);
-  }
-  block_sum_f64<2, NTS>(s, scratch);
+  double s[2];
+  featnorm::bwd_partials<NTS>(g1 + o, gbp, g2 + o, x1 + o, x2 + o, st[2], n, 0, 1, s);
+  af_block_sum_f64<2, NTS>(s, scratch);
   if (threadIdx.x == 0) tot[0] = s[0], tot[1] = s[1];
   __syncthreads();
-  const double r = 1.0 / (double)st[3], G = tot[0], Q = tot[1], dn = (double)n;
-  const float rf = (float)r;
-  const float cg = (float)(r * G / (2.0 * dn));
-  const float cq = (float)(mode == ARFLOW_FEATNORM_JOINT ? r * r * r * Q / (2.0 * dn - 1.0) : r * r * r * Q / (2.0 * (dn - 1.0)));
-  const float c1 = mode == ARFLOW_FEATNORM_JOINT ? st[2] : st[0], c2 = mode == ARFLOW_FEATNORM_JOINT ? st[2] : st[1];
-  auto f = [&](float g, float x, float c) { return fmaf(rf, g, -cg) - cq * (x - c); };
-  for (long i = threadIdx.x; i < n4; i += NTS) {
-    if (d1) {
-      const float4 g = ld4_sum(g1 + o, gbp, i), x = reinterpret_cast<const float4*>(x1 + o)[i];
-      reinterpret_cast<float4*>(d1 + o)[i] = make_float4(f(g.x, x.x, c1), f(g.y, x.y, c1), f(g.z, x.z, c1), f(g.w, x.w, c1));
-    }
-    if (d2) {
-      const float4 g = reinterpret_cast<const float4*>(g2 + o)[i], x = reinterpret_cast<const float4*>(x2 + o)[i];
-      reinterpret_cast<float4*>(d2 + o)[i] = make_float4(f(g.x, x.x, c2), f(g.y, x.y, c2), f(g.z, x.z, c2), f(g.w, x.w, c2));
-    }
-  }
-  for (long i = 4 * n4 + threadIdx.x; i < n; i += NTS) {
-    if (d1) d1[o + i] = f(g1[o + i] + (gbp ? gbp[i] : 0.f), x1[o + i], c1);
-    if (d2) d2[o + i] = f(g2[o + i], x2[o + i], c2);
-  }
+  const featnorm::NormBwd nb = featnorm::norm_bwd_coeffs(tot[0], tot[1], st, n, mode);
+  featnorm::apply_bwd(nb, g1 + o, gbp, g2 + o, x1 + o, x2 + o, d1 ? d1 + o : nullptr, d2 ? d2 + o : nullptr, n, threadIdx.x, NTS);
 }
-
-inline unsigned blocks_per_sample(int B, long n, int floats_per_block) { return af_blocks_per_sample(B, n, floats_per_block); }
 
 }  // namespace
 
@@ -336,10 +198,10 @@ extern "C" int arflow_featnorm_fwd(const float* x1, const float* x2, float* y1, 
     hipLaunchKernelGGL(fwd_small_kernel, dim3(B), dim3(NTS), 0, st, x1, x2, y1, y2, stats, n, mode);
     return af_launch_status();
   }
-  const unsigned rows = blocks_per_sample(B, n, NT * VPT);  // rows * B <= 2048 + B: fits ARFLOW_FEATNORM_ACC_DOUBLES(B)
+  const unsigned rows = af_blocks_per_sample(B, n, NT * VPT);  // rows * B <= 2048 + B: fits ARFLOW_FEATNORM_ACC_DOUBLES(B)
   hipLaunchKernelGGL(moment_kernel, dim3(rows, B), dim3(NT), 0, st, x1, x2, acc, n);
   AF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(apply_kernel, dim3(blocks_per_sample(B, n, NT * 4), B), dim3(NT), 0, st, x1, x2, y1, y2, acc, (int)rows,
+  hipLaunchKernelGGL(apply_kernel, dim3(af_blocks_per_sample(B, n, NT * 4), B), dim3(NT), 0, st, x1, x2, y1, y2, acc, (int)rows,
                      stats, n, mode);
   return af_launch_status();
 }
@@ -352,10 +214,10 @@ int af_featnorm_bwd_launch(const float* g1, const float* g1b, long g1b_bs, const
     hipLaunchKernelGGL(bwd_small_kernel, dim3(B), dim3(NTS), 0, st, g1, g2, x1, x2, stats, gx1, gx2, n, mode, g1b, g1b_bs);
     return af_launch_status();
   }
-  const unsigned rows = blocks_per_sample(B, n, NT * VPT);
+  const unsigned rows = af_blocks_per_sample(B, n, NT * VPT);
   hipLaunchKernelGGL(bwd_sum_kernel, dim3(rows, B), dim3(NT), 0, st, g1, g2, x1, x2, stats, acc, n, g1b, g1b_bs);
   AF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bwd_apply_kernel, dim3(blocks_per_sample(B, n, NT * 4), B), dim3(NT), 0, st, g1, g2, x1, x2, stats, acc,
+  hipLaunchKernelGGL(bwd_apply_kernel, dim3(af_blocks_per_sample(B, n, NT * 4), B), dim3(NT), 0, st, g1, g2, x1, x2, stats, acc,
                      (int)rows, gx1, gx2, n, mode, g1b, g1b_bs);
   return af_launch_status();
 }
@@ -375,27 +237,17 @@ extern "C" int arflow_featnorm_bwd(const float* g1, const float* g2, const float
   return af_featnorm_bwd_launch(g1, nullptr, 0, g2, x1, x2, stats, acc, gx1, gx2, B, n, mode, (hipStream_t)stream);
 }
 
-// apply pass alone: the two sums come as rows of 4 doubles ([B][nrows][4]: sum g, sum g (x - mu)) left by the level
-// correlation backward (corr_v2::bwd_kernel<.., SUMS>)
-int af_featnorm_bwd_apply_launch(const float* g1, const float* g1b, long g1b_bs, const float* g2, const float* x1,
-                                 const float* x2, const float* stats, const double* rows, int nrows, float* gx1, float* gx2,
-                                 int B, long n, int mode, hipStream_t st) {
-  hipLaunchKernelGGL(bwd_apply_kernel, dim3(blocks_per_sample(B, n, NT * 4), B), dim3(NT), 0, st, g1, g2, x1, x2, stats, rows,
-                     nrows, gx1, gx2, n, mode, g1b, g1b_bs);
-  return af_launch_status();
-}
-
 // sum pass alone (any n): rows of (sum g, sum g (x - mu)) in `acc`; returns the rows per sample through *nrows
 int af_featnorm_bwd_sums_launch(const float* g1, const float* g1b, long g1b_bs, const float* g2, const float* x1,
                                 const float* x2, const float* stats, double* acc, int* nrows, int B, long n, hipStream_t st) {
-  const unsigned rows = blocks_per_sample(B, n, NT * VPT);
+  const unsigned rows = af_blocks_per_sample(B, n, NT * VPT);
   *nrows = (int)rows;
   hipLaunchKernelGGL(bwd_sum_kernel, dim3(rows, B), dim3(NT), 0, st, g1, g2, x1, x2, stats, acc, n, g1b, g1b_bs);
   return af_launch_status();
 }
 
 int af_featnorm_moments_launch(const float* x1, const float* x2, double* acc, int B, long n, hipStream_t st) {
-  const unsigned rows = blocks_per_sample(B, n, NT * VPT);
+  const unsigned rows = af_blocks_per_sample(B, n, NT * VPT);
   hipLaunchKernelGGL(moment_kernel, dim3(rows, B), dim3(NT), 0, st, x1, x2, acc, n);
   return af_launch_status();
 }

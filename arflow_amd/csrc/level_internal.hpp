@@ -6,9 +6,6 @@
 int af_featnorm_moments_launch(const float* x1, const float* x2, double* acc, int B, long n, hipStream_t st);
 int af_featnorm_bwd_launch(const float* g1, const float* g1b, long g1b_bs, const float* g2, const float* x1, const float* x2,
                            const float* stats, double* acc, float* gx1, float* gx2, int B, long n, int mode, hipStream_t st);
-int af_featnorm_bwd_apply_launch(const float* g1, const float* g1b, long g1b_bs, const float* g2, const float* x1,
-                                 const float* x2, const float* stats, const double* rows, int nrows, float* gx1, float* gx2,
-                                 int B, long n, int mode, hipStream_t st);
 int af_level_warp_fwd_launch(const float* x1, const float* x2, const float* flow, long flow_bstride, int flow_is_coarse,
                              int up_align_corners, float* flow_up, float* flow_up2, long flow_up2_bstride, float* x2w,
                              double* acc, int B, int C, int H, int W, int pad_mode, int align_corners, int norm_mode,

@@ -75,9 +75,7 @@ __global__ __launch_bounds__(NT) void fwd_kernel(FwdArgs a) {
     for (int i = tid; i < C * HW4; i += NT) reinterpret_cast<float4*>(arena)[i] = reinterpret_cast<const float4*>(x2b)[i];
     if (!a.r1)
       for (int i = tid; i < C * HW4; i += NT) {
-        const float4 u = reinterpret_cast<const float4*>(x1b)[i];
-        mom[0] += (u.x + u.y) + (u.z + u.w);
-        mom[1] = fmaf(u.x, u.x, fmaf(u.y, u.y, fmaf(u.z, u.z, fmaf(u.w, u.w, mom[1]))));
+        featnorm::moment_step(reinterpret_cast<const float4*>(x1b)[i], mom[0], mom[1]);
       }
     TapPlan tp[2];
     bool act[2];
@@ -125,17 +123,14 @@ __global__ __launch_bounds__(NT) void fwd_kernel(FwdArgs a) {
         const float v[4] = {s[tp[k].o[0]], s[tp[k].o[1]], s[tp[k].o[2]], s[tp[k].o[3]]};
         const float r = tap_blend(tp[k], v);
         x2wb[(long)c * HW + px] = r;  // every row-shift workgroup writes the same values and reads its own
-        mom[2] += r, mom[3] = fmaf(r, r, mom[3]);
+        featnorm::moment_step(r, mom[2], mom[3]);
       }
     }
     __syncthreads();  // the arena is reused below
   } else if (!(a.r1 && a.r2)) {
     for (int i = tid; i < C * HW4; i += NT) {
-      const float4 u = reinterpret_cast<const float4*>(x1b)[i], v = reinterpret_cast<const float4*>(x2b)[i];
-      mom[0] += (u.x + u.y) + (u.z + u.w);
-      mom[1] = fmaf(u.x, u.x, fmaf(u.y, u.y, fmaf(u.z, u.z, fmaf(u.w, u.w, mom[1]))));
-      mom[2] += (v.x + v.y) + (v.z + v.w);
-      mom[3] = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, mom[3]))));
+      featnorm::moment_step(reinterpret_cast<const float4*>(x1b)[i], mom[0], mom[1]);
+      featnorm::moment_step(reinterpret_cast<const float4*>(x2b)[i], mom[2], mom[3]);
     }
   }
   double dm[4] = {(double)mom[0], (double)mom[1], (double)mom[2], (double)mom[3]};
@@ -149,12 +144,9 @@ __global__ __launch_bounds__(NT) void fwd_kernel(FwdArgs a) {
   if (a.r1) featnorm::sum_rows2(a.r1 + 2L * a.n1 * b, a.n1, ta[0], ta[1]);  // every wave adds the rows itself
   if (!HAS_FLOW && a.r1 && a.r2) featnorm::sum_rows2(a.r2 + 2L * a.n2 * b, a.n2, ta[2], ta[3]);
   const featnorm::Moments m = featnorm::moments_from_totals(ta, (long)C * HW, a.mode);
-  const float sd = sqrtf(m.var + 1e-16f);
+  const float sd = featnorm::sd_of(m);
   const float mu = m.mu, rs = 1.0f / sd;
-  if (blockIdx.y == 0 && tid == 0) {
-    float* st = a.stats + 4 * b;
-    st[0] = m.m1, st[1] = m.m2, st[2] = m.mu, st[3] = sd;
-  }
+  if (blockIdx.y == 0 && tid == 0) featnorm::store_stats(a.stats + 4 * b, m, sd);
 
   // ---------------- pass 2: cost volume of the normalised pair ----------------
   const float* s2b = HAS_FLOW ? x2wb : x2b;

@@ -196,8 +196,8 @@ __device__ __forceinline__ void run_pitch(float* __restrict__ win, const TS* __r
           const float r = tap_blend(p, a);
           op[(long)(c0 + c) * os] = r;
           if (MOM) {
-            mom[0] += xa[c], mom[1] = fmaf(xa[c], xa[c], mom[1]);
-            mom[2] += r, mom[3] = fmaf(r, r, mom[3]);
+            featnorm::moment_step(xa[c], mom[0], mom[1]);
+            featnorm::moment_step(r, mom[2], mom[3]);
           }
         }
       }
@@ -358,8 +358,8 @@ __global__ __launch_bounds__(256) void level_warp_fwd_kernel(const float* __rest
         }
         op[(long)(c + u) * os] = r;
         const float xv = x1p ? x1p[(long)(c + u) * os] : 0.f;
-        mom[0] += xv, mom[1] = fmaf(xv, xv, mom[1]);
-        mom[2] += r, mom[3] = fmaf(r, r, mom[3]);
+        featnorm::moment_step(xv, mom[0], mom[1]);
+        featnorm::moment_step(r, mom[2], mom[3]);
       }
     }
   }
@@ -402,28 +402,13 @@ __device__ __forceinline__ bool taken(int qinfo, int px, int py) {
 namespace flow_grad {
 using fwd_win::HMAX;
 // NB (level backward): `gop` holds the gradient of the NORMALISED warped map; the normalisation's backward
-//     d = r g - r G / N - r^3 Q (x - c) / (N - 1)         (featnorm.hip, bwd_apply_kernel)
+//     d = r g - r G / N - r^3 Q (x - c) / (N - 1)         (featnorm_stats.hpp: NormBwd, norm_bwd_coeffs, norm_bwd_apply)
 // is applied on load -- x, the warped value, is the bilinear sum of the four taps this kernel reads anyway -- so the
 // gradient of the raw warped map is never written; the same pass applies it to the first map's gradient
 // (g1p + gdp, with x1p) and stores d/d x1 (d1p), all at the thread's pixel.
-struct NormBwd {
-  float rf, cg, cq, c1, c2;
-};
-__device__ __forceinline__ NormBwd norm_bwd_coeffs(const double* rows, int nrows, const float* st, long n, int mode) {
-  double gq[2];
-  featnorm::sum_rows<2>(rows, nrows, gq);
-  const double r = 1.0 / (double)st[3], dn = (double)n;
-  NormBwd nb;
-  nb.rf = (float)r;
-  nb.cg = (float)(r * gq[0] / (2.0 * dn));
-  nb.cq = (float)(mode == ARFLOW_FEATNORM_JOINT ? r * r * r * gq[1] / (2.0 * dn - 1.0) : r * r * r * gq[1] / (2.0 * (dn - 1.0)));
-  nb.c1 = mode == ARFLOW_FEATNORM_JOINT ? st[2] : st[0];
-  nb.c2 = mode == ARFLOW_FEATNORM_JOINT ? st[2] : st[1];
-  return nb;
-}
-__device__ __forceinline__ float norm_bwd_apply(const NormBwd& nb, float g, float x, float c) {
-  return fmaf(nb.rf, g, -nb.cg) - nb.cq * (x - c);
-}
+using featnorm::norm_bwd_apply;
+using featnorm::norm_bwd_coeffs;
+using featnorm::NormBwd;
 
 // x, the warped value, summed again from the taps the kernel holds (v from tap_select: a tap outside the source is a zero term)
 __device__ __forceinline__ float warped_value(const TapPlan& p, const float (&v)[4]) {

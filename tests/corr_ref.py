@@ -40,8 +40,9 @@ FEATURE NORMALISATION   (x1, x2: [B, n]; N = 2n; one (mu, var) per sample; sd = 
     joint: dx   = r g - r G / N - r^3 Q (x - mu) / (N - 1)
     avg:   dx_i = r g - r G / N - r^3 Q (x - m_i) / (2 (n - 1))
 
-  What the kernels round.  The longest fp32 partial they form holds k = 16 values per tensor (moment_kernel: 4 float4 per
-  thread and trip; fwd_small_kernel: 4 float4 per thread and trip); from there on everything is double.  The scalar
+  What the kernels round.  The longest fp32 partial they form holds k = 16 values per tensor (moment_kernel and
+  fwd_small_kernel: 4 float4 per thread and trip, featnorm::moment_partials of csrc/featnorm_stats.hpp, which
+  moment_kernel writes out around the same featnorm::moment_step); from there on everything is double.  The scalar
   loops, which replace the float4 loops altogether when n % 4 != 0, convert every value to double before its first
   operation: k = 1, no fp32 rounding at all.  The bounds take k from n % 4 (`partial=`; the CPU test's comparison with the
   fp32 oracle, which has no such path, asks for k = 16 everywhere).  With S = sum |x|, Q2 = sum x^2 and
@@ -260,18 +261,19 @@ def corr_path(B, C, H, W, d):
     return 'general' if d <= 4 else 'generic'
 
 
-FEAT_SMALL_N = 16384  # SMALL_N, csrc/featnorm.hip:195
+FEAT_SMALL_N = 16384  # SMALL_N of csrc/featnorm.hip
 
 
 def feat_rows(B, n, floats_per_block=4096):
-    """(workgroups per sample wanted, allowed): af_blocks_per_sample, csrc/common.hpp:59-64, as featnorm.hip:332 calls it
-    (256 threads x 16 floats per trip)"""
+    """(workgroups per sample wanted, allowed): af_blocks_per_sample of csrc/common.hpp, as arflow_featnorm_fwd
+    (csrc/featnorm.hip) calls it for its moment pass (NT * VPT: 256 threads x 16 floats per trip)"""
     return max(_up(n, floats_per_block), 1), _up(2048, B)
 
 
 def feat_path(B, n):
-    """'small' (one launch, featnorm.hip:328), 'large' or 'capped' (the grid-stride loops of moment_kernel / bwd_sum_kernel
-    take a second trip) + '/v4' or '/scalar' (n % 4: featnorm.hip:43)"""
+    """'small' (one launch: n <= SMALL_N in arflow_featnorm_fwd, featnorm.hip), 'large' or 'capped' (the grid-stride loops of
+    moment_kernel / bwd_sum_kernel take a second trip) + '/v4' or '/scalar' (n % 4: `n4` of featnorm::moment_partials,
+    csrc/featnorm_stats.hpp)"""
     if n <= FEAT_SMALL_N:
         p = 'small'
     else:
@@ -345,7 +347,8 @@ def _dbl(n):
 
 
 def feat_partial(n):
-    """values per tensor in the longest fp32 partial: the float4 loops' 16, or 1 for the scalar loops (featnorm.hip:43-63)"""
+    """values per tensor in the longest fp32 partial: the float4 loops' 16 (featnorm::VPT), or 1 for the scalar loops
+    (featnorm::moment_partials, csrc/featnorm_stats.hpp)"""
     return 16 if n % 4 == 0 else 1
 
 

@@ -16,6 +16,10 @@ Planes (per item): 1x1; 3x5 (under a wave, scalar); 8x8 (one wave, vector); 5x52
 workgroup, vector); 25x41 (1025: past one 1024-pixel chunk, scalar); 32x36 (1152: past one chunk, vector).  Layouts:
 contiguous; channel slices of a tensor one channel wider; a view that starts one float into a larger buffer (the base is
 misaligned, so the scalar kernel must be chosen even where the plane is a multiple of 4).  B = 2 throughout.
+
+Two families have shapes of their own instead of the planes and layouts: `featnorm` (csrc/featnorm.hip on
+every launch path) and `level` (the fused pyramid level, forward and backward); their lines start with the entry point and its
+parameters, and every tensor is dense (`contig`).
 """
 import argparse
 import ctypes
@@ -26,7 +30,8 @@ import sys
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ap.add_argument('--only', default='', help='comma-separated families (lowrank, mixture, band, pyramid, mse, flow_eval, uncert, out_up)')
+ap.add_argument('--only', default='', help='comma-separated families (lowrank, mixture, band, pyramid, mse, flow_eval, uncert, out_up, '
+                'featnorm, level)')
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
 
@@ -69,8 +74,12 @@ ROWS = {}  # (name, params, plane) -> {tensor[shape]: [layout=hash, ...]}, in th
 
 
 def show(name, params, plane, layout, **tensors):
+    show_row('%s %s %dx%d' % (name, params, plane[0], plane[1]), layout, **tensors)
+
+
+def show_row(head, layout, **tensors):
     torch.cuda.synchronize()
-    row = ROWS.setdefault('%s %s %dx%d' % (name, params, plane[0], plane[1]), {})
+    row = ROWS.setdefault(head, {})
     for key, t in tensors.items():
         if t is None:
             continue
@@ -315,12 +324,124 @@ def out_up(plane, layout):
         show('up2_bwd', 'align=%d' % align, plane, layout, gcoarse=gx)
 
 
+# (B, n) of tests/corr_ref.py::FEAT_SHAPES, the smallest that reach each launch path of csrc/featnorm.hip
+FEAT_SHAPES = [(1, 2), (3, 5),  # one workgroup per sample, scalar loops
+               (2, 16384),  # one workgroup per sample, float4 loops, at the threshold
+               (2, 16385), (2, 16388),  # two launches: scalar, float4
+               (512, 20484), (512, 20487)]  # capped grid (a second trip of the grid-stride loops): float4, scalar
+
+
+def featnorm():
+    """arflow_featnorm_fwd / _bwd / arflow_level_moments, both modes; backward with both gradients, gx1 alone, gx2 alone.
+    (The second gradient of y1 that is added on load, g1b, has no stand-alone entry point: the `level` family passes it as
+    gx1n_direct in every backward, and its level without a flow is this backward with g1b.)"""
+    for B, n in FEAT_SHAPES:
+        x1, x2 = (randn(B, n) + 0.3).to(DEV), (randn(B, n, scale=1.5) - 0.2).to(DEV)
+        g1, g2 = randn(B, n).to(DEV), randn(B, n).to(DEV)
+        nacc = 4 * (2048 + B)  # ARFLOW_FEATNORM_ACC_DOUBLES(B)
+        acc = torch.zeros(nacc, device=DEV, dtype=torch.float64)
+        _call('arflow_level_moments', _p(x1), _p(x2), _p(acc), B, n, _stream())
+        show_row('level_moments B=%d,n=%d' % (B, n), 'contig', acc=acc)
+        for mode in (0, 1):
+            head = 'B=%d,n=%d,mode=%d' % (B, n, mode)
+            y1, y2, stats = torch.zeros(B, n, device=DEV), torch.zeros(B, n, device=DEV), torch.zeros(B, 4, device=DEV)
+            acc = torch.zeros(nacc, device=DEV, dtype=torch.float64)
+            _call('arflow_featnorm_fwd', _p(x1), _p(x2), _p(y1), _p(y2), _p(acc), _p(stats), B, n, mode, _stream())
+            show_row('featnorm_fwd ' + head, 'contig', y1=y1, y2=y2, stats=stats, acc=acc)
+            for want in ('both', 'gx1', 'gx2'):
+                d1 = torch.zeros(B, n, device=DEV) if want != 'gx2' else None
+                d2 = torch.zeros(B, n, device=DEV) if want != 'gx1' else None
+                acc = torch.zeros(nacc, device=DEV, dtype=torch.float64)
+                _call('arflow_featnorm_bwd', _p(g1), _p(g2), _p(x1), _p(x2), _p(stats), _p(acc), _p(d1), _p(d2), B, n, mode,
+                      _stream())
+                show_row('featnorm_bwd %s,%s' % (head, want), 'contig', gx1=d1, gx2=d2, acc=acc)
+
+
+# (B, C, H, W) of tests/test_level_gpu.py: one workgroup per sample (twice), tiled with both backward roles in one launch, SPLIT
+LEVEL_SHAPES = [(1, 32, 10, 12), (2, 32, 12, 16), (2, 8, 48, 80), (20, 8, 126, 220)]
+
+
+def level():
+    """arflow_level_fwd / _fwd_m / _warp_fwd + _corr_fwd / _bwd: both modes; a coarse flow, a fine flow, no flow; with and
+    without the moment rows of arflow_bias_act_fwd_mom; backward in deterministic mode (every output) and in the default mode
+    (the outputs that do not pass through float atomics: gx1, and all of them at the level without a flow)."""
+    D, SLOPE, PAD, ALIGN, NORM, UP_ALIGN = 4, 0.1, 0, 1, 0, 1
+    for B, C, H, W in LEVEL_SHAPES:
+        hw, n = H * W, C * H * W
+        x1, x2 = (randn(B, C, H, W) + 0.3).to(DEV), (randn(B, C, H, W) + 0.1).to(DEV)
+        nr = LIB.arflow_bias_act_mom_rows(C, hw)
+        r1, r2 = (torch.zeros(B, nr, 2, device=DEV, dtype=torch.float64) for _ in range(2))
+        for x, r in ((x1, r1), (x2, r2)):  # in place: the maps ARE the outputs whose moments the rows hold
+            _call('arflow_bias_act_fwd_mom', _p(x), None, _p(x), _p(r), B, C, hw, SLOPE, _stream())
+        flows = dict(coarse=randn(B, 2, H // 2, W // 2, scale=1.5).to(DEV), fine=randn(B, 2, H, W, scale=3.0).to(DEV), none=None)
+        ctot = 81 + C + 2
+        bs = ctot * hw
+        gbuf, gext = randn(B, ctot, H, W).to(DEV), randn(B, 2, H, W).to(DEV)
+        for mode in (0, 1):
+            for kind, flow in flows.items():
+                coarse, has_flow = int(kind == 'coarse'), flow is not None
+                fbs = 0 if flow is None else flow[0].numel()
+                nacc = 4 * B * LIB.arflow_level_acc_rows(B, C, H, W, int(has_flow))
+                for rows in (0, 1):
+                    head = '%dx%dx%dx%d mode=%d,flow=%s,rows=%d' % (B, C, H, W, mode, kind, rows)
+                    buf = torch.zeros(B, ctot, H, W, device=DEV)
+                    fup = torch.zeros(B, 2, H, W, device=DEV) if coarse else None
+                    x2w = torch.zeros(B, C, H, W, device=DEV) if has_flow else None
+                    sign = torch.zeros(B, 3, H, W, device=DEV, dtype=torch.int32)
+                    stats = torch.zeros(B, 4, device=DEV)
+                    acc = torch.zeros(nacc, device=DEV, dtype=torch.float64)
+                    common = (_p(x1), _p(x2), _p(flow), fbs, coarse, UP_ALIGN, _p(fup), buf[:, 81 + C:].data_ptr() if coarse else None,
+                              bs, _p(x2w), mode, _p(buf), bs, buf[:, 81:].data_ptr(), bs, _p(sign), _p(stats), _p(acc))
+                    tail = (B, C, H, W, D, SLOPE, PAD, ALIGN, NORM, _stream())
+                    if rows:
+                        _call('arflow_level_fwd_m', *common, _p(r1), nr, None if has_flow else _p(r2), 0 if has_flow else nr, *tail)
+                    else:
+                        _call('arflow_level_fwd', *common, *tail)
+                    show_row('level_fwd ' + head, 'contig', buf=buf, flow_up=fup, x2w=x2w, sign=sign, stats=stats, acc=acc)
+                    fl = fup if coarse else flow
+                    for det in (1, 0):
+                        prev = LIB.arflow_set_deterministic(det)
+                        ws = torch.zeros(LIB.arflow_level_bwd_ws_bytes(B, C, H, W) + 256, device=DEV, dtype=torch.uint8)
+                        wp = (ws.data_ptr() + 255) & ~255
+                        gx1, gx2 = torch.zeros(B, C, H, W, device=DEV), torch.zeros(B, C, H, W, device=DEV)
+                        gflow = torch.zeros_like(flow) if has_flow else None
+                        _call('arflow_level_bwd', _p(gbuf), bs, _p(sign), buf[:, 81:].data_ptr(), bs, gbuf[:, 81:].data_ptr(), bs,
+                              _p(x1), _p(x2), _p(x2w), _p(fl), 2 * hw, gbuf[:, 81 + C:].data_ptr() if coarse else None, bs,
+                              _p(gext) if coarse else None, _p(stats), mode, _p(gx1), _p(gx2), _p(gflow), coarse, UP_ALIGN, wp,
+                              *tail)
+                        torch.cuda.synchronize()
+                        LIB.arflow_set_deterministic(prev)
+                        keep = det or not has_flow
+                        show_row('level_bwd %s,det=%d' % (head, det), 'contig', gx1=gx1, gx2=gx2 if keep else None,
+                                 gflow=gflow if keep else None)
+                if not has_flow:
+                    continue
+                # the two stages on their own (always the tiled kernels)
+                head = '%dx%dx%dx%d mode=%d,flow=%s' % (B, C, H, W, mode, kind)
+                fup = torch.zeros(B, 2, H, W, device=DEV) if coarse else None
+                x2w, acc = torch.zeros(B, C, H, W, device=DEV), torch.zeros(nacc, device=DEV, dtype=torch.float64)
+                _call('arflow_level_warp_fwd', _p(x1), _p(x2), _p(flow), fbs, coarse, UP_ALIGN, _p(fup), None, 0, _p(x2w), _p(acc),
+                      B, C, H, W, PAD, ALIGN, NORM, _stream())
+                show_row('level_warp_fwd ' + head, 'contig', flow_up=fup, x2w=x2w, acc=acc)
+                out, x1n = torch.zeros(B, 81, H, W, device=DEV), torch.zeros(B, C, H, W, device=DEV)
+                sign, stats = torch.zeros(B, 3, H, W, device=DEV, dtype=torch.int32), torch.zeros(B, 4, device=DEV)
+                _call('arflow_level_corr_fwd', _p(x1), _p(x2w), _p(acc), nacc // (4 * B), mode, _p(out), 81 * hw, _p(x1n), n, _p(sign),
+                      _p(stats), B, C, H, W, D, SLOPE, _stream())
+                show_row('level_corr_fwd ' + head, 'contig', out=out, x1n=x1n, sign=sign, stats=stats)
+
+
 FAMILIES = dict(lowrank=lowrank, mixture=mixture, band=band, pyramid=pyramid, mse=mse, flow_eval=flow_eval, uncert=uncert,
                 out_up=out_up)
+# families with shapes of their own (the launch paths of the feature normalisation and of the fused pyramid level, DESIGN.md
+# section 43): run once, dense tensors
+SHAPED = dict(featnorm=featnorm, level=level)
 
 if __name__ == '__main__':
-    only = [f for f in args.only.split(',') if f] or list(FAMILIES)
+    only = [f for f in args.only.split(',') if f] or list(FAMILIES) + list(SHAPED)
     for fam in only:
+        if fam in SHAPED:
+            SHAPED[fam]()
+            continue
         for plane in PLANES:
             for layout in LAYOUTS:
                 FAMILIES[fam](plane, layout)
