@@ -144,6 +144,12 @@ PROTOTYPES = {
     'arflow_ar_loss_partials': [c_i, c_i, c_i],
     'arflow_ar_loss_fwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_f, c_f, c_fp],
     'arflow_ar_loss_bwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_f, c_f, c_fp],
+    'arflow_census_residual': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_em_partials': [c_l],
+    'arflow_em_stats': [c_fp, c_fp, c_l, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_fp],
+    'arflow_em_fold': [c_fp, c_i, c_i, c_fp, c_fp],
+    'arflow_log_gmm_fwd': [c_fp, c_l, c_i, c_fp, c_fp, c_i, c_fp, c_fp],
+    'arflow_log_gmm_bwd': [c_fp, c_fp, c_l, c_i, c_fp, c_fp, c_i, c_fp, c_fp],
     'arflow_uncert_rows': [c_i, c_i],
     'arflow_uncert_prep': [c_fp, c_fp, c_fp, c_l, c_fp, c_fp, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_sparsify_sums': [c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp],

@@ -34,6 +34,35 @@ __device__ __forceinline__ void load_gray_tile(float (*tile)[TX + 2 * R + 1], co
   }
 }
 
+// census_loss_no_penalty (utils/uflow_utils.py:296-306) of one pixel: the soft distance before abs_robust_loss and the
+// border-zeroed mask, stored as they are (no sums; the caller normalises the mask).  Forward only.
+template <int R>
+__global__ __launch_bounds__(TX* TY) void census_residual_kernel(const float* __restrict__ im_a, const float* __restrict__ im_b,
+                                                                 const float* __restrict__ mask, float* __restrict__ ham_out,
+                                                                 float* __restrict__ pmask_out, int nimg, int H, int W) {
+  __shared__ float ga[TY + 2 * R][TX + 2 * R + 1];
+  __shared__ float gb[TY + 2 * R][TX + 2 * R + 1];
+  int btx_, bty_, b;
+  if (!af_tile_of_block((W + TX - 1) / TX, (H + TY - 1) / TY, nimg, btx_, bty_, b)) return;
+  const int ty0 = bty_ * TY, tx0 = btx_ * TX;
+  const long ims = 3L * H * W;
+  load_gray_tile<R>(ga, im_a + b * ims, H, W, ty0, tx0);
+  load_gray_tile<R>(gb, im_b + b * ims, H, W, ty0, tx0);
+  __syncthreads();
+  const int lx = threadIdx.x % TX, ly = threadIdx.x / TX;
+  const int x = tx0 + lx, y = ty0 + ly;
+  if (x >= W || y >= H) return;
+  const float ca = ga[ly + R][lx + R], cb = gb[ly + R][lx + R];
+  float s = 0.f;
+#pragma unroll
+  for (int dy = 0; dy <= 2 * R; ++dy)
+#pragma unroll
+    for (int dx = 0; dx <= 2 * R; ++dx) s = pair_dist_acc_exact0(ca, cb, ga[ly + dy][lx + dx], gb[ly + dy][lx + dx], s);
+  const long o = ((long)b * H + y) * W + x;
+  ham_out[o] = s;
+  pmask_out[o] = interior(y, x, H, W, R) ? mask[o] : 0.f;
+}
+
 // ham = sum_k sq/(0.1+sq); optional fused census_loss partial sums.
 template <int R>
 __global__ __launch_bounds__(TX* TY) void census_fwd_kernel(const float* __restrict__ im_a,
@@ -311,3 +340,19 @@ extern "C" int arflow_census_bwd(const float* im_a, const float* im_b, const flo
   return af_launch_status();
 }
 
+extern "C" int arflow_census_residual(const float* im_a, const float* im_b, const float* mask, float* ham, float* pmask, int B,
+                                      int H, int W, int radius, arflow_stream_t stream) {
+  af_clear_stale_error();
+  AF_REQUIRE_PTR(im_a);
+  AF_REQUIRE_PTR(im_b);
+  AF_REQUIRE_PTR(mask);
+  AF_REQUIRE_PTR(ham);
+  AF_REQUIRE_PTR(pmask);
+  AF_REQUIRE(B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 8 * 65535, ARFLOW_ESHAPE);
+  AF_REQUIRE(radius >= 1 && radius <= 3, ARFLOW_EPARAM);
+  af_dispatch_radius(radius, [&](auto R) {
+    hipLaunchKernelGGL(census_residual_kernel<decltype(R)::value>, dim3(scalar_grid(B, H, W)), dim3(TX * TY), 0,
+                       (hipStream_t)stream, im_a, im_b, mask, ham, pmask, B, H, W);
+  });
+  return af_launch_status();
+}

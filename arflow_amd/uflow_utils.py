@@ -78,3 +78,26 @@ def robust_l1(x):
 def census_loss(image_a, image_b, mask, patch_size=7):
     """utils/uflow_utils.py:282-293 -- fused forward / backward kernels."""
     return AF.CensusLossFunction.apply(image_a, image_b, mask.detach(), patch_size)
+
+
+def census_loss_no_penalty(image_a, image_b, mask, patch_size=7):
+    """utils/uflow_utils.py:296-306 -- (soft Hamming map [B,1,H,W], border-zeroed mask / (its sum + 1e-6)), one forward-only
+    launch.  The outputs are detached: the EM penalty fit reads them (arflow_amd.penalty_em); training goes through the fused
+    loss paths instead."""
+    for t in (image_a, image_b, mask):
+        if t.requires_grad:
+            raise ValueError('census_loss_no_penalty is forward only (an input requires grad): to train through the census '
+                             'distance use the fused loss paths census_loss / AF.CensusWarpLossFunction / UFlowElboLoss')
+    AF._need_gpu(image_a, image_b, mask)
+    image_a, image_b, mask = image_a.contiguous(), image_b.contiguous(), mask.contiguous()
+    B, C, H, W = image_a.shape
+    if C != 3 or image_b.shape != image_a.shape or mask.shape != (B, 1, H, W):
+        raise ValueError('census_loss_no_penalty expects [B,3,H,W] images and a [B,1,H,W] mask')
+    r = int(patch_size) // 2
+    if not 1 <= r <= 3:
+        raise NotImplementedError('census_loss_no_penalty: patch_size {} not implemented (3, 5 or 7)'.format(patch_size))
+    ham, pmask = torch.empty_like(mask), torch.empty_like(mask)
+    with torch.cuda.device_of(image_a):
+        AF._call('arflow_census_residual', AF._p(image_a), AF._p(image_b), AF._p(mask), AF._p(ham), AF._p(pmask), B, H, W, r,
+                 AF._stream(), key=(B, H, W))
+    return ham, pmask / (torch.sum(pmask) + 1e-6)

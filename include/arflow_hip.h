@@ -1015,6 +1015,44 @@ int arflow_ar_loss_fwd(const float* pred, const float* flow_t, const float* mask
 int arflow_ar_loss_bwd(const float* pred, const float* flow_t, const float* mask, const double* gsums, float* gpred, int B,
                        int H, int W, float eps, float q, arflow_stream_t stream);
 
+/* census_loss_no_penalty (utils/uflow_utils.py:296-306), forward only: ham [B,1,H,W] = the soft census distance of every pixel
+ * (the arithmetic of arflow_census_fwd's 32 x 8 kernel: an image compared with itself gives exactly 0), pmask [B,1,H,W] = mask
+ * with a border of `radius` pixels zeroed (zero_mask_border).  im_a, im_b [B,3,H,W], mask [B,1,H,W], all dense; any H, W;
+ * radius 1 .. 3 (else ARFLOW_EPARAM).  The caller divides pmask by its sum. */
+int arflow_census_residual(const float* im_a, const float* im_b, const float* mask, float* ham, float* pmask, int B, int H,
+                           int W, int radius, arflow_stream_t stream);
+
+/* ---- EM fit of the Gaussian-mixture penalty and its log-density (csrc/penalty_em.hip) ----
+ * train_penalty_em.py:86-220 (class EM) without the m x k responsibility matrix: ONE pass over the samples forms the
+ * responsibilities of a sample in registers and keeps four sums per component.
+ * arflow_em_stats: x0 [m] samples, float32 (is_f64 = 0) or float64 (1); x1 [m] weights of the same type, or NULL for ones;
+ *   logw, beta, mu [k] float64 ON THE DEVICE, 1 <= k <= ARFLOW_EM_KMAX, logw_j = digamma(alpha_bar_j) - digamma(sum alpha_bar) +
+ *   log(beta_j) / 2.  In float64 per sample: a_j = -beta_j (x - mu_j)^2 / 2 + logw_j, c = max a, e_j = exp(a_j - c), den = sum e,
+ *   xi_j = e_j / den, log xi_j = a_j - c - log(den).  part [arflow_em_partials(m)][4][k] float64, one row per workgroup, every
+ *   element stored: S0_j = sum x1 xi_j, S1_j = sum x1 xi_j x, S2_j = sum x1 xi_j (x - mu_j)^2, H_j = sum x1 xi_j log xi_j.
+ *   No atomics, no zero-fill: two calls give the same bits in either mode.  Workgroup b takes the samples [b s, (b + 1) s), s a
+ *   multiple of ARFLOW_EM_UNIT chosen so that there are at most ARFLOW_EM_MAX_PARTS workgroups.
+ * arflow_em_partials: the row count, or ARFLOW_ESHAPE for m < 1; needs no GPU.
+ * arflow_em_fold: stats [4][k] = the nparts rows of part added in index order to 0.0.
+ * arflow_log_gmm_fwd: out_i = log sum_j w_j exp(-beta_j x_i^2 / 2) as c + log(sum_j w_j exp(arg_j - c)), c = max_j arg_j
+ *   (losses/uflow_elbo_loss.py:99-105 with w_j = pi_j sqrt(beta_j) / sqrt(2 pi)); x, out [n] dense, float32 or float64, computed
+ *   in that type; w, beta [k] float64 ON THE DEVICE.  arflow_log_gmm_bwd: gx_i = gout_i * -(sum_j r_j beta_j) x_i with r the
+ *   posterior weights, recomputed from x.
+ *
+ * ARFLOW_ENULL: a required pointer is NULL (x1 may be);  ARFLOW_ESHAPE: m or n < 1, nparts outside 1 .. ARFLOW_EM_MAX_PARTS;
+ * ARFLOW_EPARAM: k outside 1 .. ARFLOW_EM_KMAX, is_f64 not 0 / 1, a pointer off its element's alignment. */
+#define ARFLOW_EM_KMAX 16
+#define ARFLOW_EM_UNIT 1024
+#define ARFLOW_EM_MAX_PARTS 1024
+int arflow_em_partials(long m);
+int arflow_em_stats(const void* x0, const void* x1, long m, int is_f64, const double* logw, const double* beta, const double* mu,
+                    int k, double* part, arflow_stream_t stream);
+int arflow_em_fold(const double* part, int nparts, int k, double* stats, arflow_stream_t stream);
+int arflow_log_gmm_fwd(const void* x, long n, int is_f64, const double* w, const double* beta, int k, void* out,
+                       arflow_stream_t stream);
+int arflow_log_gmm_bwd(const void* x, const void* gout, long n, int is_f64, const double* w, const double* beta, int k, void* gx,
+                       arflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ fraction of the 8 TB/s HBM roofline.  Calls the C ABI directly (no autograd over
     python tools/kbench.py --filter augment        # the batch augmentation, fused against composed ATen ops
     python tools/kbench.py --filter optim          # the fused optimiser step against torch.optim.Adam(fused=True)
     python tools/kbench.py --filter ar             # the AR transform and loss, fused against composed ATen ops
+    python tools/kbench.py --filter penalty_em     # one EM update of the penalty fit and log_gmm against their torch formulations
 """
 import argparse
 import json
@@ -842,6 +843,107 @@ def optim_bench(dev, jsonl, launches=20, repeats=5):
             out.write(json.dumps(line) + '\n')
 
 
+def penalty_em_bench(dev, jsonl, m=3000000, init_vars=None, launches=20, repeats=5):
+    """one EM.update() at the script's size (m = 3e6 fp32 samples, k = 10, x1 = 1) on the fused pass
+    (arflow_em_stats + arflow_em_fold + the k-sized torch ops) next to the reference's formulation -- the methods of class EM of
+    train_penalty_em.py transcribed here as torch float64 device ops, the m x k matrix xi materialised -- and log_gmm forward +
+    backward at 8 x 1 x 384 x 640 (fp32) next to its torch composition.  HIP events around `launches` calls after 5 warm-ups, the
+    legs in alternation, `repeats` rounds: median (min .. max).  Algorithmic bytes: the update reads x0 and x1 once (8 m); log_gmm
+    reads x twice and the upstream gradient once and writes out and gx (5 x 4 n).  `pass` is update_xi's two launches alone: the
+    difference to `fused` is the k-sized torch ops (digamma, lgamma, the M-step, the objective: launch-bound)."""
+    import math
+    import statistics
+    from arflow_amd import penalty_em as P
+    init_vars = list(P.INIT_VARS) if init_vars is None else init_vars
+    k = len(init_vars)
+    cpu = torch.Generator().manual_seed(0)
+    scale = torch.tensor([0.05, 0.5, 3.0])[torch.arange(m) % 3]
+    x0 = (torch.randn(m, generator=cpu) * scale).to(dev)
+    x1 = torch.ones_like(x0)
+
+    class TorchEM:  # the reference's EM, its operations in its order, float64 on the device
+        def __init__(self):
+            f64 = dict(device=dev, dtype=torch.float64)
+            self.alpha, self.mu_0, self.beta_0, self.a, self.b = torch.ones(k, **f64), 0, 1e-3, 1, 1
+            self.mu, self.beta = torch.zeros(k, **f64), 1 / torch.tensor(init_vars, **f64)
+            self.alpha_bar = self.alpha.clone()
+
+        def update(self, x):
+            x0, x1 = x[0].double(), x[1].double()
+            log_pi = torch.special.digamma(self.alpha_bar) - torch.special.digamma(torch.sum(self.alpha_bar, dim=0, keepdim=True))
+            arg = -self.beta[None, :] * ((x0[:, None] - self.mu[None, :]) ** 2) / 2 + log_pi[None, :]
+            num = torch.sqrt(self.beta)[None, :] * torch.exp(arg - torch.max(arg, dim=1, keepdim=True).values)
+            xi = num / torch.sum(num, dim=1, keepdim=True)
+            self.alpha_bar = self.alpha + torch.sum(x1[:, None] * xi, dim=0)
+            self.pi = self.alpha_bar / torch.sum(self.alpha_bar, dim=0, keepdim=True)
+            num = 2 * self.a - 1 + torch.sum(xi * x1[:, None], dim=0)
+            den = 2 * self.b + self.beta_0 * (self.mu - self.mu_0) ** 2 + torch.sum(xi * x1[:, None] * (x0[:, None] - self.mu[None, :]) ** 2, dim=0)
+            self.beta = num / den
+            sum_i = torch.sum(xi * x1[:, None] * (torch.log(self.beta)[None, :] - math.log(2 * math.pi)
+                              - self.beta[None, :] * (x0[:, None] - self.mu[None, :]) ** 2) / 2 - x1[:, None] * torch.xlogy(xi, xi), dim=0)
+            sum_j = torch.sum((self.a - 1 / 2) * torch.log(self.beta) - (self.beta_0 * self.beta * (self.mu - self.mu_0) ** 2) / 2
+                              - self.b * self.beta + sum_i)
+            return sum_j + torch.sum(torch.lgamma(self.alpha_bar)) - torch.lgamma(torch.sum(self.alpha_bar))
+
+    def one_update(cls, x):
+        def run():
+            em = cls()  # every call starts from the initial state: the same arithmetic each time
+            return em.update(x), em.beta
+        return run
+    fused_em = lambda: P.EM(k=k, init_vars=init_vars, device=dev)  # noqa: E731
+    em0 = fused_em()
+    logw0 = em0._logw().contiguous()
+    # `pass`: the two launches of update_xi alone (arflow_em_stats + arflow_em_fold), without the k-sized torch ops around them
+    legs = {'fused': one_update(fused_em, [x0, None]), 'fused_x1': one_update(fused_em, [x0, x1]), 'torch': one_update(TorchEM, [x0, x1]),
+            'pass': lambda: P.em_stats(x0, None, logw0, em0.beta, em0.mu), 'pass_x1': lambda: P.em_stats(x0, x1, logw0, em0.beta, em0.mu)}
+    n = 8 * 1 * 384 * 640
+    lx = (3.0 * torch.randn(8, 1, 384, 640, generator=cpu)).to(dev)
+    pi = torch.full((k,), 1.0 / k, dtype=torch.float64)
+    beta = 1 / torch.tensor(init_vars, dtype=torch.float64)
+
+    def torch_log_gmm(x):
+        p, b = pi.to(x.device, x.dtype), beta.to(x.device, x.dtype)
+        arg = -b * torch.square(x).unsqueeze(-1) / 2
+        w = p * torch.sqrt(b) / math.sqrt(2 * math.pi)
+        c = torch.max(arg, dim=-1).values
+        return c + torch.log(torch.sum(w * torch.exp(arg - c.unsqueeze(-1)), dim=-1))
+
+    def node(fn):
+        def run():
+            x = lx.clone().requires_grad_(True)
+            fn(x).sum().backward()
+            return x.grad
+        return run
+    lg_legs = {'fused': node(lambda x: P.log_gmm(x, pi, beta)), 'torch': node(torch_log_gmm)}
+    with open(jsonl, 'a') as out:
+        for bench, fns, nbytes, extra in (('update', legs, 8 * m, {'m': m, 'k': k, 'partials': -(-m // P.em_share(m))}),
+                                          ('log_gmm fwd+bwd', lg_legs, 20 * n, {'shape': [8, 1, 384, 640], 'k': k})):
+            a, b = fns['fused'](), fns['torch']()
+            if bench == 'update':
+                diff = max(abs(float(a[0]) - float(b[0])) / abs(float(b[0])), float(((a[1] - b[1]).abs() / b[1]).max()))
+            else:
+                diff = float((a - b).abs().max())
+            del a, b
+            t = {name: [] for name in fns}
+            for _ in range(repeats):
+                for name, fn in fns.items():
+                    t[name].append(timeit(fn, launches))
+                    MANIFEST[-1].update(name='penalty_em/%s/%s' % (bench, name), shape=[])
+            line = dict({'bench': 'penalty_em', 'case': bench, 'algorithmic_bytes': nbytes, 'launches': launches, 'rounds': repeats,
+                         'max_diff_fused_vs_torch': diff}, **extra)
+            for name, v in t.items():
+                line.update({name + '_us': statistics.median(v), name + '_us_min': min(v), name + '_us_max': max(v)})
+                print('penalty_em %-16s %-9s %9.1f us (%.1f .. %.1f)' % (bench, name, statistics.median(v), min(v), max(v)), flush=True)
+            gbs = nbytes / line['fused_us'] / 1e3
+            line.update(fused_gbs=gbs, fused_fraction_of_hbm_peak=gbs / HBM_PEAK_GBS, torch_over_fused=line['torch_us'] / line['fused_us'])
+            if bench == 'update':  # the pass alone: bytes per second and float64 exp evaluations per nanosecond (k per sample)
+                line.update(pass_gbs=4 * m / line['pass_us'] / 1e3, pass_x1_gbs=8 * m / line['pass_x1_us'] / 1e3,
+                            pass_exp_per_ns=k * m / line['pass_us'] / 1e3)
+            print('penalty_em %-16s torch / fused = %.2f   fused %.0f GB/s = %.1f%% of HBM peak   (difference %.1e)'
+                  % (bench, line['torch_over_fused'], gbs, 100 * gbs / HBM_PEAK_GBS, diff), flush=True)
+            out.write(json.dumps(line) + '\n')
+
+
 def main():
     if os.environ.get('ARFLOW_LIB_PATH'):  # an alternative build of the library (A/B timing; tools only)
         _lib.LIB_PATH = os.environ['ARFLOW_LIB_PATH']
@@ -851,8 +953,9 @@ def main():
     ap.add_argument('--levels', default='uflow')
     ap.add_argument('--batch', type=int, default=16, help='model-side batch (2B: both directions stacked)')
     ap.add_argument('--size', type=int, nargs=2, default=[384, 640])
-    ap.add_argument('--jsonl', default='', help='--filter augment, optim and ar append their result lines here '
-                    '(default: profiles/augment_kbench.jsonl, profiles/optim_kbench.jsonl, profiles/ar_kbench.jsonl)')
+    ap.add_argument('--jsonl', default='', help='--filter augment, optim, ar and penalty_em append their result lines here '
+                    '(default: profiles/augment_kbench.jsonl, profiles/optim_kbench.jsonl, profiles/ar_kbench.jsonl, '
+                    'profiles/penalty_em_kbench.jsonl)')
     ap.add_argument('--manifest', default='', help='write the ordered (name, shape, calls) list of the timed ops here')
     args = ap.parse_args()
     lib = _lib.load()
@@ -1348,6 +1451,8 @@ def main():
         optim_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'optim_kbench.jsonl'))
     if want('ar'):  # the AR transform and loss (csrc/ar.hip) against the same arithmetic composed of ATen operations
         ar_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'ar_kbench.jsonl'))
+    if want('penalty_em'):  # one EM update and log_gmm (csrc/penalty_em.hip) against the reference's formulation in torch ops
+        penalty_em_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'penalty_em_kbench.jsonl'))
     if args.manifest:
         json.dump(MANIFEST, open(args.manifest, 'w'), indent=1)
     if not rows:  # only ops that keep their own byte model (the head convolutions) were selected
