@@ -150,6 +150,11 @@ PROTOTYPES = {
     'arflow_em_fold': [c_fp, c_i, c_i, c_fp, c_fp],
     'arflow_log_gmm_fwd': [c_fp, c_l, c_i, c_fp, c_fp, c_i, c_fp, c_fp],
     'arflow_log_gmm_bwd': [c_fp, c_fp, c_l, c_i, c_fp, c_fp, c_i, c_fp, c_fp],
+    'arflow_census_warp_pen_fwd': [c_fp, c_fp, c_fp, c_l, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_l, c_fp, c_fp],
+    'arflow_census_warp_pair_pen_fwd': [c_fp, c_fp, c_l, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_l, c_fp, c_fp],
+    'arflow_census_pen_fwd': [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp],
+    'arflow_smooth_pen_fwd': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_l, c_f, c_f, c_i, c_i, c_fp, c_fp],
+    'arflow_smooth_pen_bwd': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_l, c_f, c_f, c_i, c_i, c_fp, c_fp],
     'arflow_uncert_rows': [c_i, c_i],
     'arflow_uncert_prep': [c_fp, c_fp, c_fp, c_l, c_fp, c_fp, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fp],
     'arflow_sparsify_sums': [c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp],
@@ -159,6 +164,14 @@ PROTOTYPES = {
 
 ABI_VERSION = 10
 _lib = None
+
+# arflow_penalty_t and the ARFLOW_PEN_* kinds of include/arflow_hip.h
+PEN_IDENTITY, PEN_CHARBONNIER, PEN_ABS_ROBUST, PEN_GMM, PEN_GMM_SQ = range(5)
+PEN_KMAX = 16  # ARFLOW_EM_KMAX
+
+
+class Penalty(ctypes.Structure):
+    _fields_ = [('kind', c_i), ('k', c_i), ('w', c_f * PEN_KMAX), ('beta', c_f * PEN_KMAX)]
 
 
 class ArflowHipError(RuntimeError):

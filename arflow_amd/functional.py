@@ -1962,6 +1962,197 @@ def census_warp_loss(gray_a, gray_b, flow, occ_small, patch_size=7):
     return CensusWarpLossFunction.apply(gray_a, gray_b, flow, occ_small, patch_size)
 
 
+# ---- selectable penalties (csrc/penalty_dev.hpp) -------------------------------------------------
+PEN_KINDS = {'identity': _lib.PEN_IDENTITY, 'charbonnier': _lib.PEN_CHARBONNIER, 'abs_robust_loss': _lib.PEN_ABS_ROBUST}
+
+
+def make_penalty(name, pi=None, beta=None, squared=False):
+    """The host descriptor (arflow_penalty_t) of a penalty: 'identity', 'charbonnier', 'abs_robust_loss', or 'gmm' with the
+    mixture (pi, beta) -- the data-term form rho(h), or with squared=True the smoothness form rho(x^2).  The weights
+    w_j = pi_j sqrt(beta_j) / sqrt(2 pi) are formed in float64 and rounded to fp32 once, like beta_j."""
+    import math
+    d = _lib.Penalty()
+    if name in PEN_KINDS:
+        d.kind, d.k = PEN_KINDS[name], 0
+        return d
+    if name != 'gmm':
+        raise ValueError('penalty %r (known: identity, charbonnier, abs_robust_loss, gmm)' % (name,))
+    from .losses.penalty_functions import check_mixture  # (imported here: that module builds on this one)
+    pi, beta = check_mixture(pi, beta, "penalty 'gmm'")
+    d.kind, d.k = (_lib.PEN_GMM_SQ if squared else _lib.PEN_GMM), len(pi)
+    for j, (p, b) in enumerate(zip(pi, beta)):
+        d.w[j] = p * math.sqrt(b) / math.sqrt(2.0 * math.pi)
+        d.beta[j] = b
+    return d
+
+
+def _pen_ptr(pen):
+    import ctypes
+    return ctypes.addressof(pen)
+
+
+class CensusPenLossFunction(torch.autograd.Function):
+    """CensusLossFunction with the penalty `pen` (make_penalty) in place of abs_robust_loss: arflow_census_pen_fwd; the
+    backward is CensusLossFunction's (arflow_census_bwd reads dham = pm rho'(ham))."""
+
+    @staticmethod
+    def forward(ctx, im_a, im_b, mask, patch_size, pen):
+        _need_gpu(im_a, im_b, mask)
+        im_a, im_b, mask = im_a.contiguous(), im_b.contiguous(), mask.contiguous()
+        B, C, H, W = im_a.shape
+        if C != 3 or im_b.shape != im_a.shape or mask.shape != (B, 1, H, W):
+            raise ValueError('census_pen_loss expects [B,3,H,W] images and a [B,1,H,W] mask')
+        r = int(patch_size) // 2
+        buf = _new_sums(im_a.device, B, H, W)
+        ham = torch.empty(B, 1, H, W, device=im_a.device, dtype=torch.float32)
+        dham = torch.empty(B, 1, H, W, device=im_a.device, dtype=torch.float32)
+        with torch.cuda.device_of(im_a):
+            _call('arflow_census_pen_fwd', _p(im_a), _p(im_b), _p(mask), _p(ham), _p(dham), _p(buf), B, H, W, r, _pen_ptr(pen),
+                  _stream(), key=(B, H, W))
+        sums = _fold_sums(buf, 2)
+        den = _ddp.global_denominator(sums[1]) + 1e-6 / _ddp.world_size()
+        inv = 1.0 / den
+        ctx.save_for_backward(im_a, im_b, dham, inv)
+        ctx.r = r
+        return sums[0] * inv
+
+    @staticmethod
+    def backward(ctx, gloss):
+        return CensusLossFunction.backward(ctx, gloss) + (None,)
+
+
+def census_pen_loss(im_a, im_b, mask, pen, patch_size=7):
+    return CensusPenLossFunction.apply(im_a, im_b, mask, patch_size, pen)
+
+
+def _valid_view(valid_flow, shape):
+    if valid_flow is None:
+        return None, 0
+    valid_flow, vbs = _flow_view(valid_flow.detach())
+    _need_gpu(valid_flow)
+    if valid_flow.shape != shape:
+        raise ValueError('valid_flow must have the shape of the flow')
+    return valid_flow, vbs
+
+
+class CensusWarpPenLossFunction(torch.autograd.Function):
+    """CensusWarpLossFunction with the penalty `pen` and an optional validity flow (mask_invalid is taken of `valid_flow`
+    while the warp samples at `flow`): arflow_census_warp_pen_fwd; backward arflow_census_warp_bwd, as there."""
+
+    @staticmethod
+    def forward(ctx, gray_a, gray_b, flow, occ_small, patch_size, pen, valid_flow):
+        _need_gpu(gray_a, gray_b, flow, occ_small)
+        gray_a, gray_b = gray_a.detach().contiguous(), gray_b.detach().contiguous()
+        flow, fbs = _flow_view(flow)
+        B, C, H, W = gray_a.shape
+        if C != 1 or gray_b.shape != gray_a.shape or flow.shape != (B, 2, H, W):
+            raise ValueError('census_warp_pen_loss expects [B,1,H,W] grey planes and a [B,2,H,W] flow')
+        if occ_small is not None:
+            occ_small = occ_small.detach().contiguous()
+            if occ_small.shape != (B, 1, H // 4, W // 4):
+                raise ValueError('occ_small must be the [B,1,H/4,W/4] range map')
+        valid_flow, vbs = _valid_view(valid_flow, flow.shape)
+        r = int(patch_size) // 2
+        buf = _new_sums(gray_a.device, B, H, W)
+        dham = torch.empty(B, 1, H, W, device=gray_a.device, dtype=torch.float32)
+        mask = torch.empty(B, 1, H, W, device=gray_a.device, dtype=torch.float32)
+        with torch.cuda.device_of(gray_a):
+            _call('arflow_census_warp_pen_fwd', _p(gray_a), _p(gray_b), _p(flow), fbs, _p(occ_small), _p(mask), _p(dham),
+                  _p(buf), B, H, W, r, _p(valid_flow), vbs, _pen_ptr(pen), _stream(), key=(B, H, W))
+        sums = _fold_sums(buf, 2)
+        den = _ddp.global_denominator(sums[1]) + 1e-6 / _ddp.world_size()
+        inv = 1.0 / den
+        ctx.save_for_backward(gray_a, gray_b, flow, dham, inv)
+        ctx.r, ctx.fbs = r, fbs
+        ctx.mark_non_differentiable(mask)
+        return sums[0] * inv, mask
+
+    @staticmethod
+    def backward(ctx, gloss, gmask_unused):
+        return CensusWarpLossFunction.backward(ctx, gloss, gmask_unused) + (None, None)
+
+
+def census_warp_pen_loss(gray_a, gray_b, flow, occ_small, pen, valid_flow=None, patch_size=7):
+    return CensusWarpPenLossFunction.apply(gray_a, gray_b, flow, occ_small, patch_size, pen, valid_flow)
+
+
+class CensusWarpPairPenLossFunction(torch.autograd.Function):
+    """CensusWarpPairLossFunction with the penalty `pen` and an optional validity flow: arflow_census_warp_pair_pen_fwd;
+    backward arflow_census_warp_pair_bwd, as there."""
+
+    @staticmethod
+    def forward(ctx, gray2, flow2, occ_small2, patch_size, pen, valid_flow2):
+        _need_gpu(gray2, flow2, occ_small2)
+        gray2 = gray2.detach().contiguous()
+        flow2, fbs = _flow_view(flow2)
+        B2, C, H, W = gray2.shape
+        if C != 1 or B2 % 2 or flow2.shape != (B2, 2, H, W):
+            raise ValueError('census_warp_pair_pen_loss expects [2B,1,H,W] grey planes and [2B,2,H,W] flows')
+        occ_small2 = occ_small2.detach().contiguous()
+        if occ_small2.shape != (B2, 1, H // 4, W // 4):
+            raise ValueError('occ_small2 must be the [2B,1,H/4,W/4] range maps')
+        valid_flow2, vbs = _valid_view(valid_flow2, flow2.shape)
+        r = int(patch_size) // 2
+        buf = _new_sums(gray2.device, B2, H, W)
+        dham = torch.empty(B2, 1, H, W, device=gray2.device, dtype=torch.float32)
+        mask = torch.empty(B2, 1, H, W, device=gray2.device, dtype=torch.float32)
+        with torch.cuda.device_of(gray2):
+            _call('arflow_census_warp_pair_pen_fwd', _p(gray2), _p(flow2), fbs, _p(occ_small2), _p(mask), _p(dham), _p(buf), B2,
+                  H, W, r, _p(valid_flow2), vbs, _pen_ptr(pen), _stream(), key=(B2, H, W))
+        sums = _fold_sums(buf, 4)
+        den = torch.stack([_ddp.global_denominator(sums[1]), _ddp.global_denominator(sums[3])]) + 1e-6 / _ddp.world_size()
+        inv = 1.0 / den
+        ctx.save_for_backward(gray2, flow2, dham, inv)
+        ctx.r, ctx.fbs = r, fbs
+        ctx.mark_non_differentiable(mask)
+        return sums[0] * inv[0], sums[2] * inv[1], mask
+
+    @staticmethod
+    def backward(ctx, g0, g1, gmask_unused):
+        return CensusWarpPairLossFunction.backward(ctx, g0, g1, gmask_unused) + (None, None)
+
+
+def census_warp_pair_pen_loss(gray2, flow2, occ_small2, pen, valid_flow2=None, patch_size=7):
+    return CensusWarpPairPenLossFunction.apply(gray2, flow2, occ_small2, patch_size, pen, valid_flow2)
+
+
+class SmoothPenSumsFunction(torch.autograd.Function):
+    """SmoothSumsFunction with the penalty `pen` applied to the SQUARED flow differences (losses/uflow_elbo_loss.py:507-533):
+    arflow_smooth_pen_fwd / _bwd.  Gradient w.r.t. flow only."""
+
+    @staticmethod
+    def forward(ctx, flow, img, flow_scale, alpha, order, wmode, pen):
+        _need_gpu(flow, img)
+        flow, fbs = _flow_view(flow)
+        img = img.contiguous()
+        B, _, H, W = flow.shape
+        Ci = img.shape[1]
+        if img.shape[0] != B or img.shape[2:] != flow.shape[2:]:
+            raise ValueError('smoothness: image and flow must share batch and spatial size')
+        buf = _new_sums(flow.device, B, H, W)
+        args = (B, Ci, H, W, fbs, float(flow_scale), float(alpha), int(order), int(wmode))
+        with torch.cuda.device_of(flow):
+            _call('arflow_smooth_pen_fwd', _p(flow), _p(img), _p(buf), *args, _pen_ptr(pen), _stream(), key=(B, Ci, H, W))
+        ctx.save_for_backward(flow, img)
+        ctx.args, ctx.pen = args, pen
+        return _fold_sums(buf, 2)
+
+    @staticmethod
+    def backward(ctx, gsums):
+        flow, img = ctx.saved_tensors
+        B, _, H, W = flow.shape
+        coef = gsums.contiguous()
+        g = torch.empty(B, 2, H, W, device=flow.device, dtype=torch.float32)
+        with torch.cuda.device_of(flow):
+            _call('arflow_smooth_pen_bwd', _p(flow), _p(img), _p(coef), _p(g), *ctx.args, _pen_ptr(ctx.pen), _stream(),
+                  key=(B, img.shape[1], H, W))
+        return g, None, None, None, None, None, None
+
+
+def smooth_pen_sums(flow, img, flow_scale, alpha, order, wmode, pen):
+    return SmoothPenSumsFunction.apply(flow, img, flow_scale, alpha, order, wmode, pen)
+
+
 def down4_gray(img, want_small=True, zero_plane=False):
     """(downsample(img, x1/4) or None, rgb_to_grayscale(img) * 255) from ONE read of the image (no gradient: the
     reference applies both to data only, losses/uflow_loss.py:59-60, utils/uflow_utils.py:248).  zero_plane=True also

@@ -5,7 +5,7 @@ from .flow_loss import unFlowLoss
 from .fullres_loss import FullResLoss
 from .mse_loss import MseLoss
 from .mv_loss import MvLoss
-from .uflow_elbo_loss import UFlowElboLoss
+from .uflow_elbo_loss import UFlowElboLoss, UFlowElboPenLoss, takes_default_path
 from .uflow_loss import UFlowLoss
 
 
@@ -19,7 +19,8 @@ def get_loss(cfg):
     if cfg.type == 'uflow':
         return UFlowLoss(cfg)
     if cfg.type == 'uflow_elbo':
-        return UFlowElboLoss(cfg)
+        # selectable penalties / mean-flow masks: the subclass on the penalised kernels
+        return UFlowElboLoss(cfg) if takes_default_path(cfg) else UFlowElboPenLoss(cfg)
     if cfg.type == 'mse':
         return MseLoss(cfg)
     if cfg.type == 'mv':  # build-defined 3-frame objective; not a reference type

@@ -16,7 +16,16 @@ log-determinants of csrc/lowrank.hip; approx_entropy is no
 n_samples; with_bk; w_oof, w_occ; and 'mixture' (inv_cov false, n_components 2..4: the sampler, the mixture log-density and
 their one backward launch of csrc/mixture.hip; level-2 outputs of 4 n_components channels = the
 components' means, then their log-stds; weights from res_dict['weights_fw'] / ['weights_bw'] or uniform; approx_entropy is not
-consulted, as in the reference).  Everything else raises NotImplementedError naming the value.  A missing `isotropic_smooth` / `order_smooth` reads as False / 1 (the reference
+consulted, as in the reference).  UFlowElboLoss itself takes data_penalty ['abs_robust_loss'], penalty_smooth 'charbonnier' and
+occ_type 'sample' and refuses every other value of the three at construction; UFlowElboPenLoss, the subclass get_loss returns
+for any other setting, takes: data_penalty[0] in abs_robust_loss, identity, charbonnier,
+gmm (mixture from penalty_census_pi / penalty_census_beta); penalty_smooth in charbonnier, identity, abs_robust_loss, gmm
+(penalty_smooth_pi / penalty_smooth_beta), sampled and in both closed forms; occ_type 'sample' or 'mean' (range map of the
+partner's MEAN flow, validity of the x4 upsample of the own mean; not with approx 'mixture', which has no single mean).  The
+default setting (abs_robust_loss, charbonnier, sample) makes exactly the calls described above; any other runs the penalised
+census forward (arflow_census_warp_pair_pen_fwd and its siblings) and, for the smoothness, arflow_smooth_pen_fwd / _bwd: the
+backward is then arflow_census_warp_pair_bwd plus a smoothness backward, two launches.  Everything else raises
+NotImplementedError naming the value; a malformed mixture raises ValueError.  A missing `isotropic_smooth` / `order_smooth` reads as False / 1 (the reference
 raises AttributeError on its own chairs_uflow_elbo_nondiag.json, which omits them).
 """
 import torch
@@ -27,6 +36,7 @@ from ..lowrank import RMAX, reparam_lowrank_pair
 from ..mixture import KMAX, reparam_gmm_pair
 from ..triag_solve import reparam_triag_pair
 from ..uflow_utils import census_loss, flow_to_warp, image_grads
+from .penalty_functions import check_mixture, get_penalty
 
 
 def _charbonnier(x_sq, eps=0.001):
@@ -55,6 +65,11 @@ def range_map(flow):
 
 
 class UFlowElboLoss(nn.Module):
+    # what this class takes; UFlowElboPenLoss below widens the three sets (get_loss chooses between the two)
+    DATA_PENALTIES = ('abs_robust_loss',)
+    SMOOTH_PENALTIES = ('charbonnier',)
+    OCC_TYPES = ('sample',)
+
     def __init__(self, cfg):
         super().__init__()
         self.cfg = cfg
@@ -76,14 +91,35 @@ class UFlowElboLoss(nn.Module):
                 raise NotImplementedError('columns: %r (supported: 1..%d)' % (columns, RMAX))
             if cfg.inv_cov:
                 raise NotImplementedError("inv_cov: True with approx: 'lowrank'")
-        if cfg.occ_type != 'sample':
-            raise NotImplementedError("occ_type: %r (supported: 'sample')" % (cfg.occ_type,))
+        if cfg.occ_type not in self.OCC_TYPES:
+            raise NotImplementedError("occ_type: %r (supported by %s: %s)" % (cfg.occ_type, type(self).__name__, list(self.OCC_TYPES)))
+        if cfg.occ_type == 'mean' and cfg.approx == 'mixture':
+            raise NotImplementedError("occ_type: 'mean' with approx: 'mixture' (a mixture has no single mean flow)")
         if list(cfg.data_loss) != ['census']:
             raise NotImplementedError("data_loss: %r (supported: ['census'])" % (list(cfg.data_loss),))
-        if list(cfg.data_penalty) != ['abs_robust_loss']:
-            raise NotImplementedError("data_penalty: %r (supported: ['abs_robust_loss'])" % (list(cfg.data_penalty),))
-        if cfg.penalty_smooth != 'charbonnier':
-            raise NotImplementedError("penalty_smooth: %r (supported: 'charbonnier')" % (cfg.penalty_smooth,))
+        data_penalty = list(cfg.data_penalty)
+        if len(data_penalty) != 1 or data_penalty[0] not in self.DATA_PENALTIES:
+            raise NotImplementedError("data_penalty: %r (supported by %s: one of %s)"
+                                      % (data_penalty, type(self).__name__, list(self.DATA_PENALTIES)))
+        if cfg.penalty_smooth not in self.SMOOTH_PENALTIES:
+            raise NotImplementedError("penalty_smooth: %r (supported by %s: %s)"
+                                      % (cfg.penalty_smooth, type(self).__name__, list(self.SMOOTH_PENALTIES)))
+        # the default setting keeps the calls it has always made; everything else goes through the penalised entry points
+        self.default = (data_penalty[0], cfg.penalty_smooth, cfg.occ_type) == ('abs_robust_loss', 'charbonnier', 'sample')
+        census_mix = smooth_mix = (None, None)
+        if data_penalty[0] == 'gmm':
+            census_mix = check_mixture(getattr(cfg, 'penalty_census_pi', None), getattr(cfg, 'penalty_census_beta', None),
+                                       "data_penalty 'gmm' (penalty_census_pi / penalty_census_beta)")
+        if cfg.penalty_smooth == 'gmm':
+            smooth_mix = check_mixture(getattr(cfg, 'penalty_smooth_pi', None), getattr(cfg, 'penalty_smooth_beta', None),
+                                       "penalty_smooth 'gmm' (penalty_smooth_pi / penalty_smooth_beta)")
+        self.data_pen = AF.make_penalty(data_penalty[0], *census_mix)
+        # the sampled smoothness of a non-default penalty: the descriptor of rho over the SQUARED differences (None: charbonnier,
+        # arflow_smooth_fwd's own penalty 1); the closed forms, plain torch, take the callable
+        self.smooth_pen = None if cfg.penalty_smooth == 'charbonnier' else AF.make_penalty(cfg.penalty_smooth, *smooth_mix,
+                                                                                          squared=True)
+        self.smooth_fn = _charbonnier if cfg.penalty_smooth == 'charbonnier' else get_penalty(
+            cfg.penalty_smooth, pi=smooth_mix[0], beta=smooth_mix[1], squared=True)
         self.closed = bool(getattr(cfg, 'closed_form_smooth', False))
         self.isotropic = bool(getattr(cfg, 'isotropic_smooth', False))
         self.order = int(getattr(cfg, 'order_smooth', 1))
@@ -148,7 +184,7 @@ class UFlowElboLoss(nn.Module):
                   + diag[:, :, 0:-2] ** 2 + 4 * diag[:, :, 1:-1] ** 2 + diag[:, :, 2:] ** 2)
         if self.isotropic:
             Ex, Ey = torch.mean(Ex, dim=1), torch.mean(Ey, dim=1)
-        return torch.mean(wx * cfg.w_smooth * _charbonnier(Ex)) + torch.mean(wy * cfg.w_smooth * _charbonnier(Ey))
+        return torch.mean(wx * cfg.w_smooth * self.smooth_fn(Ex)) + torch.mean(wy * cfg.w_smooth * self.smooth_fn(Ey))
 
     def _sampled_smooth(self, s_alpha, flow2, small, n_per_direction):
         """s_alpha: the smoothness sums at edge_constant, or None (computed here); -> the sampled charbonnier term."""
@@ -162,6 +198,76 @@ class UFlowElboLoss(nn.Module):
         h, w = flow2.shape[2:]
         nx, ny = float(n_per_direction * 2 * h * (w - 1)), float(n_per_direction * 2 * (h - 1) * w)
         return cfg.w_smooth * (s[0] / nx + s[1] / ny) / 2.
+
+    def _sampled_smooth_pen(self, flow2, small, n_per_direction):
+        """_sampled_smooth under a non-default smoothness penalty (arflow_smooth_pen_fwd / _bwd)."""
+        cfg = self.cfg
+        if self.smooth_pen is None:
+            return self._sampled_smooth(None, flow2, small, n_per_direction)
+        ea = float(getattr(cfg, 'edge_asymp', 0.0))
+        s = AF.smooth_pen_sums(flow2, small, 1.0, float(cfg.edge_constant), 1, 1, self.smooth_pen)
+        if ea != 0.0:
+            s = ea * AF.smooth_pen_sums(flow2, small, 1.0, 0.0, 1, 1, self.smooth_pen) + (1.0 - ea) * s
+        h, w = flow2.shape[2:]
+        nx, ny = float(n_per_direction * 2 * h * (w - 1)), float(n_per_direction * 2 * (h - 1) * w)
+        return cfg.w_smooth * (s[0] / nx + s[1] / ny) / 2.
+
+    def _direction_pen(self, a, b, flow_ab0, occ_small, valid_flow0):
+        """_direction under the penalty self.data_pen: occ_small is the range map that masks this direction (of the partner's
+        samples, or of its mean), valid_flow0 the flow mask_invalid is taken of (None: flow_ab0)."""
+        if a['gray'] is not None:
+            l_c, _ = AF.census_warp_pen_loss(a['gray'], b['gray'], flow_ab0, occ_small, self.data_pen, valid_flow0, 7)
+            return l_c
+        recons, valid = AF.warp_with_valid(b['im'].detach(), flow_ab0, pad='zeros', align_corners=True, norm=AF.NORM_UFLOW)
+        if valid_flow0 is not None:
+            valid = AF.coord_mask(valid_flow0, 0)
+        return AF.census_pen_loss(a['im'], recons, AF.up4_clamp_mul(occ_small, valid), self.data_pen, 7)
+
+    def _pen_terms(self, im1_0, im2_0, flows2, f0, mean12, mean21, S, with_bk, grey):
+        """The data term and the sampled smoothness of every non-default setting -> (loss_warp, loss_smooth or None, the range
+        map [S B,1,h,w] masking the forward direction, the validity flow of the forward direction or None, small1, small2).
+        f0: flows0 [2 S B,2,H,W] (with_bk) or the forward level-0 flows."""
+        cfg = self.cfg
+        SB, _, h, w = flows2.shape
+        B = SB // S
+        H, W = 4 * h, 4 * w
+        flow12_2, flow21_2 = flows2[:, 0:2], flows2[:, 2:4]
+        mean = cfg.occ_type == 'mean'
+        vf_fw = vf_bw = None
+        if mean:  # everything detached: the masks carry no gradient (losses/uflow_elbo_loss.py:42-50)
+            m12, m21 = mean12.detach().contiguous(), mean21.detach().contiguous()
+            range21 = AF.splat_map(m21, 0).repeat(S, 1, 1, 1)
+            vf_fw = AF.interpolate_flow(m12, 4, False).repeat(S, 1, 1, 1)
+            if with_bk:
+                range12 = AF.splat_map(m12, 0).repeat(S, 1, 1, 1)
+                vf_bw = AF.interpolate_flow(m21, 4, False).repeat(S, 1, 1, 1)
+        else:
+            range21 = AF.splat_map(flow21_2, 0)
+            if with_bk:
+                range12 = AF.splat_map(flow12_2, 0)
+        loss_smooth = None
+        if grey and self.pair and with_bk:
+            small, gray = AF.down4_gray(torch.cat((im1_0, im2_0), 1).view(2 * B, 3, H, W))
+            small_rep, gray_rep = small.repeat(S, 1, 1, 1), gray.repeat(S, 1, 1, 1)
+            occ = torch.stack((range12, range21), 1).view(2 * SB, 1, h, w)  # plane n masks sample n ^ 1
+            vf = torch.stack((vf_fw, vf_bw), 1).view(2 * SB, 2, H, W) if mean else None
+            l_fw, l_bw, _ = AF.census_warp_pair_pen_loss(gray_rep, f0, occ, self.data_pen, vf, 7)
+            loss_warp = cfg.data_weight[0] * l_fw + cfg.data_weight[0] * l_bw
+            small1, small2 = small.view(B, 2, 3, h, w)[:, 0], small.view(B, 2, 3, h, w)[:, 1]
+            if not self.closed:
+                loss_smooth = self._sampled_smooth_pen(flows2.view(2 * SB, 2, h, w), small_rep, SB)
+        else:
+            one, two = self._prepare(im1_0, S, grey), self._prepare(im2_0, S, grey)
+            f0_fw, f0_bw = (f0.view(SB, 2, 2, H, W)[:, 0], f0.view(SB, 2, 2, H, W)[:, 1]) if with_bk else (f0, None)
+            loss_warp = cfg.data_weight[0] * self._direction_pen(one, two, f0_fw, range21, vf_fw)
+            if with_bk:
+                loss_warp = loss_warp + cfg.data_weight[0] * self._direction_pen(two, one, f0_bw, range12, vf_bw)
+            small1, small2 = one['small1'], two['small1']
+            if not self.closed:
+                loss_smooth = self._sampled_smooth_pen(flow12_2, one['small'], SB)
+                if with_bk:
+                    loss_smooth = loss_smooth + self._sampled_smooth_pen(flow21_2, two['small'], SB)
+        return loss_warp, loss_smooth, range21, vf_fw, small1, small2
 
     def _direction(self, a, b, flow_ab0, flow_ba2):
         """One photometric direction as UFlowLoss._direction composes it -> (census loss, range map of the partner)."""
@@ -270,7 +376,12 @@ class UFlowElboLoss(nn.Module):
             f0_fw, f0_bw = AF.interpolate_flow(flow12_2.contiguous(), 4, False), None
         valid_mask12 = AF.coord_mask(f0_fw, 0)
         s_alpha = None
-        if grey and self.pair and with_bk:
+        if not self.default:
+            loss_warp, loss_smooth, range21, vf_fw, small1, small2 = self._pen_terms(
+                im1_0, im2_0, flows2, flows0 if with_bk else f0_fw, mean12, mean21, S, with_bk, grey)
+            if vf_fw is not None:
+                valid_mask12 = AF.coord_mask(vf_fw, 0)
+        elif grey and self.pair and with_bk:
             small, gray = AF.down4_gray(torch.cat((im1_0, im2_0), 1).view(2 * B, 3, H, W))
             small_rep, gray_rep = small.repeat(S, 1, 1, 1), gray.repeat(S, 1, 1, 1)
             occ = torch.zeros(2 * S * B, 1, h, w, device=net12.device, dtype=torch.float32)
@@ -309,10 +420,12 @@ class UFlowElboLoss(nn.Module):
                 loss_oof = loss_oof + cfg.w_oof * (u + v).mean()
         loss_occ = 0
         if cfg.w_occ > 0.0:  # the reference differentiates this term through the range map as well
-            occu_mask12 = torch.clamp(range_map(flow21_2), min=0., max=1.)
+            # occ_type 'mean': the masks data_loss_no_penalty returned, the range maps of the (repeated) mean flows
+            occ_of12, occ_of21 = (mean12.repeat(S, 1, 1, 1), mean21.repeat(S, 1, 1, 1)) if cfg.occ_type == 'mean' else (flow12_2, flow21_2)
+            occu_mask12 = torch.clamp(range_map(occ_of21), min=0., max=1.)
             loss_occ = cfg.w_occ * (1 / (100.0 * occu_mask12 + 1) * torch.square(flow12_2)).mean()
             if with_bk:
-                occu_mask21 = torch.clamp(range_map(flow12_2), min=0., max=1.)
+                occu_mask21 = torch.clamp(range_map(occ_of12), min=0., max=1.)
                 loss_occ = loss_occ + cfg.w_occ * (1 / (100.0 * occu_mask21 + 1) * torch.square(flow21_2)).mean()
         else:
             occu_mask12 = torch.clamp(range21, min=0., max=1.)
@@ -324,3 +437,17 @@ class UFlowElboLoss(nn.Module):
                 loss_offdiag = loss_offdiag + torch.mean(torch.square(off21))
             total = total + cfg.offdiag_reg * loss_offdiag
         return total, loss_warp, loss_smooth, loss_entropy, loss_oof, flow12_2, occu_mask12, valid_mask12
+
+
+class UFlowElboPenLoss(UFlowElboLoss):
+    """UFlowElboLoss with the selectable penalties and mean-flow masks of DESIGN.md section 45: what get_loss returns for
+    type 'uflow_elbo' whenever (data_penalty, penalty_smooth, occ_type) is not (abs_robust_loss, charbonnier, sample).  The
+    base class keeps refusing those settings, as it always has; with the default triple this class makes the base's calls."""
+    DATA_PENALTIES = ('abs_robust_loss', 'identity', 'charbonnier', 'gmm')
+    SMOOTH_PENALTIES = ('charbonnier', 'identity', 'abs_robust_loss', 'gmm')
+    OCC_TYPES = ('sample', 'mean')
+
+
+def takes_default_path(cfg):
+    """True where UFlowElboLoss itself runs the config's penalties and masks (get_loss's choice of class)"""
+    return (list(cfg.data_penalty), cfg.penalty_smooth, cfg.occ_type) == (['abs_robust_loss'], 'charbonnier', 'sample')

@@ -33,7 +33,7 @@ from . import uflow_utils as U
 from .functional import _call, _p, _stream
 
 __all__ = ['EM', 'fit_penalty', 'fwhm_scale', 'gaussian_mixture', 'robust_l1_fwhm', 'abs_robust_loss_fwhm', 'log_gmm',
-           'data_loss_no_penalty', 'smooth_loss_no_penalty', 'collect_samples', 'em_stats', 'em_share', 'KMAX', 'INIT_VARS']
+           'data_loss_no_penalty', 'smooth_loss_no_penalty', 'collect_samples', 'em_stats', 'em_share', 'penalty_cfg', 'KMAX', 'INIT_VARS']
 
 KMAX = 16         # ARFLOW_EM_KMAX of include/arflow_hip.h
 EM_UNIT = 1024    # ARFLOW_EM_UNIT
@@ -279,6 +279,17 @@ def log_gmm(x, pi, beta):
         raise ValueError('log_gmm expects pi and beta of one length k, 1 <= k <= %d' % KMAX)
     w = (pi * torch.sqrt(beta) / math.sqrt(2 * math.pi)).contiguous()
     return LogGmmFunction.apply(x, w, beta)
+
+
+def penalty_cfg(pi, beta, scale=1.0):
+    """A fitted mixture as the config entries UFlowElboLoss reads: {'pi': [...], 'beta': [scale * beta ...]} of Python floats
+    (scale: what fwhm_scale returned).  Assign them to penalty_census_pi / penalty_census_beta (data_penalty ['gmm']) or
+    penalty_smooth_pi / penalty_smooth_beta (penalty_smooth 'gmm')."""
+    pi = [float(v) for v in torch.as_tensor(pi, dtype=torch.float64).reshape(-1).tolist()]
+    beta = [float(scale) * float(v) for v in torch.as_tensor(beta, dtype=torch.float64).reshape(-1).tolist()]
+    if len(pi) != len(beta) or not 1 <= len(pi) <= KMAX:
+        raise ValueError('penalty_cfg expects pi and beta of one length k, 1 <= k <= %d' % KMAX)
+    return {'pi': pi, 'beta': beta}
 
 
 # ---- residual collection (losses/uflow_elbo_loss.py:18-96, train_penalty_em.py:235-289) -----------------------------

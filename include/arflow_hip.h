@@ -1053,6 +1053,62 @@ int arflow_log_gmm_fwd(const void* x, long n, int is_f64, const double* w, const
 int arflow_log_gmm_bwd(const void* x, const void* gout, long n, int is_f64, const double* w, const double* beta, int k, void* gx,
                        arflow_stream_t stream);
 
+/* ---- selectable penalties of UFlowElboLoss (csrc/penalty_dev.hpp) ----------------------------------
+ * One pair (rho, rho') per kind, fp32:
+ *   ARFLOW_PEN_IDENTITY     rho(x) = x
+ *   ARFLOW_PEN_CHARBONNIER  rho(x) = sqrt(x + 1e-6)                       (losses/penalty_functions.py:6-7, eps = 0.001)
+ *   ARFLOW_PEN_ABS_ROBUST   rho(x) = (|x| + 0.01)^0.4                     (losses/penalty_functions.py:3-4)
+ *   ARFLOW_PEN_GMM          rho(x) = -log sum_j w_j exp(-beta_j x^2 / 2)  data term, x = the soft census distance
+ *   ARFLOW_PEN_GMM_SQ       rho(x) = -log sum_j w_j exp(-beta_j x / 2)    smoothness, x = the squared flow difference
+ * The mixtures are evaluated in the order of losses/uflow_elbo_loss.py:99-105: arg_j, c = max_j arg_j, e_j = exp(arg_j - c),
+ * den = sum_j w_j e_j (j ascending), rho = -(c + log den), rho' = (sum_j w_j e_j beta_j / den) * x (GMM) or / 2 (GMM_SQ).
+ * w_j = pi_j sqrt(beta_j) / sqrt(2 pi) is formed by the caller in float64 and rounded to fp32 once, like beta_j.
+ * The descriptor lives in HOST memory and is copied into the kernel arguments: no allocation, no synchronisation.
+ * Every entry point below answers ARFLOW_ENULL for a NULL descriptor and ARFLOW_EPARAM for an unknown kind, k outside
+ * 1 .. ARFLOW_EM_KMAX, a kind it does not take (GMM_SQ in a census call, GMM in a smoothness call), a non-finite or
+ * non-positive beta_j, a negative or non-finite w_j, or w = 0 for the component with the smallest beta (its term bounds the
+ * density away from 0 for every argument) -- w, beta and k are only read for the two mixture kinds. */
+#define ARFLOW_PEN_IDENTITY 0
+#define ARFLOW_PEN_CHARBONNIER 1
+#define ARFLOW_PEN_ABS_ROBUST 2
+#define ARFLOW_PEN_GMM 3
+#define ARFLOW_PEN_GMM_SQ 4
+typedef struct arflow_penalty_t {
+  int kind;
+  int k;
+  float w[ARFLOW_EM_KMAX];
+  float beta[ARFLOW_EM_KMAX];
+} arflow_penalty_t;
+/* arflow_census_warp_fwd / arflow_census_warp_pair_fwd with the census_loss epilogue rho of `pen` in place of abs_robust_loss:
+ * sums numerator = sum rho(ham) pm, dham = pm rho'(ham) -- the plane every census backward entry point reads, so
+ * arflow_census_warp_bwd / _pair_bwd serve every kind (the ordered family's too when the environment selects it).
+ * valid_flow (nullable; [B,2,H,W] with batch stride valid_bstride >= 2 H W): when given, mask_invalid is taken of THIS flow
+ * while the warp still samples at `flow` (occ_type 'mean': the x4 upsample of the mean flow); NULL = `flow`, as today.
+ * These two ALWAYS run the column family (csrc/census_col.hpp): ARFLOW_CENSUS_COL / ARFLOW_CENSUS_SYM do not route them.
+ * With ARFLOW_PEN_ABS_ROBUST and valid_flow NULL the outputs equal the unpenalised entry points' bit for bit. */
+int arflow_census_warp_pen_fwd(const float* gray_a, const float* gray_b, const float* flow, long flow_bstride,
+                               const float* occ_small, float* mask_out, float* dham, float* sums, int B, int H, int W,
+                               int radius, const float* valid_flow, long valid_bstride, const arflow_penalty_t* pen,
+                               arflow_stream_t stream);
+int arflow_census_warp_pair_pen_fwd(const float* gray, const float* flow, long flow_bstride, const float* occ_small,
+                                    float* mask_out, float* dham, float* sums, int B2, int H, int W, int radius,
+                                    const float* valid_flow, long valid_bstride, const arflow_penalty_t* pen,
+                                    arflow_stream_t stream);
+/* arflow_census_fwd with a mask and a descriptor, for the unfused route: ham [B,1,H,W] (required: the distances are written
+ * there by arflow_census_fwd's kernels, then a second launch applies rho under the border-zeroed mask), dham = pm rho'(ham),
+ * sums as arflow_census_fwd.  mask, ham, dham, sums required; radius 1 .. 3 (else ARFLOW_EPARAM); H <= 65535. */
+int arflow_census_pen_fwd(const float* im_a, const float* im_b, const float* mask, float* ham, float* dham, float* sums,
+                          int B, int H, int W, int radius, const arflow_penalty_t* pen, arflow_stream_t stream);
+/* arflow_smooth_fwd / arflow_smooth_bwd with rho of `pen` applied to x = v^2 of the signed (first- or second-order)
+ * difference v, d rho / d v = 2 v rho'(x).  Kinds: IDENTITY, CHARBONNIER, ABS_ROBUST, GMM_SQ.  CHARBONNIER is
+ * arflow_smooth_fwd / _bwd with penalty = 1 bit for bit.  order, wmode and the edge weights as there. */
+int arflow_smooth_pen_fwd(const float* flow, const float* img, float* sums, int B, int Ci, int H, int W, long flow_bstride,
+                          float flow_scale, float alpha, int order, int wmode, const arflow_penalty_t* pen,
+                          arflow_stream_t stream);
+int arflow_smooth_pen_bwd(const float* flow, const float* img, const float* coef, float* gflow, int B, int Ci, int H, int W,
+                          long flow_bstride, float flow_scale, float alpha, int order, int wmode, const arflow_penalty_t* pen,
+                          arflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ fraction of the 8 TB/s HBM roofline.  Calls the C ABI directly (no autograd over
     python tools/kbench.py --filter optim          # the fused optimiser step against torch.optim.Adam(fused=True)
     python tools/kbench.py --filter ar             # the AR transform and loss, fused against composed ATen ops
     python tools/kbench.py --filter penalty_em     # one EM update of the penalty fit and log_gmm against their torch formulations
+    python tools/kbench.py --filter elbo_penalty   # one UFlowElboLoss step with the fitted mixture penalties against the default step and the unfused composition
 """
 import argparse
 import json
@@ -17,6 +18,11 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+# --tree DIR: import arflow_amd (and its built library) from another checkout of the project, for the legs of a bench that the
+# other checkout can run too (--filter elbo_penalty: the default step); read here because it decides what the imports below find
+TREE = os.path.abspath(sys.argv[sys.argv.index('--tree') + 1]) if '--tree' in sys.argv[1:-1] else None
+if TREE:
+    sys.path.insert(0, TREE)
 import torch  # noqa: E402
 
 from arflow_amd import _lib  # noqa: E402
@@ -944,18 +950,131 @@ def penalty_em_bench(dev, jsonl, m=3000000, init_vars=None, launches=20, repeats
             out.write(json.dumps(line) + '\n')
 
 
+ELBO_PENALTY_BASE = dict(type='uflow_elbo', edge_constant=150, edge_asymp=0.01, w_smooth=4.0, penalty_smooth='charbonnier',
+                         closed_form_smooth=False, data_loss=['census'], data_weight=[1.0], data_penalty=['abs_robust_loss'],
+                         w_entropy=0.1, w_oof=0.0, w_occ=0.0, with_bk=True, approx='diag', cov_supp=0, inv_cov=False,
+                         approx_entropy=False, occ_type='sample', n_samples=4, offdiag_reg=0.0, natural_grad=False)
+
+
+def elbo_penalty_inputs(dev, B=8, M=96, N=160, seed=7):
+    """the loss case of band_bench at approx 'diag': two [B,4,M,N] level-2 outputs (mean 1.5 N(0,1), log-std -1 + 0.3 N(0,1))
+    and a uniform-noise image pair at 4M x 4N, from a generator of their own"""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    nets = [torch.cat((1.5 * torch.randn(B, 2, M, N, device=dev, generator=g), -1 + 0.3 * torch.randn(B, 2, M, N, device=dev, generator=g)),
+                      1).requires_grad_(True) for _ in range(2)]
+    ims = [torch.rand(B, 3, 4 * M, 4 * N, device=dev, generator=g) for _ in range(2)]
+    return nets, ims
+
+
+def elbo_penalty_bench(dev, jsonl, B=8, S=4, M=96, N=160, launches=20, repeats=5, settle=40):
+    """one UFlowElboLoss step (forward + backward to the level-2 outputs) at the shape of band_bench's loss
+    case (B = 8, S = 4, 384 x 640, a 96 x 160 level 2), approx 'diag', with
+      default   abs_robust_loss + charbonnier (the unchanged path: one-launch backward),
+      gmm       the ten-component mixtures of the reference's chairs_uflow_elbo_gmm.json for both penalties (the penalised pair
+                forward, arflow_smooth_pen_fwd / _bwd, two-launch backward),
+      torch     the same objective composed without the penalised kernels: the differentiable warp and census distance nodes,
+                -log_gmm on the distance map, the squared-mixture torch node on torch-made flow differences.
+    `settle` untimed calls of every leg, then HIP events around `launches` steps after 5 warm-ups, the legs in alternation,
+    `repeats` rounds: median (min .. max).  With --tree DIR (another checkout, e.g. the parent commit's, built) only the default
+    leg runs, on that checkout's package, and the line carries tree = DIR's last component; the comparison (a) of the default
+    step at two commits is two such invocations writing to one --jsonl file."""
+    import statistics
+    from arflow_amd import functional as AF, uflow_utils as U
+    from arflow_amd.config import AttrDict
+    from arflow_amd.losses.get_loss import get_loss
+    nets, ims = elbo_penalty_inputs(dev, B, M, N)
+    H, W = 4 * M, 4 * N
+    eps = tuple(torch.randn(S * B, 2, M, N, device=dev, generator=torch.Generator(device=dev).manual_seed(11 + d)) for d in (0, 1))
+
+    def run(loss):
+        out = loss({'flows_fw': [None, None, nets[0]], 'flows_bw': [None, None, nets[1]]}, ims[0], ims[1], eps=eps)
+        return out, torch.autograd.grad(out[0], nets)
+
+    def measure(legs, line):
+        for fn in legs.values():  # (launch-bound steps: the host time of a call settles after some tens of calls, as in band_bench)
+            for _ in range(settle):
+                fn()
+        torch.cuda.synchronize()
+        t = {name: [] for name in legs}
+        for _ in range(repeats):
+            for name, fn in legs.items():
+                t[name].append(timeit(fn, launches))
+                MANIFEST[-1].update(name='elbo_penalty/' + name, shape=[B, S, H, W])
+        for name, v in t.items():
+            line.update({name + '_us': statistics.median(v), name + '_us_min': min(v), name + '_us_max': max(v)})
+            print('elbo_penalty %-8s %9.1f us (%.1f .. %.1f)' % (name, statistics.median(v), min(v), max(v)), flush=True)
+        return line
+    default = get_loss(AttrDict(dict(ELBO_PENALTY_BASE, n_samples=S)))
+    line = {'bench': 'elbo_penalty', 'tree': os.path.basename(TREE) if TREE else 'this', 'shape': [B, S, H, W], 'approx': 'diag',
+            'launches': launches, 'rounds': repeats}
+    if TREE:
+        import arflow_amd
+        assert os.path.abspath(arflow_amd.__file__).startswith(TREE + os.sep), arflow_amd.__file__
+        with open(jsonl, 'a') as out_file:
+            out_file.write(json.dumps(measure({'default': lambda: run(default)}, line)) + '\n')
+        return
+    from arflow_amd.losses.penalty_functions import get_penalty
+    from tests import elbo_penalty_ref as PR
+    gmm_cfg = dict(ELBO_PENALTY_BASE, n_samples=S, data_penalty=['gmm'], penalty_smooth='gmm', **PR.GMM_KEYS)
+    losses = {'default': default, 'gmm': get_loss(AttrDict(gmm_cfg))}
+    pen_data = get_penalty('gmm', pi=PR.CENSUS_PI, beta=PR.CENSUS_BETA)
+    pen_smooth = get_penalty('gmm', pi=PR.SMOOTH_PI, beta=PR.SMOOTH_BETA, squared=True)
+    cfg = AttrDict(gmm_cfg)
+
+    def composed():
+        """the objective of the 'gmm' leg on the unpenalised nodes (data + sampled smoothness - entropy)"""
+        total = 0.
+        rep = lambda t: t.repeat(S, 1, 1, 1)  # noqa: E731
+        z = [rep(n[:, 0:2]) + rep(torch.exp(n[:, 2:4])) * e for n, e in zip(nets, eps)]
+        for d in (0, 1):
+            im_a, im_b = rep(ims[d]), rep(ims[d ^ 1])
+            f0 = AF.interpolate_flow(z[d], 4, False)
+            recons, valid = AF.warp_with_valid(im_b, f0, pad='zeros', align_corners=True, norm=AF.NORM_UFLOW)
+            mask = AF.up4_clamp_mul(AF.splat_map(z[d ^ 1], 0), valid)
+            pm = torch.nn.functional.pad(mask[:, :, 3:-3, 3:-3], (3, 3, 3, 3))
+            ham = AF.TernaryDistFunction.apply(im_a, recons, 3)
+            total = total + cfg.data_weight[0] * (pen_data(ham) * pm).sum() / (pm.sum() + 1e-6)
+            small = rep(AF.down4(ims[d]))
+            gx, gy = U.image_grads(small)
+            wx = cfg.edge_asymp + (1 - cfg.edge_asymp) * torch.exp(-torch.mean(torch.abs(cfg.edge_constant * gx), 1, keepdim=True))
+            wy = cfg.edge_asymp + (1 - cfg.edge_asymp) * torch.exp(-torch.mean(torch.abs(cfg.edge_constant * gy), 1, keepdim=True))
+            dx, dy = U.image_grads(z[d])
+            total = total + (wx / 2 * cfg.w_smooth * pen_smooth(dx ** 2)).mean() + (wy / 2 * cfg.w_smooth * pen_smooth(dy ** 2)).mean()
+            total = total - cfg.w_entropy * nets[d][:, 2:4].sum(1).mean()
+        return total
+
+    def torch_step():
+        torch.autograd.grad(composed(), nets)
+    legs = {'default': lambda: run(losses['default']), 'gmm': lambda: run(losses['gmm']), 'torch': torch_step}
+    (out, grads), ref = run(losses['gmm']), composed()
+    diff = abs(float(out[0].detach()) - float(ref.detach())) / abs(float(ref.detach()))
+    gdiff = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(grads, torch.autograd.grad(ref, nets)))
+    AF.start_kernel_timing()
+    run(losses['gmm'])
+    calls = AF.stop_kernel_timing()
+    line.update(k=len(PR.CENSUS_PI), total_rel_diff_gmm_vs_torch=diff, grad_rel_diff_gmm_vs_torch=gdiff,
+                gmm_library_launches=sorted({n for n, _ in calls}))
+    measure(legs, line)
+    line.update(gmm_over_default=line['gmm_us'] / line['default_us'], torch_over_gmm=line['torch_us'] / line['gmm_us'])
+    print('elbo_penalty gmm / default = %.3f   torch / gmm = %.2f   (total differs by %.1e, gradients by %.1e of their maximum)'
+          % (line['gmm_over_default'], line['torch_over_gmm'], diff, gdiff), flush=True)
+    with open(jsonl, 'a') as out_file:
+        out_file.write(json.dumps(line) + '\n')
+
+
 def main():
     if os.environ.get('ARFLOW_LIB_PATH'):  # an alternative build of the library (A/B timing; tools only)
         _lib.LIB_PATH = os.environ['ARFLOW_LIB_PATH']
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=50)
     ap.add_argument('--filter', default='')
+    ap.add_argument('--tree', default='', help='another checkout of the project to import arflow_amd from (see TREE above)')
     ap.add_argument('--levels', default='uflow')
     ap.add_argument('--batch', type=int, default=16, help='model-side batch (2B: both directions stacked)')
     ap.add_argument('--size', type=int, nargs=2, default=[384, 640])
-    ap.add_argument('--jsonl', default='', help='--filter augment, optim, ar and penalty_em append their result lines here '
+    ap.add_argument('--jsonl', default='', help='--filter augment, optim, ar, penalty_em and elbo_penalty append their result lines here '
                     '(default: profiles/augment_kbench.jsonl, profiles/optim_kbench.jsonl, profiles/ar_kbench.jsonl, '
-                    'profiles/penalty_em_kbench.jsonl)')
+                    'profiles/penalty_em_kbench.jsonl, profiles/elbo_penalty_kbench.jsonl)')
     ap.add_argument('--manifest', default='', help='write the ordered (name, shape, calls) list of the timed ops here')
     args = ap.parse_args()
     lib = _lib.load()
@@ -1453,6 +1572,8 @@ def main():
         ar_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'ar_kbench.jsonl'))
     if want('penalty_em'):  # one EM update and log_gmm (csrc/penalty_em.hip) against the reference's formulation in torch ops
         penalty_em_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'penalty_em_kbench.jsonl'))
+    if want('elbo_penalty'):  # one UFlowElboLoss step: default penalties, the fitted mixtures, and the mixtures composed of unpenalised nodes
+        elbo_penalty_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'elbo_penalty_kbench.jsonl'))
     if args.manifest:
         json.dump(MANIFEST, open(args.manifest, 'w'), indent=1)
     if not rows:  # only ops that keep their own byte model (the head convolutions) were selected
