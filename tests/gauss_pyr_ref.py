@@ -1,7 +1,8 @@
 """Definitions shared by tools/make_pwcliteprob_golden.py and the tests that replay tests/golden/elbo_pyramid.npz (DESIGN.md
 section 27): the loss and model cases, their seeded inputs, a numpy float64 restatement of the pyramid sampler with its entropy
 sums and closed-form gradient, a torch restatement of ElboLoss (losses/elbo_loss.py:9-146) on oracle/ops.py / oracle/losses.py,
-and a float64 restatement of the align_corners=True upsample with the per-pixel bounds the kernel tests use.
+and float64 restatements of the align_corners=True upsample and of the half-pixel x4 flow upsample with the per-pixel bounds
+the kernel tests use.
 TEST INFRASTRUCTURE ONLY."""
 import math
 
@@ -182,11 +183,42 @@ def _taps(n, f):
     return torch.from_numpy(i0), torch.from_numpy(i1), torch.from_numpy(1.0 - l1), torch.from_numpy(l1)
 
 
-def up_align(x, f):
+def _taps_half(n, f):
+    """... with align_corners=False and the scale factor given (up_source, upsample_dev.hpp:14-28): src = max((d + 1/2) / f
+    - 1/2, 0), both taps clamped.  The weights are multiples of 1 / (2 f): exact in fp32 for f = 2, 4, no coordinate term."""
+    d = np.arange(f * n, dtype=np.float64)
+    src = np.maximum((d + 0.5) / f - 0.5, 0.0)
+    i0 = np.minimum(np.floor(src).astype(np.int64), n - 1)
+    i1 = np.minimum(i0 + 1, n - 1)
+    l1 = src - i0
+    return torch.from_numpy(i0), torch.from_numpy(i1), torch.from_numpy(1.0 - l1), torch.from_numpy(l1)
+
+
+def up_half(x, f):
+    """x f bilinear resize (align_corners=False, half-pixel centres) of a [..., h, w] tensor in x's dtype, blended in the
+    order of up_blend."""
+    return up_align(x, f, _taps_half)
+
+
+def flow_up_half_ref(x, g, f=4, dtype=torch.float64, taps=_taps_half):
+    """AF.flow_upsample(x, f, False) = f * up_half(x, f) and its adjoint for the fine gradient g, in `dtype` on the CPU, with
+    the float64 bounds  6 EPS f sum w |x|  (the out_up rule, FWD_ROUNDINGS)  and  bwd_roundings(f) EPS f sum w |g|.
+    taps=_taps (WRONG on purpose): the align_corners=True weights.  -> out, bound, gin, gbound"""
+    x, g = x.detach().cpu(), g.detach().cpu()
+    xv = x.to(dtype).requires_grad_(True)
+    out = f * up_align(xv, f, taps)
+    (gin,) = torch.autograd.grad(out, xv, g.to(dtype))
+    xa = x.double().abs().requires_grad_(True)
+    mag = f * up_align(xa, f, _taps_half)
+    (gmag,) = torch.autograd.grad(mag, xa, g.double().abs())
+    return out.detach(), FWD_ROUNDINGS * EPS * mag.detach(), gin, bwd_roundings(f) * EPS * gmag
+
+
+def up_align(x, f, taps=_taps):
     """x f bilinear resize (align_corners=True) of a [..., h, w] tensor in x's dtype."""
     h, w = x.shape[-2:]
-    ya, yb, wy0, wy1 = _taps(h, f)
-    xa, xb, wx0, wx1 = _taps(w, f)
+    ya, yb, wy0, wy1 = taps(h, f)
+    xa, xb, wx0, wx1 = taps(w, f)
     wy0, wy1 = wy0.to(x.dtype).view(-1, 1), wy1.to(x.dtype).view(-1, 1)
     wx0, wx1 = wx0.to(x.dtype), wx1.to(x.dtype)
     top, bot = x[..., ya, :], x[..., yb, :]

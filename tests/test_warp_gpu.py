@@ -13,8 +13,8 @@ must be exact.  Outputs of the raw entry points are handed over full of NaN and 
 back untouched.  The forward, and the flow gradient without a channel split, must agree bit for bit over two runs; in
 deterministic mode all outputs must over three (every test leaves the mode off: autouse fixture).
 
-The per-pixel statement of the nearest and bicubic warps (csrc/generic.hip), of warp_up2 and of the level kernels is not
-here: the last two are held by tests/test_level_gpu.py."""
+The per-pixel statement of the nearest and bicubic warps (csrc/generic.hip) is tests/test_generic_gpu.py, on the restatement
+of tests/generic_ref.py; that of warp_up2 and of the level kernels is tests/test_level_gpu.py."""
 import pytest
 import torch
 
