@@ -160,6 +160,11 @@ PROTOTYPES = {
     'arflow_sparsify_sums': [c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp],
     'arflow_calib_rows': [c_i, c_i],
     'arflow_calib_hist': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_restore_out': [c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_flow_stats': [c_fp, c_l, c_i, c_fp, c_i, c_i, c_i, c_fp],
+    'arflow_flow_render': [c_fp, c_l, c_i, c_fp, c_i, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'arflow_scalar_stats': [c_fp, c_l, c_i, c_fp, c_i, c_i, c_i, c_fp],
+    'arflow_scalar_render': [c_fp, c_l, c_i, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
 }
 
 ABI_VERSION = 10

@@ -1109,6 +1109,42 @@ int arflow_smooth_pen_bwd(const float* flow, const float* img, const float* coef
                           long flow_bstride, float flow_scale, float alpha, int order, int wmode, const arflow_penalty_t* pen,
                           arflow_stream_t stream);
 
+/* ---- Flow rendering and original-size restore (csrc/render.hip) ---------------------------------
+ * Layouts of a flow argument, and the two output kinds of the render entry points. */
+#define ARFLOW_LAYOUT_NCHW 0 /* [B,2,H,W], planes dense, samples flow_bstride floats apart */
+#define ARFLOW_LAYOUT_NHWC 1 /* [B,H,W,2], pixels dense, samples flow_bstride floats apart */
+#define ARFLOW_RENDER_U8 0   /* uint8, trunc(255 c) of the fp32 product: [B,H,W,3] (flow) / [B,H,W] (scalar) */
+#define ARFLOW_RENDER_F32 1  /* float32: [B,3,H,W] planar (flow) / [B,H,W] (scalar) */
+#define ARFLOW_RENDER_RGB 0   /* np_flow2rgb, utils/flow_utils.py:84-96 */
+#define ARFLOW_RENDER_WHEEL 1 /* flow_to_image, utils/flow_utils.py:67-81 (hsv wheel) */
+/* inference.py:98-107 in one pass: flow [B,2,h,w] (samples flow_bstride >= 2 h w floats apart: a channel slice is read in
+ * place) -> out_flow [B,H,W,2] dense, the half-pixel bilinear resize (rf_axis of csrc/resize_dev.hpp with align = 0) with
+ * u times W / w and v times H / h (the product formed in float64, rounded once).  ent (nullable, same layout rule, stride
+ * ent_bstride) -> out_ent [B,H,W,2], the same resize plus 2 log W - 2 log w on channel 0 and 2 log H - 2 log h on channel 1;
+ * ent and out_ent are given together or not at all (else ARFLOW_ENULL).  stats (nullable) [B,2]: per sample, over the stored
+ * out_flow, (max(|u|, |v|), max(u, v)); integer atomic maxima on the float bits, so the result does not depend on the order
+ * (bitwise repeatable, allowed in deterministic mode).  A NaN in the flow leaves its sample's stats unspecified.
+ * Launches: one kernel; with stats, a B-lane kernel in front of it that stores the identities (0, -inf). */
+int arflow_restore_out(const float* flow, long flow_bstride, const float* ent, long ent_bstride, float* out_flow,
+                       float* out_ent, float* stats, int B, int h, int w, int H, int W, arflow_stream_t stream);
+/* the same stats [B,2] of a flow that is already at its final size, in either layout */
+int arflow_flow_stats(const float* flow, long flow_bstride, int layout, float* stats, int B, int H, int W,
+                      arflow_stream_t stream);
+/* flow -> colour.  scale: sample b is normalised by scale[b * scale_stride] (so scale may point at either column of stats
+ * with scale_stride = 2); a scale that is not positive and finite renders white (normalised flow 0 / saturation 0).
+ * mode RGB: n = f / scale, (1 + n_u, 1 - 0.5 (n_u + n_v), 1 + n_v) clipped to [0,1], the reference's fp32 sequence.
+ * mode WHEEL: h = mod(atan2(v,u) / 2 pi + 1, 1), s = clip(8 |f| / scale), val = clip(8 - s), matplotlib's hsv_to_rgb.
+ * out: uint8 [B,H,W,3] (ARFLOW_RENDER_U8) or float [B,3,H,W] (ARFLOW_RENDER_F32), dense. */
+int arflow_flow_render(const float* flow, long flow_bstride, int layout, const float* scale, int scale_stride, void* out,
+                       int out_kind, int mode, int B, int H, int W, arflow_stream_t stream);
+/* uflow_elbo_trainer.py:259-262: e = sum over the C (1 .. 16) channels of x [B,C,H,W] (samples x_bstride floats apart), added
+ * in channel order.  arflow_scalar_stats: minmax [2] = (min e, max e) over the WHOLE batch (atomics as above, identities
+ * stored by a one-lane kernel in front).  arflow_scalar_render: (e - min) / (max - min) as float or trunc(255 .) uint8
+ * [B,H,W]; max == min (a constant map) renders 0. */
+int arflow_scalar_stats(const float* x, long x_bstride, int C, float* minmax, int B, int H, int W, arflow_stream_t stream);
+int arflow_scalar_render(const float* x, long x_bstride, int C, const float* minmax, void* out, int out_kind, int B, int H,
+                         int W, arflow_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

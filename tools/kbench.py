@@ -9,6 +9,7 @@ fraction of the 8 TB/s HBM roofline.  Calls the C ABI directly (no autograd over
     python tools/kbench.py --filter optim          # the fused optimiser step against torch.optim.Adam(fused=True)
     python tools/kbench.py --filter ar             # the AR transform and loss, fused against composed ATen ops
     python tools/kbench.py --filter penalty_em     # one EM update of the penalty fit and log_gmm against their torch formulations
+    python tools/kbench.py --filter render         # restore + stats + flow picture, fused against composed ATen ops
     python tools/kbench.py --filter elbo_penalty   # one UFlowElboLoss step with the fitted mixture penalties against the default step and the unfused composition
 """
 import argparse
@@ -791,6 +792,75 @@ def ar_bench(dev, jsonl, B=8, hw=(384, 640), launches=20, repeats=5, steps=10):
         out.write(json.dumps(line) + '\n')
 
 
+def render_bench(dev, jsonl, B=8, hw=(384, 640), out_hw=(436, 1024), launches=20, repeats=5):
+    """what arflow_amd.predict does per batch after the model call -- the flow [B,2,h,w] restored to
+    NHWC at the original size with its per-sample statistics (arflow_amd.render.restore, one pass) and the uint8 flow picture
+    normalised by the sample's max |f| (flow_rgb, one pass) -- next to the same outputs composed of ATen operations on the same
+    device: F.interpolate, the two scalings, permute().contiguous(), abs / amax, the colour expression and .to(torch.uint8).  The
+    parent has no such path, so the composition is the baseline.  HIP events around `launches` calls after 5 warm-ups, the
+    versions in alternation, `repeats` rounds: median (min .. max).  Bytes: what each side's operations read and write, counted
+    per operation from the shapes (an elementwise ATen operation reads its inputs and writes its output once)."""
+    import statistics
+    import torch.nn.functional as F
+    from arflow_amd import render
+    (h, w), (H, W) = hw, out_hw
+    flow = 6.0 * torch.randn(B, 2, h, w, device=dev, generator=torch.Generator(device=dev).manual_seed(0))
+    scale = torch.tensor([W / w, H / h], device=dev).view(1, 2, 1, 1)
+
+    def fused():
+        r = render.restore(flow, out_hw, stats=True)
+        return r.flow, render.flow_rgb(r.flow, 'rgb', layout='nhwc', stats=r.stats)
+
+    def composed():
+        up = F.interpolate(flow, out_hw, mode='bilinear', align_corners=False) * scale
+        nhwc = up.permute(0, 2, 3, 1).contiguous()
+        n = up / up.abs().amax((1, 2, 3), keepdim=True)
+        c = torch.stack([1 + n[:, 0], 1 - 0.5 * (n[:, 0] + n[:, 1]), 1 + n[:, 1]], -1).clamp(0, 1)
+        return nhwc, (c * 255.0).to(torch.uint8)
+    small, big = 4 * B * 2 * h * w, 4 * B * 2 * H * W  # the flow at the test size / at the original size, in bytes
+    plane = big // 2
+    bytes_fused = (small + big) + (big + 3 * B * H * W)  # restore: in, out;  picture: in, out
+    # interpolate (in, out), * scale (r, w), permute copy (r, w), abs (r, w), amax (r), / (r, w), 1 + n_u (r, w), n_u + n_v (2r, w),
+    # 0.5 * (r, w), 1 - (r, w), 1 + n_v (r, w), stack (3r, 3w), clamp (3r, 3w), * 255 (3r, 3w), to uint8 (3r, 3 B H W)
+    bytes_composed = (small + big) + 2 * big + 2 * big + 2 * big + big + 2 * big + 2 * plane + 3 * plane + 2 * plane + 2 * plane \
+        + 2 * plane + 6 * plane + 6 * plane + 6 * plane + 3 * plane + 3 * B * H * W
+    fns = {'fused': fused, 'composed ATen': composed}
+    a, b = fused(), composed()
+    diff_flow = float((a[0] - b[0]).abs().max())
+    diff_u8 = int((a[1].int() - b[1].int()).abs().max())
+    del a, b
+    t = {name: [] for name in fns}
+    for _ in range(repeats):
+        for name, fn in fns.items():
+            t[name].append(timeit(fn, launches))
+            MANIFEST[-1].update(name='render/' + name, shape=[])
+    line = {'bench': 'render', 'shape': [B, 2, h, w], 'out_hw': [H, W], 'bytes_fused': bytes_fused, 'bytes_composed': bytes_composed,
+            'max_abs_diff_flow': diff_flow, 'max_abs_diff_u8': diff_u8}
+    for name, v in t.items():
+        key = name.split()[0]
+        line.update({key + '_us': statistics.median(v), key + '_us_min': min(v), key + '_us_max': max(v)})
+        print('render %-14s %9.1f us (%.1f .. %.1f)' % (name, statistics.median(v), min(v), max(v)), flush=True)
+    # the device's share of the fused call: HIP events around each entry point (AF.start_kernel_timing), 20 calls after the warm-up
+    from arflow_amd import functional as AF
+    AF.start_kernel_timing()
+    for _ in range(launches):
+        fused()
+    per_call = {name: statistics.median(ms) * 1e3 for (name, _), ms in AF.stop_kernel_timing().items()}
+    line['entry_point_us'] = per_call
+    dev_us = sum(per_call.values())
+    for name, us in per_call.items():
+        print('render   %-20s %7.1f us between events' % (name, us), flush=True)
+    gbs = bytes_fused / line['fused_us'] / 1e3
+    line.update(fused_gbs=gbs, fused_fraction_of_hbm_peak=gbs / HBM_PEAK_GBS, hbm_peak_gbs=HBM_PEAK_GBS,
+                composed_over_fused=line['composed_us'] / line['fused_us'], entry_points_us=dev_us,
+                entry_points_gbs=bytes_fused / dev_us / 1e3)
+    print('render composed / fused = %.2f   fused %.0f GB/s = %.1f%% of HBM peak   bytes %.1f MB against %.1f MB   (max |diff| flow '
+          '%.1e, picture %d levels)' % (line['composed_over_fused'], gbs, 100 * gbs / HBM_PEAK_GBS, bytes_fused / 1e6,
+                                        bytes_composed / 1e6, diff_flow, diff_u8), flush=True)
+    with open(jsonl, 'a') as out:
+        out.write(json.dumps(line) + '\n')
+
+
 def optim_bench(dev, jsonl, launches=20, repeats=5):
     """arflow_amd.optim.FlatOptimizer.step() (one launch; two with the clip) on the parameters of
     PWCProbFlow [2,2,0] (5,909,172 elements) under the train section of configs/chairs_uflow_elbo.json, next to what TrainStep
@@ -1570,6 +1640,8 @@ def main():
         optim_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'optim_kbench.jsonl'))
     if want('ar'):  # the AR transform and loss (csrc/ar.hip) against the same arithmetic composed of ATen operations
         ar_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'ar_kbench.jsonl'))
+    if want('render'):  # restore + stats + flow picture (csrc/render.hip) against the same outputs composed of ATen operations
+        render_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'render_kbench.jsonl'))
     if want('penalty_em'):  # one EM update and log_gmm (csrc/penalty_em.hip) against the reference's formulation in torch ops
         penalty_em_bench(dev, args.jsonl or os.path.join(ROOT, 'profiles', 'penalty_em_kbench.jsonl'))
     if want('elbo_penalty'):  # one UFlowElboLoss step: default penalties, the fitted mixtures, and the mixtures composed of unpenalised nodes
